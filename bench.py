@@ -19,6 +19,10 @@ before the timed region (config C4 streams new chunks into them DURING it: that 
 nsteps; the deterministic roofline number).  The realistic early-out LMIP mode is in the ``lmip`` block.
 The timed region of K steps is repeated (``spread``) and also run with one frame at a time (``sequential``).
 
+``--dump-outputs DIR`` writes the planes the last frame of each mode's K-step region handed its caller (C4: of each
+fly-through run) as ``DIR/<region>_<plane>.npy``, so that two builds can be compared output for output on the same
+seeded inputs; ``dump_outputs`` says how a frame larger than the size limit is sampled.
+
 N > 1 (launched by torch.distributed.run): rings replicated per GPU, the frame dealt to ranks in interleaved
 row bands (``--tiling rows``) or as config 3's literal grid (``--tiling 2x4``), one gather of every rank's
 planes to rank 0 per frame over RCCL (``svr_gather_tiles``) + an un-tile kernel; strong scaling.
@@ -95,7 +99,13 @@ def parse():
     ap.add_argument("--pace-hz", type=float, default=120.0,
                     help="C4: also run the fly-through with frames released at this rate, like a display (0: skip), reported as `paced`")
     ap.add_argument("--store-dir", default=None, help="C4 --source zarr3: where to write the store (default: a fresh directory under $TMPDIR)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the planes the last frame of each timed region handed its caller as "
+                         "DIR/<region>_<plane>.npy (a seeded sample of pixels when they exceed the size limit; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -250,6 +260,45 @@ def summarise(ms):
 
     a = np.sort(np.asarray(ms, float))
     return {"n": int(a.size), "median_ms": float(np.median(a)), "min_ms": float(a[0]), "max_ms": float(a[-1])}
+
+
+DUMP_BYTES = 60_000_000   # --dump-outputs: bytes of array data at most (under 64 MB with the .npy headers)
+DUMP_SEED = 0
+
+
+def dump_outputs(path, kept):
+    """Writes `kept` ({region: {plane: tensor [h, w, ...]}}, every plane of one frame size) as
+    ``path/<region>_<plane>.npy``: float planes as float32, flags as float32, labels (uint32 bit patterns) as float64.
+    When all of it exceeds DUMP_BYTES, every plane keeps the same seeded sample of pixels, in raster order, and
+    ``pixel_index.npy`` (float64) holds their row-major indices.  Returns what was written, for the result line."""
+    import numpy as np
+
+    arrays = {}
+    for region, planes in kept.items():
+        for plane, t in planes.items():
+            a = t.cpu().numpy()
+            if a.dtype.kind in "iu" and a.dtype.itemsize == 4:
+                a = a.view(np.uint32).astype(np.float64)
+            else:
+                a = a.astype(np.float32)
+            arrays[f"{region}_{plane}"] = a
+    if not arrays:
+        return None
+    h, w = next(iter(arrays.values())).shape[:2]
+    npix = h * w
+    assert all(a.shape[:2] == (h, w) for a in arrays.values()), {k: a.shape for k, a in arrays.items()}
+    per_pixel = sum(a.nbytes for a in arrays.values()) // npix
+    taken = npix
+    if per_pixel * npix > DUMP_BYTES:
+        taken = DUMP_BYTES // (per_pixel + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(npix, size=taken, replace=False))
+        arrays = {k: a.reshape(npix, *a.shape[2:])[idx] for k, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "arrays": sorted(arrays), "pixels": int(taken), "frame_pixels": int(npix),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def main():
@@ -409,8 +458,9 @@ def main():
         def loop(self, F, prime_s=0.0):
             return FrameLoop(self, F, prime_s)
 
-        def timed(self, loop, mode, nframes, warmup):
-            """W untimed frames, then EXACTLY nframes bracketed by barrier + synchronize; max over ranks."""
+        def timed(self, loop, mode, nframes, warmup, keep=None):
+            """W untimed frames, then EXACTLY nframes bracketed by barrier + synchronize; max over ranks.  `keep` (a dict)
+            receives device copies of what the last timed frame handed its caller, taken after the clock stopped."""
             self.set_mode(mode == "full")
             # block -> tile placement: with several frames in flight the next frame's head fills this frame's tail anyway,
             # and the camera-independent table (policy 7) is ~1 % faster; one frame at a time wants the cost-sorted one
@@ -425,12 +475,14 @@ def main():
             torch.cuda.synchronize()
             t = time.perf_counter()
             for _ in range(nframes):
-                loop.frame()
+                res = loop.frame()
             loop.drain()                                     # the K-th frame's gather + un-tile are inside the timed region
             torch.cuda.synchronize()
             if collective:
                 dist.barrier()
             dt = time.perf_counter() - t
+            if keep is not None:
+                keep.update(loop.outputs(res))
             if collective:
                 tt = torch.tensor([dt], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -451,9 +503,10 @@ def main():
                     "svr_time_render")
             return float(ms.value)
 
-        def measure(self, in_flight, prime_s):
+        def measure(self, in_flight, prime_s, keep=None):
             """Exact step / hit / pixel counts (instrumented kernel, untimed), the contract's K-step region (+ repeats,
-            + one frame at a time) per mode, and the kernel alone."""
+            + one frame at a time) per mode, and the kernel alone.  `keep` ({mode: dict}): the last frame of each mode's
+            K-step region (`timed`)."""
             counts = {}
             for mode in modes:
                 self.set_mode(mode == "full")
@@ -462,7 +515,8 @@ def main():
             seq = loop if loop.F == 1 else self.loop(1)
             dts = {}
             for mode in modes:
-                first = self.timed(loop, mode, steps, args.warmup)                       # the contract's K steps
+                first = self.timed(loop, mode, steps, args.warmup,                       # the contract's K steps
+                                   keep=None if keep is None else keep.setdefault(mode, {}))
                 more = [self.timed(loop, mode, steps, 0) for _ in range(max(0, args.repeats - 1))]
                 one = [self.timed(seq, mode, steps, 1 if i == 0 else 0) for i in range(max(1, args.repeats))]
                 dts[mode] = (first, [first] + more, one)
@@ -519,6 +573,16 @@ def main():
                     p = self.planes_of(res)
                     tiled.gather_async(tuple(t.cpu() for t in p) if want_all else p.cpu(), slot, dst=0)   # gloo rehearsal
             return res
+
+        def outputs(self, res):
+            """Device copies (the loop reuses its buffers) of the planes a caller holds after frame `res`: its
+            RenderResult, or on N > 1 the frame gathered on rank 0 (nothing on the other ranks)."""
+            if not collective:
+                return {p: getattr(res, p).clone() for p in ("rgba", "depth", "label", "flags")}
+            if self.last is None:
+                return {}
+            names = ("rgba", "depth", "label") if want_all else ("rgba",)
+            return {p: t.clone() for p, t in zip(names, self.last if want_all else (self.last,))}
 
         def drain(self):
             if collective:
@@ -623,8 +687,9 @@ def main():
         return blk
 
     result = None
+    kept = {} if args.dump_outputs else None          # timed region -> its last frame's planes (--dump-outputs)
     if cfg != "C4":
-        m = harness.measure(args.in_flight, args.prime_s)
+        m = harness.measure(args.in_flight, args.prime_s, keep=kept)
         counts, loop = m["counts"], m["loop"]
         if rank == 0:
             dens = "u8" if args.source_dtype == "uint8" else "u16"
@@ -703,10 +768,12 @@ def main():
         path_steps = [instrumented(c)["steps"] for c in cams[args.warmup:]]
         loop = harness.loop(1)
 
-        def fly(mode, asynchronous, pace_hz=0.0):
+        def fly(mode, asynchronous, pace_hz=0.0, name=None):
             """Back to the start, W untimed frames, then K timed ones; per-frame wall times (frame k = enqueue the render,
             move the ring windows while it runs, wait for it as a display would).  `pace_hz` > 0: frames are released at
-            that rate, like a display's refresh (the wait for the next slot is not part of a frame's time)."""
+            that rate, like a display's refresh (the wait for the next slot is not part of a frame's time).  With
+            --dump-outputs the last frame is kept as `kept[name]`; its pixels depend on which asynchronous loads had
+            landed when it was drawn."""
             set_mode(mode == "full")
             vol.poll_uploads(wait=True)
             vol.center_on_position(poses[0][0])                            # blocking: rings as at the start
@@ -727,7 +794,7 @@ def main():
                     torch.cuda.synchronize()
                     t_start = time.perf_counter()
                 t = time.perf_counter()
-                loop.frame(cams[k])                                            # enqueue the draw ...
+                res = loop.frame(cams[k])                                      # enqueue the draw ...
                 loop.drain()
                 vol.center_on_position(eye, asynchronous=asynchronous)         # ... plan / start the window moves beside it
                 torch.cuda.current_stream(dev).synchronize()                   # (the order of the reference's do_draw:
@@ -739,6 +806,8 @@ def main():
             if collective:
                 dist.barrier()
             dt = time.perf_counter() - t_start
+            if kept is not None:
+                kept[name or mode] = loop.outputs(res)
             if pace_hz > 0.0:
                 time.sleep(1.0 / pace_hz)                                      # the last frame's own requests get one slot too
             landed = vol.poll_uploads(wait=False)
@@ -772,9 +841,9 @@ def main():
             # the same path released at a display's rate: what the streaming front-end is for.  Unpaced, the march outruns
             # any source (several hundred frames per second ask for GB/s of new chunks) and superseded requests are
             # dropped; paced, every load should land before the next window move asks for more
-            runs["paced"] = fly("lmip" if "lmip" in modes else "full", True, pace_hz=args.pace_hz)
+            runs["paced"] = fly("lmip" if "lmip" in modes else "full", True, pace_hz=args.pace_hz, name="paced")
         if args.blocking_too:
-            runs["full_blocking"] = fly("full", False)
+            runs["full_blocking"] = fly("full", False, name="full_blocking")
         if rank == 0:
             r = runs["full"]
             result = {
@@ -917,6 +986,8 @@ def main():
             rep["transport"] = transport
             result["check" if world > 1 else "check_gathered"] = rep
     if rank == 0:
+        if kept is not None:
+            result["dump_outputs"] = dump_outputs(args.dump_outputs, kept)
         print(json.dumps(result), flush=True)
     if collective:
         dist.barrier()

@@ -91,6 +91,41 @@ def test_summarise():
     assert s == {"n": 3, "median_ms": 2.0, "min_ms": 1.0, "max_ms": 3.0}
 
 
+def _frame_planes(h, w, seed):
+    import torch
+
+    g = torch.Generator().manual_seed(seed)
+    return {"rgba": torch.rand(h, w, 4, generator=g), "depth": torch.rand(h, w, generator=g),
+            "label": torch.randint(-2 ** 31, 2 ** 31 - 1, (h, w), generator=g, dtype=torch.int32),
+            "flags": torch.randint(0, 3, (h, w), generator=g, dtype=torch.uint8)}
+
+
+@pytest.mark.parametrize("h, w", [(120, 160), (1080, 1920)])
+def test_dump_outputs_writes_float_planes_of_one_seeded_pixel_sample_within_the_size_limit(tmp_path, h, w):
+    """bench.py --dump-outputs: every plane as float32 / float64 (labels as their exact uint32 value), the whole frame
+    when it fits, else the same seeded pixels of every plane, the same ones on every run, and never more than 64 MB."""
+    kept = {"full": _frame_planes(h, w, 1), "lmip": _frame_planes(h, w, 2)}
+    info = bench.dump_outputs(str(tmp_path / "a"), kept)
+    again = bench.dump_outputs(str(tmp_path / "b"), kept)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) == [n + ".npy" for n in info["arrays"]]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64e6
+    sampled = h * w * 64 > bench.DUMP_BYTES
+    assert ("pixel_index.npy" in files) == sampled and info["frame_pixels"] == h * w
+    idx = np.load(tmp_path / "a" / "pixel_index.npy").astype(np.int64) if sampled else np.arange(h * w)
+    assert idx.size == info["pixels"] and np.all(np.diff(idx) > 0)
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    for region, planes in kept.items():
+        for plane, t in planes.items():
+            want = t.numpy()
+            want = want.view(np.uint32) if plane == "label" else want
+            want = want.reshape(h * w, *want.shape[2:])[idx]
+            got = np.load(tmp_path / "a" / f"{region}_{plane}.npy").reshape(want.shape)
+            assert np.array_equal(got, want.astype(got.dtype)) and np.array_equal(got.astype(want.dtype), want), (region, plane)
+
+
 def test_config4_corridor_store_holds_exactly_what_the_flythrough_reads(tmp_path):
     """bench.py --config C4 --source zarr3 at a rehearsal size: the sparse zarr v3 store written during setup holds
     every voxel any `center_on_position` window of the path can request (equal to the lazily generated volume there),
