@@ -35,7 +35,7 @@ extern "C" {
 
 #define SVR_MAX_LODS 8
 #define SVR_MAX_CLIP_PLANES 8
-#define SVR_ABI_VERSION 7
+#define SVR_ABI_VERSION 8
 
 typedef enum svr_status {
     SVR_OK = 0,
@@ -330,6 +330,44 @@ typedef struct svr_compose_params {
 } svr_compose_params;
 int  svr_compose(svr_ctx* ctx, const float* rgba, const float* depth, const uint8_t* flags, int width, int height,
                  const svr_compose_params* params, uint8_t* out_rgba8, float* inout_depth, void* stream);
+
+/* ---- display side: segmentation outlines and selected-object highlighting (FUTURE.md "Tracing Objects": a second
+ * pass that finds label edges in the rendered label image and draws them over the intensity image).  Inputs are the
+ * planes of one render, each height x width: F = flags (SVR_PIX_*), L = label, Z = depth (optional), S = rgba.
+ * Defined HERE (numpy restatement: tests/test_outline.py `outline_reference`) as
+ *     hit(p)       F(p) == SVR_PIX_HIT
+ *     N_r(p)       the pixels q != p INSIDE the image with max(|dy|, |dx|) <= r  (the image border draws no outline)
+ *     selected(p)  selected_count == 0, or L(p) is one of selected[0 .. selected_count)
+ *     edge(p)      hit(p) and (!only_selected or selected(p)) and some q in N_r(p) has
+ *                    !hit(q)                                   (silhouette against a miss or a discard), or
+ *                    hit(q) and L(q) != L(p), or
+ *                    depth_tolerance >= 0 and hit(q) and |Z(q) - Z(p)| > depth_tolerance   (units of the depth plane)
+ *     out(p)       f32, in this order:
+ *                    !hit(p): S(p), bit for bit;
+ *                    else b = S(p), and if selected_count > 0 and !selected(p): b.rgb = S.rgb * dim_unselected;
+ *                    edge(p): c = color.rgb, or with color_by_label hsv_to_rgb(h, s, 1.0f) of colors[L(p) % color_count]
+ *                             (hsv_selection.wgsl: no fog, no srgb2physical), a = color[3],
+ *                             out.rgb = b.rgb * (1 - a) + c * a,  out.a = b.a * (1 - a) + a;
+ *                    otherwise out = b.
+ *     edge_mask(p) 1 where edge(p), else 0 (u8).
+ * DEVICE pointers; depth may be NULL when depth_tolerance < 0, edge_mask may be NULL.  rgba, out_rgba and colors are
+ * 16-byte aligned.  `selected` is sorted ascending (an unsorted set gives wrong highlighting but never reads outside
+ * it).  out_rgba may be rgba itself (in place): a pixel's output depends on its own rgba alone.  A plane rendered with
+ * a region (svr_frame) is outlined as an image of its own: pixels outside it are not neighbours.  Enqueued on
+ * `stream`. */
+typedef struct svr_outline_params {
+    int32_t radius;                /* r, 1 .. 16 */
+    float   depth_tolerance;       /* < 0: off */
+    int32_t color_by_label;
+    float   color[4];              /* rgb used unless color_by_label; [3] = outline opacity in [0, 1] */
+    float   dim_unselected;        /* [0, 1]; only used when selected_count > 0 */
+    int32_t only_selected;
+} svr_outline_params;
+int  svr_outline(svr_ctx* ctx, const float* rgba, const float* depth, const uint32_t* label, const uint8_t* flags,
+                 int width, int height, const svr_outline_params* params,
+                 const float* colors, uint32_t color_count,          /* color_count x vec4 (h, s, v, pad) */
+                 const uint32_t* selected, uint32_t selected_count,
+                 float* out_rgba, uint8_t* edge_mask, void* stream);
 
 /* ---- sync */
 int  svr_sync(svr_ctx* ctx);                 /* both streams idle */

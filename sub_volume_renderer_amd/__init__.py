@@ -9,6 +9,7 @@ device work raises if ``csrc/libsvr_hip.so`` has not been built.
 
 from ._geometry import Coordinate, Roi
 from .compose import compose
+from .outline import outline
 from ._material import SubVolumeMaterial
 from ._transform import AffineTransform, PerspectiveCamera
 from ._wobject import FrameRegion, RenderResult, SubVolume
@@ -28,4 +29,5 @@ __all__ = [
     "subtract_rois",
     # display-side output of a render (pygfx's job in the reference)
     "compose",
+    "outline",
 ]

