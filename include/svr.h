@@ -35,7 +35,7 @@ extern "C" {
 
 #define SVR_MAX_LODS 8
 #define SVR_MAX_CLIP_PLANES 8
-#define SVR_ABI_VERSION 8
+#define SVR_ABI_VERSION 9
 
 typedef enum svr_status {
     SVR_OK = 0,
@@ -264,7 +264,8 @@ int  svr_render(svr_ctx* ctx, const svr_camera* cam, const svr_frame* frame,
  *            stretches whose macro-cell maxima stay below the threshold while no lane tracks a maximum)
  * bits 4-7  1 + log2(wave tile width): wave tile = 2^k x 64/2^k pixels (0 = default 8x8)
  * bit  8    never stage LDS bricks nor gather from a micro-block twin (linear gathers only); bit 9: always
- *            (default: per-wave probe)
+ *            (default: per-wave probe).  svr_slice reads these two bits too: 8 = rows only, 9 = the micro-block copy
+ *            wherever a LOD keeps one (default: per LOD, the layout whose 128-byte lines a wave's tile touches fewer of)
  * bit  10   keep row-major lane order (default: lanes follow the projected x axis)
  * bits 11-12 reserved: SVR_ERR_INVALID.  (Builds made with -DSVR_EXPERIMENTS — tools/ab_build.py, never the shipped
  *            library — use them for timing experiments that render WRONG pixels, and read the SVR_* environment
@@ -368,6 +369,48 @@ int  svr_outline(svr_ctx* ctx, const float* rgba, const float* depth, const uint
                  const float* colors, uint32_t color_count,          /* color_count x vec4 (h, s, v, pad) */
                  const uint32_t* selected, uint32_t selected_count,
                  float* out_rgba, uint8_t* edge_mask, void* stream);
+
+/* ---- cross-section views: the LOD rings sampled on a world-space plane (no counterpart in the reference; the planar
+ * view that EM viewers pair with the 3-D one).  A slice is an image of frame_w x frame_h pixels on the plane through
+ * `origin` (world position of the image centre) spanned by `u` (world step from one column to the next) and `v` (from
+ * one row to the next; rows go down the image).  Output pixels map to frame pixels (x, y) through svr_frame exactly as
+ * in svr_render (tiles and stripes alike; frame pixels outside the frame are DISCARD).  Defined HERE (numpy
+ * restatement: tests/slice_twin.py) as, in f32, in this order, with no fused operations:
+ *     fx   = ((float)x + 0.5f) - 0.5f * (float)frame_w,   fy = ((float)y + 0.5f) - 0.5f * (float)frame_h
+ *     p_k  = (origin_k + fx * u_k) + fy * v_k                         world position
+ *     q    = world_inv * (p, 1)  in the march's mat_vec summation order ((m0 x + m4 y) + m8 z) + m12;  d = q.xyz
+ *     c_k  = (d_k + 0.5f) / size_k                                    the march's normalised coordinate
+ *     dx_k = c_k * size_k                                             as sample_vol.wgsl:6 computes it
+ * classified from dx:
+ *     DISCARD  not 0 <= dx_k < size_k on every axis (NaN is outside):  rgba (0,0,0,0), value 0, label 0, lod 255
+ *     HIT      the first LOD l whose ROI holds dx (the march's try_sample_scale_i test, sample_vol.wgsl:4-25):
+ *                value = that LOD's density texel (f32), label = its label texel (0 without label rings), lod = l,
+ *                v = (value - clim[0]) / (clim[1] - clim[0]);  v = powf(v, gamma) if gamma != 1;
+ *                v = srgb2physical(v) if colorspace_srgb;  rgb = hsv_to_rgb(h, s, v) of colors[label % color_count];
+ *                rgba = (rgb, opacity)                             (the march's shading without fog)
+ *     MISS     inside the box, but no LOD's ROI holds it (not resident): rgba (0,0,0,1), value 0, label 0, lod 255
+ * depth is 0 everywhere (a slice has no camera).  The material's fog, LMIP uniforms, render mode and clipping planes
+ * are not read.  A slice pixel thus shows exactly the voxel a ray sample at that point would read.
+ * Reads the LOD state of svr_set_lod_state and the material of svr_set_material.  A render-thread call: it waits for
+ * published uploads and later uploads are ordered behind it, like svr_render.  Enqueued on `stream`; asynchronous. */
+typedef struct svr_slice_plane {
+    float world_inv[16];           /* column-major, like svr_camera */
+    float volume_dimensions[3];    /* shader order (x, y, z) */
+    float origin[3];               /* world space */
+    float u[3];
+    float v[3];
+} svr_slice_plane;
+/* DEVICE pointers, out_h*out_w elements each (rgba: x4, 16-byte aligned).  Any pointer except rgba may be NULL. */
+typedef struct svr_slice_outputs {
+    float*    rgba;
+    float*    depth;               /* 0 */
+    uint32_t* label;
+    uint8_t*  flags;               /* SVR_PIX_* */
+    float*    value;               /* the density texel, 0 where nothing was hit */
+    uint8_t*  lod;                 /* the LOD the texel came from, 255 where nothing was hit */
+} svr_slice_outputs;
+int  svr_slice(svr_ctx* ctx, const svr_slice_plane* plane, const svr_frame* frame, const svr_slice_outputs* out,
+               void* stream);
 
 /* ---- sync */
 int  svr_sync(svr_ctx* ctx);                 /* both streams idle */

@@ -12,7 +12,7 @@ from .compose import compose
 from .outline import outline
 from ._material import SubVolumeMaterial
 from ._transform import AffineTransform, PerspectiveCamera
-from ._wobject import FrameRegion, RenderResult, SubVolume
+from ._wobject import FrameRegion, RenderResult, SliceResult, SubVolume
 from ._wrapping_buffer import WrappingBuffer, subtract_rois
 
 __all__ = [
@@ -26,6 +26,7 @@ __all__ = [
     "AffineTransform",
     "FrameRegion",
     "RenderResult",
+    "SliceResult",
     "subtract_rois",
     # display-side output of a render (pygfx's job in the reference)
     "compose",

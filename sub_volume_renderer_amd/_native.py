@@ -119,6 +119,20 @@ class OutlineParams(C.Structure):
     ]
 
 
+class SlicePlane(C.Structure):
+    _fields_ = [
+        ("world_inv", C.c_float * 16),
+        ("volume_dimensions", C.c_float * 3),
+        ("origin", C.c_float * 3),
+        ("u", C.c_float * 3),
+        ("v", C.c_float * 3),
+    ]
+
+
+class SliceOutputs(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("rgba", "depth", "label", "flags", "value", "lod")]
+
+
 _I3 = C.c_int32 * 3
 _L3 = C.c_int64 * 3
 
@@ -161,6 +175,7 @@ SIGNATURES = {
     "svr_outline": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                               C.POINTER(OutlineParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "svr_slice": (C.c_int, [C.c_void_p, C.POINTER(SlicePlane), C.POINTER(Frame), C.POINTER(SliceOutputs), C.c_void_p]),
     "svr_sync": (C.c_int, [C.c_void_p]),
     "svr_sync_uploads": (C.c_int, [C.c_void_p]),
     "svr_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),

@@ -65,6 +65,38 @@ class RenderResult:
         return self.label.cpu().numpy().view(np.uint32)
 
 
+@dataclass
+class SliceResult(RenderResult):
+    """Device tensors written by one cross-section (``svr_slice``): the planes of a render (``steps`` and ``pick`` are
+    None, depth is 0) plus the density texel each pixel shows and the LOD it came from."""
+
+    value: "object | None" = None     # torch f32 [h, w]   density texel (0 where nothing was hit)
+    lod: "object | None" = None       # torch u8  [h, w]   LOD of that texel (255 where nothing was hit)
+
+
+_SLICE_PLANES = (("depth", "float32"), ("label", "int32"), ("flags", "uint8"), ("value", "float32"), ("lod", "uint8"))
+
+
+def _vec3(name, value):
+    """Three numbers that are finite as float32, the precision the kernel works in (a str is not a vector)."""
+    if isinstance(value, (str, bytes)):
+        raise ValueError(f"{name} must be three finite numbers")
+    try:
+        vals = np.array([float(c) for c in value], np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be three finite numbers") from None
+    if vals.shape != (3,) or not np.all(np.isfinite(vals)):
+        raise ValueError(f"{name} must be three finite numbers")
+    with np.errstate(over="ignore"):
+        vals = vals.astype(np.float32)
+    if not np.all(np.isfinite(vals)):
+        raise ValueError(f"{name} must be three numbers that are finite in float32")
+    return [float(c) for c in vals]
+
+
+_SLICE_CACHE_SIZES = 4      # output sets kept per volume: e.g. the three axis views of a viewer, each of its own size
+
+
 def _stop_upload_worker(jobs_queue, thread):
     """Let the upload thread finish what it holds and end (called by ``SubVolume.close`` or when a volume is collected)."""
     import threading
@@ -160,6 +192,7 @@ class SubVolume(_HasWorld):
         self._cam_cache = None
         self._frame_cache = {}
         self._ob_cache = {}
+        self._slice_cache = {}
         self._worker = None
         self._worker_error = None
         self._inflight = []
@@ -237,7 +270,7 @@ class SubVolume(_HasWorld):
         self._worker = None
         self._inflight.clear()
         self._completed = self._submitted
-        self._out_cache, self._ob_cache = {}, {}
+        self._out_cache, self._ob_cache, self._slice_cache = {}, {}, {}
         self._rings.close()
 
     # -- asynchronous streaming ------------------------------------------------------
@@ -471,6 +504,109 @@ class SubVolume(_HasWorld):
             N.lib().svr_render(handle, C.byref(cb), C.byref(fb), C.byref(ob), C.c_void_p(stream)),
             "svr_render",
         )
+        return res
+
+    # -- cross-sections ---------------------------------------------------------
+    @staticmethod
+    def axis_slice_plane(axis, center, pixel_size: float = 1.0):
+        """``(origin, u, v)`` of the axis-aligned slice through the world point ``center`` whose normal is the world
+        ``axis`` ("x", "y", "z" or 0, 1, 2), ``pixel_size`` world units per pixel: z-normal u = +x, v = +y; y-normal
+        u = +x, v = +z; x-normal u = +y, v = +z."""
+        key = {"x": 0, "y": 1, "z": 2}.get(axis, axis)
+        if isinstance(key, bool) or key not in (0, 1, 2):
+            raise ValueError("axis must be 'x', 'y', 'z', 0, 1 or 2")
+        origin = tuple(_vec3("center", center))
+        p = float(pixel_size)
+        with np.errstate(over="ignore"):
+            finite32 = bool(np.isfinite(np.float32(p)))
+        if not (finite32 and p > 0.0):
+            raise ValueError("pixel_size must be finite and > 0")
+        ua, va = {2: (0, 1), 1: (0, 2), 0: (1, 2)}[key]
+        u, v = [0.0, 0.0, 0.0], [0.0, 0.0, 0.0]
+        u[ua], v[va] = p, p
+        return origin, tuple(u), tuple(v)
+
+    def _slice_outputs(self, h, w):
+        import torch
+
+        res = self._slice_cache.pop((h, w), None)
+        if res is None:
+            dev = torch.device("cuda", self._rings.device if self._rings.device is not None else torch.cuda.current_device())
+            res = SliceResult(
+                rgba=torch.empty((h, w, 4), dtype=torch.float32, device=dev),
+                depth=torch.empty((h, w), dtype=torch.float32, device=dev),
+                label=torch.empty((h, w), dtype=torch.int32, device=dev),
+                flags=torch.empty((h, w), dtype=torch.uint8, device=dev),
+                steps=None,
+                value=torch.empty((h, w), dtype=torch.float32, device=dev),
+                lod=torch.empty((h, w), dtype=torch.uint8, device=dev),
+            )
+            while len(self._slice_cache) >= _SLICE_CACHE_SIZES:
+                del self._slice_cache[next(iter(self._slice_cache))]      # least recently used
+        self._slice_cache[(h, w)] = res
+        return res
+
+    def _check_slice_out(self, out, h, w):
+        import torch
+
+        if not isinstance(out, SliceResult):
+            raise ValueError("out must be a SliceResult")
+        if out.rgba is None:
+            raise ValueError("out.rgba is required")
+        planes = [(n, getattr(out, n), dt, s) for n, dt, s in
+                  [("rgba", "float32", (h, w, 4))] + [(n, dt, (h, w)) for n, dt in _SLICE_PLANES] if getattr(out, n) is not None]
+        for name, t, dt, shape in planes:
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"out.{name} must be a contiguous tensor of shape {list(shape)}")
+            if t.dtype != getattr(torch, dt):
+                raise ValueError(f"out.{name} must have dtype {dt}")
+        for name, t, _, _ in planes:
+            if t.device.type != "cuda" or (self._rings.device is not None and t.device.index != self._rings.device):
+                raise ValueError(f"out.{name} must be on the volume's GPU device")
+
+    def render_slice(self, origin, u, v, width: int, height: int, *, region: FrameRegion | None = None,
+                     out: SliceResult | None = None, stream=None) -> SliceResult:
+        """Sample the multi-LOD rings on a world-space plane into device tensors (definition: ``svr_slice`` in
+        include/svr.h).  ``origin`` is the world position of the image centre, ``u`` / ``v`` the world steps from one
+        column / row to the next (rows go down the image); world coordinates are those of the camera positions passed
+        to :meth:`render` (the volume's ``world`` transform applies).  Every pixel shows the voxel a ray sample at its
+        centre would read: the finest resident LOD's texel.  Asynchronous on the current torch stream.  Unless ``out`` is
+        given, the output tensors of a size are reused by the next call of that size (the last few sizes are kept), so
+        a result is overwritten by the next slice of its size."""
+        import torch
+
+        origin, u, v = _vec3("origin", origin), _vec3("u", u), _vec3("v", v)
+        for name, n in (("width", width), ("height", height)):
+            if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+                raise ValueError(f"{name} must be an integer >= 1")
+        width, height = int(width), int(height)
+        with np.errstate(all="ignore"):
+            normal = np.cross(np.array(u, np.float32), np.array(v, np.float32))      # float32, as the kernel steps
+        if not np.any(normal != 0):
+            raise ValueError("u and v must be nonzero and not parallel")
+        if region is not None:
+            stripes = 0 < region.band_h < region.out_h
+            if (region.x0 < 0 or region.y0 < 0 or region.out_w < 1 or region.out_h < 1
+                    or region.x0 + region.out_w > width
+                    or (region.y0 >= height if stripes else region.y0 + region.out_h > height)):
+                raise ValueError(f"region {region} does not fit the {width} x {height} frame")
+        fb = self.frame_block(width, height, region)
+        if out is not None:
+            self._check_slice_out(out, fb.out_h, fb.out_w)
+
+        handle = self.prepare()
+        res = out or self._slice_outputs(fb.out_h, fb.out_w)
+        pl = N.SlicePlane()
+        pl.world_inv = N.mat_to_c(self.world.inverse_matrix)
+        pl.volume_dimensions[:] = [float(c) for c in self._volume_dimensions]
+        pl.origin[:], pl.u[:], pl.v[:] = origin, u, v
+        ob = N.SliceOutputs()
+        for name in ("rgba",) + tuple(n for n, _ in _SLICE_PLANES):
+            t = getattr(res, name)
+            setattr(ob, name, t.data_ptr() if t is not None else None)
+        if stream is None:
+            stream = torch.cuda.current_stream(self._rings.device).cuda_stream
+        N.check(N.lib().svr_slice(handle, C.byref(pl), C.byref(fb), C.byref(ob), C.c_void_p(stream)), "svr_slice")
         return res
 
     def synchronize(self):

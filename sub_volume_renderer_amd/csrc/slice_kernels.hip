@@ -1,0 +1,236 @@
+// Cross-section views (svr_slice, include/svr.h): the march's sampling rule evaluated on a plane of pixels instead of
+// along rays.  One lane = one pixel; one wave64 = a 16 x 4 pixel tile, four waves per workgroup stacked into 16 x 16,
+// so that planes that are not x-normal still share L2 lines between neighbouring lanes.  No LDS.
+//
+// Arithmetic contract: strict IEEE f32 without contraction (-ffp-contract=off), operation order as written in svr.h.
+// The device helpers below are copies of the march's (march_kernel.hip), whose bytes are the kernel-source stamp
+// bench.py records and stay untouched; tests/test_gpu_slice.py holds both to the same numpy restatement.
+#include <math.h>
+#include <string.h>
+
+#include "svr_internal.h"
+
+namespace {
+
+struct SliceLod {
+    const void*     density;   // ring [z][y][x], element type per SliceParams::esh
+    const uint32_t* labels;    // null: no label rings
+    const void*     twin;      // micro-block copy to read from (svr_lod_desc::blocked_twin), or null: read the rows
+    int32_t  off[3];           // current_logical_offset_in_pixels
+    uint32_t shape[3];         // current_logical_shape_in_pixels
+    uint32_t wrap0[3];         // ring slot of the ROI's first voxel
+    uint32_t ring[3];
+    float    scale[3];
+};
+
+struct SliceParams {
+    float world_inv[16];
+    float size[3];
+    float origin[3], u[3], v[3];
+    svr_frame frame;
+    float clim0, clim1, gamma, opacity;
+    int32_t colorspace_srgb;
+    uint32_t color_count;
+    const float* colors;       // device, color_count x vec4 (h, s, v, pad)
+    int32_t esh;               // log2 of the density element size: 0 u8, 1 u16, 2 f32
+    float*    rgba;
+    float*    depth;
+    uint32_t* label;
+    uint8_t*  flags;
+    float*    value;
+    uint8_t*  lod;
+    SliceLod L[SVR_MAX_LODS];
+};
+
+struct f3 { float x, y, z; };
+
+// march_kernel.hip `wrap`: t in [0, shape), wrap0 in [0, ring) -> (t + wrap0) mod ring
+__device__ __forceinline__ uint32_t wrap(uint32_t t, uint32_t wrap0, uint32_t ring) {
+    const uint32_t w = t + wrap0;
+    return min(w, w - ring);
+}
+
+// march_kernel.hip `lod_texel` (sample_vol.wgsl:4-25), with the ring slot returned instead of a 32-bit-row index: the
+// caller forms a 64-bit element index (a float ring can exceed 4 GiB)
+__device__ __forceinline__ bool lod_slot(const SliceLod& L, float dx, float dy, float dz, uint32_t& wx, uint32_t& wy,
+                                         uint32_t& wz) {
+    const float sx = dx * L.scale[0], sy = dy * L.scale[1], sz = dz * L.scale[2];
+    const int ix = (int)sx, iy = (int)sy, iz = (int)sz;
+    const uint32_t tx = (uint32_t)(ix - L.off[0]), ty = (uint32_t)(iy - L.off[1]), tz = (uint32_t)(iz - L.off[2]);
+    if (!(tx < L.shape[0] && ty < L.shape[1] && tz < L.shape[2])) return false;
+    wx = wrap(tx, L.wrap0[0], L.ring[0]);
+    wy = wrap(ty, L.wrap0[1], L.ring[1]);
+    wz = wrap(tz, L.wrap0[2], L.ring[2]);
+    return true;
+}
+
+// march_kernel.hip `hsv_to_rgb` (hsv_selection.wgsl:7-41)
+__device__ __forceinline__ f3 hsv_to_rgb(float h, float s, float v) {
+    f3 r;
+    if (s == 0.0f) { r.x = v; r.y = v; r.z = v; return r; }
+    const float h_scaled = h * 6.0f;
+    const float fl = floorf(h_scaled);
+    const int sector = (int)fl;
+    const float fr = h_scaled - fl;
+    const float p = v * (1.0f - s);
+    const float q = v * (1.0f - s * fr);
+    const float t = v * (1.0f - s * (1.0f - fr));
+    if (sector == 0)      { r.x = v; r.y = t; r.z = p; }
+    else if (sector == 1) { r.x = q; r.y = v; r.z = p; }
+    else if (sector == 2) { r.x = p; r.y = v; r.z = t; }
+    else if (sector == 3) { r.x = p; r.y = q; r.z = v; }
+    else if (sector == 4) { r.x = t; r.y = p; r.z = v; }
+    else                  { r.x = v; r.y = p; r.z = q; }
+    return r;
+}
+
+// march_kernel.hip `srgb2physical` (pygfx std.wgsl, restated)
+__device__ __forceinline__ float srgb2physical(float c) {
+    const float f = powf((c + 0.055f) / 1.055f, 2.4f);
+    const float t = c / 12.92f;
+    return (c <= 0.04045f) ? t : f;
+}
+
+template <int ESH>
+__device__ __forceinline__ float load_texel(const void* base, size_t i) {
+    if (ESH == 0) return (float)static_cast<const uint8_t*>(base)[i];
+    if (ESH == 1) return (float)static_cast<const uint16_t*>(base)[i];
+    return static_cast<const float*>(base)[i];
+}
+
+template <int NL, int ESH>
+__global__ __launch_bounds__(256) void slice_kernel(const SliceParams P) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = blockIdx.x * 16 + (lane & 15);
+    const int r = blockIdx.y * 16 + wave * 4 + (lane >> 4);
+    if (c >= P.frame.out_w || r >= P.frame.out_h) return;
+    const size_t o = (size_t)r * (size_t)P.frame.out_w + (size_t)c;
+    const int x = P.frame.x0 + c;
+    const int y = P.frame.y0 + (r / P.frame.band_h) * P.frame.band_pitch + (r % P.frame.band_h);
+
+    float4 color = make_float4(0.f, 0.f, 0.f, 0.f);
+    float value = 0.0f;
+    uint32_t label = 0u;
+    uint8_t cls = SVR_PIX_DISCARD, lod = 255;
+    if (x < P.frame.frame_w && y < P.frame.frame_h) {
+        const float fx = ((float)x + 0.5f) - 0.5f * (float)P.frame.frame_w;
+        const float fy = ((float)y + 0.5f) - 0.5f * (float)P.frame.frame_h;
+        const float px = (P.origin[0] + fx * P.u[0]) + fy * P.v[0];
+        const float py = (P.origin[1] + fx * P.u[1]) + fy * P.v[1];
+        const float pz = (P.origin[2] + fx * P.u[2]) + fy * P.v[2];
+        const float* m = P.world_inv;
+        const float qx = ((m[0] * px + m[4] * py) + m[8] * pz) + m[12] * 1.0f;
+        const float qy = ((m[1] * px + m[5] * py) + m[9] * pz) + m[13] * 1.0f;
+        const float qz = ((m[2] * px + m[6] * py) + m[10] * pz) + m[14] * 1.0f;
+        const float dx = ((qx + 0.5f) / P.size[0]) * P.size[0];
+        const float dy = ((qy + 0.5f) / P.size[1]) * P.size[1];
+        const float dz = ((qz + 0.5f) / P.size[2]) * P.size[2];
+        if (dx >= 0.0f && dx < P.size[0] && dy >= 0.0f && dy < P.size[1] && dz >= 0.0f && dz < P.size[2]) {
+            cls = SVR_PIX_MISS;
+            color.w = 1.0f;
+#pragma unroll
+            for (int l = 0; l < NL; ++l) {
+                uint32_t wx, wy, wz;
+                if (!lod_slot(P.L[l], dx, dy, dz, wx, wy, wz)) continue;
+                const SliceLod& L = P.L[l];
+                const size_t idx = ((size_t)wz * L.ring[1] + wy) * (size_t)L.ring[0] + wx;
+                value = L.twin ? load_texel<ESH>(L.twin, svr_blocked_index(ESH, L.ring[0], L.ring[1], wx, wy, wz))
+                               : load_texel<ESH>(L.density, idx);
+                label = L.labels ? L.labels[idx] : 0u;
+                lod = (uint8_t)l;
+                cls = SVR_PIX_HIT;
+                break;
+            }
+            if (cls == SVR_PIX_HIT) {
+                float s = (value - P.clim0) / (P.clim1 - P.clim0);
+                if (P.gamma != 1.0f) s = powf(s, P.gamma);
+                const float phys = P.colorspace_srgb ? srgb2physical(s) : s;
+                const float* hs = P.colors + 4u * (label % P.color_count);
+                const f3 rgb = hsv_to_rgb(hs[0], hs[1], phys);
+                color = make_float4(rgb.x, rgb.y, rgb.z, P.opacity);
+            }
+        }
+    }
+    reinterpret_cast<float4*>(P.rgba)[o] = color;
+    if (P.depth) P.depth[o] = 0.0f;
+    if (P.label) P.label[o] = label;
+    if (P.flags) P.flags[o] = cls;
+    if (P.value) P.value[o] = value;
+    if (P.lod) P.lod[o] = lod;
+}
+
+template <int NL>
+hipError_t launch_nl(const SliceParams& P, int esh, dim3 grid, hipStream_t stream) {
+    if (esh == 0) hipLaunchKernelGGL((slice_kernel<NL, 0>), grid, dim3(256), 0, stream, P);
+    else if (esh == 1) hipLaunchKernelGGL((slice_kernel<NL, 1>), grid, dim3(256), 0, stream, P);
+    else hipLaunchKernelGGL((slice_kernel<NL, 2>), grid, dim3(256), 0, stream, P);
+    return hipGetLastError();
+}
+
+// 128-byte lines a 16 x 4 wave tile touches, estimated from the bounding box of its footprint in ring voxels (extent
+// e per axis) for a layout of b-voxel lines: prod(e_k / b_k + 1), at most one per lane
+float lines_per_tile(const float e[3], float bx, float by, float bz) {
+    return fminf(64.0f, (e[0] / bx + 1.0f) * (e[1] / by + 1.0f) * (e[2] / bz + 1.0f));
+}
+
+}  // namespace
+
+// Declared in svr_api.hip (which validates the arguments, orders the launch against the uploads and marks it as a
+// render).  twin_mode: 0 rows only, 2 the micro-block copy wherever there is one, 1 per LOD the fewer lines.
+hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const svr_frame& fr, const svr_slice_outputs& out,
+                            int twin_mode, hipStream_t stream) {
+    SliceParams P;
+    memset(&P, 0, sizeof(P));
+    memcpy(P.world_inv, pl.world_inv, sizeof(P.world_inv));
+    for (int a = 0; a < 3; ++a) {
+        P.size[a] = pl.volume_dimensions[a];
+        P.origin[a] = pl.origin[a]; P.u[a] = pl.u[a]; P.v[a] = pl.v[a];
+    }
+    P.frame = fr;
+    const svr_material& m = c->material;
+    P.clim0 = m.clim[0]; P.clim1 = m.clim[1]; P.gamma = m.gamma; P.opacity = m.opacity;
+    P.colorspace_srgb = m.colorspace_srgb;
+    P.color_count = m.color_count; P.colors = c->colors_dev;
+    P.esh = c->density_storage == SVR_U8 ? 0 : (c->density_storage == SVR_U16 ? 1 : 2);
+    P.rgba = out.rgba; P.depth = out.depth; P.label = out.label; P.flags = out.flags; P.value = out.value; P.lod = out.lod;
+    // data-space voxel steps per column and per row (the linear part of world_inv applied to u and v)
+    float du[3], dv[3];
+    for (int k = 0; k < 3; ++k) {
+        du[k] = (pl.world_inv[k] * pl.u[0] + pl.world_inv[4 + k] * pl.u[1]) + pl.world_inv[8 + k] * pl.u[2];
+        dv[k] = (pl.world_inv[k] * pl.v[0] + pl.world_inv[4 + k] * pl.v[1]) + pl.world_inv[8 + k] * pl.v[2];
+    }
+    for (int l = 0; l < c->num_lods; ++l) {
+        const LodStorage& S = c->lod[l];
+        SliceLod& Q = P.L[l];
+        Q.density = S.density; Q.labels = S.labels;
+        for (int a = 0; a < 3; ++a) {
+            Q.off[a] = S.state.offset[a];
+            Q.shape[a] = (uint32_t)S.state.shape[a];
+            Q.ring[a] = (uint32_t)S.ring[a];
+            Q.wrap0[a] = (uint32_t)(S.state.offset[a] % S.ring[a]);     // (svr_set_lod_state: offsets are >= 0)
+            Q.scale[a] = S.state.scale[a];
+        }
+        Q.twin = nullptr;
+        if (S.twin && twin_mode == 2) Q.twin = S.twin;
+        if (S.twin && twin_mode == 1) {
+            float e[3];
+            for (int k = 0; k < 3; ++k) e[k] = (15.0f * fabsf(du[k]) + 3.0f * fabsf(dv[k])) * Q.scale[k];
+            const float es = (float)(1 << P.esh);
+            const float rows = lines_per_tile(e, 128.0f / es, 1.0f, 1.0f);
+            const float blocks = P.esh == 0 ? lines_per_tile(e, 8.0f, 4.0f, 4.0f)
+                               : P.esh == 1 ? lines_per_tile(e, 4.0f, 4.0f, 4.0f) : lines_per_tile(e, 4.0f, 4.0f, 2.0f);
+            if (blocks < rows) Q.twin = S.twin;
+        }
+    }
+    const dim3 grid((unsigned)((fr.out_w + 15) / 16), (unsigned)((fr.out_h + 15) / 16));
+    switch (c->num_lods) {
+        case 1: return launch_nl<1>(P, P.esh, grid, stream);
+        case 2: return launch_nl<2>(P, P.esh, grid, stream);
+        case 3: return launch_nl<3>(P, P.esh, grid, stream);
+        case 4: return launch_nl<4>(P, P.esh, grid, stream);
+        case 5: return launch_nl<5>(P, P.esh, grid, stream);
+        case 6: return launch_nl<6>(P, P.esh, grid, stream);
+        case 7: return launch_nl<7>(P, P.esh, grid, stream);
+        default: return launch_nl<8>(P, P.esh, grid, stream);
+    }
+}

@@ -43,6 +43,9 @@ int floor_div(int a, int b) { int q = a / b, r = a % b; return (r != 0 && ((r < 
 hipError_t svr_launch_outline(const float* rgba, const float* depth, const uint32_t* label, const uint8_t* flags, int w,
                               int h, const svr_outline_params& q, const float* colors, uint32_t ncolors,
                               const uint32_t* sel, uint32_t nsel, float* out, uint8_t* mask, hipStream_t stream);
+// slice_kernels.hip (same reason).  twin_mode: 0 rows only, 1 per LOD the layout with fewer lines per wave, 2 the copy.
+hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const svr_frame& fr, const svr_slice_outputs& out,
+                            int twin_mode, hipStream_t stream);
 
 extern "C" {
 
@@ -1142,6 +1145,28 @@ int svr_time_render(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, cons
     SVR_HIP_TRY(hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
     *avg_ms = ms / (float)iters;
     return SVR_OK;
+}
+
+int svr_slice(svr_ctx* c, const svr_slice_plane* plane, const svr_frame* fr, const svr_slice_outputs* out, void* stream) {
+    SVR_REQUIRE(c && plane && fr && out && out->rgba, "svr_slice: null argument");
+    SVR_REQUIRE(c->material_set, "svr_slice: svr_set_material has not been called");
+    SVR_REQUIRE(fr->frame_w > 0 && fr->frame_h > 0 && fr->out_w > 0 && fr->out_h > 0, "svr_slice: empty frame");
+    SVR_REQUIRE(fr->x0 >= 0 && fr->y0 >= 0, "svr_slice: negative tile origin");
+    for (int a = 0; a < 3; ++a) {
+        SVR_REQUIRE(plane->volume_dimensions[a] >= 1.0f, "svr_slice: volume_dimensions must be >= 1");
+        SVR_REQUIRE(isfinite(plane->origin[a]) && isfinite(plane->u[a]) && isfinite(plane->v[a]),
+                    "svr_slice: origin, u and v must be finite");
+    }
+    SVR_REQUIRE((uintptr_t)out->rgba % 16 == 0, "svr_slice: rgba must be 16-byte aligned");
+    svr_frame f = *fr;
+    if (f.band_h <= 0) { f.band_h = fr->out_h; f.band_pitch = fr->out_h; }
+    const int twin_mode = (c->variant & 256) ? 0 : ((c->variant & 512) ? 2 : 1);
+    DeviceGuard guard(c->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);         // NULL = default stream, as in svr_render
+    // ordered like a render: behind the published uploads, and later uploads behind this slice (mark_render)
+    if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
+    SVR_HIP_TRY(svr_launch_slice(c, *plane, f, *out, twin_mode, s));
+    return mark_render(c, s);
 }
 
 int svr_untile_stripes(svr_ctx* c, const void* gathered, void* frame_out, int frame_w, int frame_h,
