@@ -412,6 +412,44 @@ typedef struct svr_slice_outputs {
 int  svr_slice(svr_ctx* ctx, const svr_slice_plane* plane, const svr_frame* frame, const svr_slice_outputs* out,
                void* stream);
 
+/* ---- thick-slab projections: the maximum, minimum or mean of N samples stacked along a slice's normal (no
+ * counterpart in the reference; the thick slices of napari, Fiji's Z-project of a sub-stack).  An addition within ABI
+ * version 9: svr_slab is a new symbol, nothing older changes.  Defined HERE (numpy restatement: tests/slab_twin.py),
+ * in f32, in this order, with no fused operations.  Each pixel starts from svr_slice's chain: fx, fy, p and
+ * q = world_inv * (p, 1) exactly as there.  With the data-space sample step
+ *     dw_k = (m[k] * w_x + m[4+k] * w_y) + m[8+k] * w_z                the linear part of world_inv applied to w
+ * sample k = 0 .. N-1 sits at t_k = (float)k - 0.5f * (float)(N-1) steps from the plane:
+ *     q_k  = q + t_k * dw                                               per component, multiply then add
+ *     dx_k = ((q_k + 0.5f) / size) * size
+ * and is classified DISCARD / MISS / HIT from dx_k exactly as a slice pixel (outside the box; inside with nothing
+ * resident; the first LOD whose ROI holds it, giving value_k, label_k, lod_k).  Reduced over the HIT samples only:
+ *     MAX / MIN  best = the first HIT sample; a later HIT sample replaces it iff value_k > best (MAX) or
+ *                value_k < best (MIN).  Ties keep the lowest k; a NaN first HIT stays, a later NaN never wins.
+ *                value, label, lod and depth are those of the chosen sample.
+ *     MEAN       value = (the sum of the HIT values, accumulated in f32 in increasing k) / (float)hits;
+ *                label, lod and depth are those of the sample MAX would choose.
+ *     depth      t_k * w_len of the chosen sample: the signed world offset from the centre plane (w_len = |w|, the
+ *                f32 of its float64 norm, given by the caller), so svr_outline's depth test applies to slabs.
+ * The pixel is HIT if any sample hit, shaded from (value, label) exactly as a slice HIT; else MISS if any sample lay
+ * inside the box (rgba (0,0,0,1), value 0, label 0, lod 255, depth 0); else svr_slice's DISCARD.  Since t_0 = 0 when
+ * N = 1, q_0 = q: N = 1 with MAX is bit-identical to svr_slice on every plane.  Output planes and pointer rules are
+ * svr_slice_outputs'; ordering and variant bits 8 / 9 (micro-block copy routing) are svr_slice's.  SVR_ERR_INVALID,
+ * with nothing enqueued, for: samples outside 1 .. 4096, an unknown mode, a w, dw or w_len that is not finite (or a
+ * negative w_len), and svr_slice's own refusals. */
+#define SVR_SLAB_MAX  0
+#define SVR_SLAB_MIN  1
+#define SVR_SLAB_MEAN 2
+#define SVR_SLAB_MAX_SAMPLES 4096
+typedef struct svr_slab_params {
+    svr_slice_plane plane;         /* as svr_slice: the centre plane */
+    float   w[3];                  /* world step from one sample to the next */
+    float   w_len;                 /* |w|, for the depth plane */
+    int32_t samples;               /* N, 1 .. SVR_SLAB_MAX_SAMPLES */
+    int32_t mode;                  /* SVR_SLAB_* */
+} svr_slab_params;
+int  svr_slab(svr_ctx* ctx, const svr_slab_params* params, const svr_frame* frame, const svr_slice_outputs* out,
+              void* stream);
+
 /* ---- sync */
 int  svr_sync(svr_ctx* ctx);                 /* both streams idle */
 int  svr_sync_uploads(svr_ctx* ctx);         /* upload stream idle */

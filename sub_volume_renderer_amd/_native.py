@@ -133,6 +133,20 @@ class SliceOutputs(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("rgba", "depth", "label", "flags", "value", "lod")]
 
 
+class SlabParams(C.Structure):
+    _fields_ = [
+        ("plane", SlicePlane),
+        ("w", C.c_float * 3),
+        ("w_len", C.c_float),
+        ("samples", C.c_int32),
+        ("mode", C.c_int32),
+    ]
+
+
+SLAB_MODES = {"max": 0, "min": 1, "mean": 2}        # SVR_SLAB_*
+SLAB_MAX_SAMPLES = 4096
+
+
 _I3 = C.c_int32 * 3
 _L3 = C.c_int64 * 3
 
@@ -176,6 +190,7 @@ SIGNATURES = {
                               C.POINTER(OutlineParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "svr_slice": (C.c_int, [C.c_void_p, C.POINTER(SlicePlane), C.POINTER(Frame), C.POINTER(SliceOutputs), C.c_void_p]),
+    "svr_slab": (C.c_int, [C.c_void_p, C.POINTER(SlabParams), C.POINTER(Frame), C.POINTER(SliceOutputs), C.c_void_p]),
     "svr_sync": (C.c_int, [C.c_void_p]),
     "svr_sync_uploads": (C.c_int, [C.c_void_p]),
     "svr_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),

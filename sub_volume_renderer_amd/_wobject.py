@@ -193,6 +193,7 @@ class SubVolume(_HasWorld):
         self._frame_cache = {}
         self._ob_cache = {}
         self._slice_cache = {}
+        self._slab_cache = {}         # separate: a slab never overwrites the tensors of the last slice
         self._worker = None
         self._worker_error = None
         self._inflight = []
@@ -270,7 +271,7 @@ class SubVolume(_HasWorld):
         self._worker = None
         self._inflight.clear()
         self._completed = self._submitted
-        self._out_cache, self._ob_cache, self._slice_cache = {}, {}, {}
+        self._out_cache, self._ob_cache, self._slice_cache, self._slab_cache = {}, {}, {}, {}
         self._rings.close()
 
     # -- asynchronous streaming ------------------------------------------------------
@@ -527,9 +528,15 @@ class SubVolume(_HasWorld):
         return origin, tuple(u), tuple(v)
 
     def _slice_outputs(self, h, w):
+        return self._plane_outputs(self._slice_cache, h, w)
+
+    def _slab_outputs(self, h, w):
+        return self._plane_outputs(self._slab_cache, h, w)
+
+    def _plane_outputs(self, cache, h, w):
         import torch
 
-        res = self._slice_cache.pop((h, w), None)
+        res = cache.pop((h, w), None)
         if res is None:
             dev = torch.device("cuda", self._rings.device if self._rings.device is not None else torch.cuda.current_device())
             res = SliceResult(
@@ -541,9 +548,9 @@ class SubVolume(_HasWorld):
                 value=torch.empty((h, w), dtype=torch.float32, device=dev),
                 lod=torch.empty((h, w), dtype=torch.uint8, device=dev),
             )
-            while len(self._slice_cache) >= _SLICE_CACHE_SIZES:
-                del self._slice_cache[next(iter(self._slice_cache))]      # least recently used
-        self._slice_cache[(h, w)] = res
+            while len(cache) >= _SLICE_CACHE_SIZES:
+                del cache[next(iter(cache))]      # least recently used
+        cache[(h, w)] = res
         return res
 
     def _check_slice_out(self, out, h, w):
@@ -573,17 +580,83 @@ class SubVolume(_HasWorld):
         centre would read: the finest resident LOD's texel.  Asynchronous on the current torch stream.  Unless ``out`` is
         given, the output tensors of a size are reused by the next call of that size (the last few sizes are kept), so
         a result is overwritten by the next slice of its size."""
-        import torch
+        origin, u, v, width, height = self._plane_args(origin, u, v, width, height)
+        fb = self._plane_frame(region, out, width, height)
+        handle = self.prepare()
+        res = out or self._slice_outputs(fb.out_h, fb.out_w)
+        pl = self._plane_struct(origin, u, v)
+        N.check(N.lib().svr_slice(handle, C.byref(pl), C.byref(fb), C.byref(self._plane_ob(res)),
+                                  C.c_void_p(self._plane_stream(stream))), "svr_slice")
+        return res
 
+    def render_slab(self, origin, u, v, w, samples: int, width: int, height: int, *, mode: str = "max",
+                    region: FrameRegion | None = None, out: SliceResult | None = None, stream=None) -> SliceResult:
+        """Thick-slab projection (definition: ``svr_slab`` in include/svr.h): ``samples`` slices of
+        :meth:`render_slice`'s plane stacked along the world step ``w`` and centred on it (sample k lies
+        ``k - (samples - 1) / 2`` steps off the plane), reduced per pixel over the samples that hit a resident voxel:
+        ``mode`` "max" / "min" (value, label, LOD and depth of the winning sample, ties to the first) or "mean" (the mean
+        of the values; label, LOD and depth of the sample "max" picks).  ``depth`` is the winner's signed world offset
+        from the centre plane, so ``outline(..., depth_tolerance=)`` applies.  Returns the planes of a slice; its
+        output tensors are kept per size apart from the slices', so a slab never overwrites the last slice."""
+        origin, u, v, width, height = self._plane_args(origin, u, v, width, height)
+        w = _vec3("w", w)
+        f32 = np.float32
+        with np.errstate(all="ignore"):
+            normal = np.cross(np.array(u, f32), np.array(v, f32))
+            triple = f32(np.dot(normal, np.array(w, f32)))
+        if not triple != 0:
+            raise ValueError("w must not be coplanar with u and v")
+        if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or not 1 <= samples <= N.SLAB_MAX_SAMPLES:
+            raise ValueError(f"samples must be an integer in 1 .. {N.SLAB_MAX_SAMPLES}")
+        if not isinstance(mode, str) or mode not in N.SLAB_MODES:
+            raise ValueError("mode must be 'max', 'min' or 'mean'")
+        # the data-space step, in float32 in svr_slab's order, and |w| as the kernel receives it
+        m = np.asarray(self.world.inverse_matrix, np.float64).astype(f32)
+        w32 = np.array(w, f32)
+        with np.errstate(all="ignore"):
+            dw = [(m[k, 0] * w32[0] + m[k, 1] * w32[1]) + m[k, 2] * w32[2] for k in range(3)]
+            w_len = f32(np.linalg.norm(w32.astype(np.float64)))
+        if not (np.all(np.isfinite(dw)) and np.isfinite(w_len)):
+            raise ValueError("w must have a length and a data-space step that are finite in float32")
+        fb = self._plane_frame(region, out, width, height)
+        handle = self.prepare()
+        res = out or self._slab_outputs(fb.out_h, fb.out_w)
+        sp = N.SlabParams()
+        sp.plane = self._plane_struct(origin, u, v)
+        sp.w[:] = w
+        sp.w_len, sp.samples, sp.mode = float(w_len), int(samples), N.SLAB_MODES[mode]
+        N.check(N.lib().svr_slab(handle, C.byref(sp), C.byref(fb), C.byref(self._plane_ob(res)),
+                                 C.c_void_p(self._plane_stream(stream))), "svr_slab")
+        return res
+
+    @staticmethod
+    def axis_slab_plane(axis, center, pixel_size: float = 1.0, step: float = 1.0):
+        """``(origin, u, v, w)`` of the axis-aligned slab centred on the world point ``center``: ``origin``, ``u`` and
+        ``v`` as :meth:`axis_slice_plane`, ``w`` along +``axis`` with length ``step`` (world units between samples)."""
+        origin, u, v = SubVolume.axis_slice_plane(axis, center, pixel_size)
+        s = float(step)
+        with np.errstate(over="ignore"):
+            finite32 = bool(np.isfinite(np.float32(s)))
+        if not (finite32 and s > 0.0):
+            raise ValueError("step must be finite and > 0")
+        w = [0.0, 0.0, 0.0]
+        w[{"x": 0, "y": 1, "z": 2}.get(axis, axis)] = s
+        return origin, u, v, tuple(w)
+
+    # -- the argument handling slices and slabs share ---------------------------------------
+    @staticmethod
+    def _plane_args(origin, u, v, width, height):
         origin, u, v = _vec3("origin", origin), _vec3("u", u), _vec3("v", v)
         for name, n in (("width", width), ("height", height)):
             if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
                 raise ValueError(f"{name} must be an integer >= 1")
-        width, height = int(width), int(height)
         with np.errstate(all="ignore"):
             normal = np.cross(np.array(u, np.float32), np.array(v, np.float32))      # float32, as the kernel steps
         if not np.any(normal != 0):
             raise ValueError("u and v must be nonzero and not parallel")
+        return origin, u, v, int(width), int(height)
+
+    def _plane_frame(self, region, out, width, height):
         if region is not None:
             stripes = 0 < region.band_h < region.out_h
             if (region.x0 < 0 or region.y0 < 0 or region.out_w < 1 or region.out_h < 1
@@ -593,21 +666,27 @@ class SubVolume(_HasWorld):
         fb = self.frame_block(width, height, region)
         if out is not None:
             self._check_slice_out(out, fb.out_h, fb.out_w)
+        return fb
 
-        handle = self.prepare()
-        res = out or self._slice_outputs(fb.out_h, fb.out_w)
+    def _plane_struct(self, origin, u, v):
         pl = N.SlicePlane()
         pl.world_inv = N.mat_to_c(self.world.inverse_matrix)
         pl.volume_dimensions[:] = [float(c) for c in self._volume_dimensions]
         pl.origin[:], pl.u[:], pl.v[:] = origin, u, v
+        return pl
+
+    @staticmethod
+    def _plane_ob(res):
         ob = N.SliceOutputs()
         for name in ("rgba",) + tuple(n for n, _ in _SLICE_PLANES):
             t = getattr(res, name)
             setattr(ob, name, t.data_ptr() if t is not None else None)
-        if stream is None:
-            stream = torch.cuda.current_stream(self._rings.device).cuda_stream
-        N.check(N.lib().svr_slice(handle, C.byref(pl), C.byref(fb), C.byref(ob), C.c_void_p(stream)), "svr_slice")
-        return res
+        return ob
+
+    def _plane_stream(self, stream):
+        import torch
+
+        return torch.cuda.current_stream(self._rings.device).cuda_stream if stream is None else stream
 
     def synchronize(self):
         N.check(N.lib().svr_sync(self._rings.handle), "svr_sync")

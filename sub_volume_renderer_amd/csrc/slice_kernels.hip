@@ -167,19 +167,182 @@ hipError_t launch_nl(const SliceParams& P, int esh, dim3 grid, hipStream_t strea
     return hipGetLastError();
 }
 
+// ---- thick slabs (svr_slab, include/svr.h): N samples per pixel along the data-space step dw, reduced to one.
+// One kernel for the three modes: MIN is MAX on keys whose sign bit is flipped (an exact bit flip, so ties and NaN
+// follow the same strict '>' and the value comes back bit for bit), and the f32 sum MEAN needs is one add per sample
+// that MAX and MIN carry unused.  That costs two VALU per sample against three times the code.
+struct SlabParams {
+    SliceParams S;
+    float dw[3];               // data-space step from one sample to the next (svr_slab computes and checks it)
+    float half;                // 0.5f * (float)(N - 1): t_k = (float)k - half
+    float w_len;
+    int32_t samples;
+    uint32_t smask;            // 0x80000000 for MIN, else 0
+    int32_t mean;
+};
+
+// a texel at a byte address known to be in global memory (global_load rather than flat_load: the ring pointers come
+// from the kernel arguments through a pointer the compiler cannot see into)
+template <int ESH>
+__device__ __forceinline__ float load_global(const char* a) {
+    typedef __attribute__((address_space(1))) const uint8_t G8;
+    typedef __attribute__((address_space(1))) const uint16_t G16;
+    typedef __attribute__((address_space(1))) const float G32;
+    if (ESH == 0) return (float)*(G8*)a;
+    if (ESH == 1) return (float)*(G16*)a;
+    return *(G32*)a;
+}
+
+using SlabArgs = const SlabParams __attribute__((address_space(4)));     // the kernel arguments' own address space
+
+constexpr int SLAB_UNROLL = 4;     // samples whose gathers are in flight together per lane
+
+// POW2: every size_k is a power of two <= 2^24.  Then ((x / size) * size) == x for every x = q_k + 0.5f: a nonzero
+// x is at least 2^-25 in magnitude (q_k + 0.5f is exact by Sterbenz's lemma where it is small), so x / size stays
+// normal and both steps are exact scalings; 0, inf and NaN pass through unchanged.  The round trip, three IEEE
+// divisions per sample, is skipped.
+template <int NL, int ESH, bool POW2>
+__global__ __launch_bounds__(256) void slab_kernel(const SlabParams Q) {
+    const SliceParams& P = Q.S;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = blockIdx.x * 16 + (lane & 15);
+    const int r = blockIdx.y * 16 + wave * 4 + (lane >> 4);
+    if (c >= P.frame.out_w || r >= P.frame.out_h) return;
+    const size_t o = (size_t)r * (size_t)P.frame.out_w + (size_t)c;
+    const int x = P.frame.x0 + c;
+    const int y = P.frame.y0 + (r / P.frame.band_h) * P.frame.band_pitch + (r % P.frame.band_h);
+
+    float4 color = make_float4(0.f, 0.f, 0.f, 0.f);
+    float value = 0.0f, depth = 0.0f;
+    uint32_t label = 0u;
+    uint8_t cls = SVR_PIX_DISCARD, lod = 255;
+    if (x < P.frame.frame_w && y < P.frame.frame_h) {
+        const float fx = ((float)x + 0.5f) - 0.5f * (float)P.frame.frame_w;
+        const float fy = ((float)y + 0.5f) - 0.5f * (float)P.frame.frame_h;
+        const float px = (P.origin[0] + fx * P.u[0]) + fy * P.v[0];
+        const float py = (P.origin[1] + fx * P.u[1]) + fy * P.v[1];
+        const float pz = (P.origin[2] + fx * P.u[2]) + fy * P.v[2];
+        const float* m = P.world_inv;
+        const float qx = ((m[0] * px + m[4] * py) + m[8] * pz) + m[12] * 1.0f;
+        const float qy = ((m[1] * px + m[5] * py) + m[9] * pz) + m[13] * 1.0f;
+        const float qz = ((m[2] * px + m[6] * py) + m[10] * pz) + m[14] * 1.0f;
+
+        bool inside = false;
+        int hits = 0, best_k = 0, best_l = 0;
+        float sum = 0.0f, best = 0.0f;
+        size_t best_idx = 0;
+        const SlabArgs* kq = (const SlabArgs*)__builtin_amdgcn_kernarg_segment_ptr();     // Q itself: the only argument
+        for (int k0 = 0; k0 < Q.samples; k0 += SLAB_UNROLL) {
+            // The LOD table is read from the kernel arguments afresh in each iteration (scalar loads from the constant
+            // cache): held in SGPRs across the loop, its 21 dwords per LOD spill SGPRs from NL = 3 on.
+            asm volatile("" : "+s"(kq));
+            const SliceLod* Ls = (const SliceLod*)kq->S.L;
+            // addresses of SLAB_UNROLL samples first, then their gathers, then the compares in increasing k
+            const char* addr[SLAB_UNROLL];
+            size_t ridx[SLAB_UNROLL];
+            int sl[SLAB_UNROLL];
+            bool in[SLAB_UNROLL];
+#pragma unroll
+            for (int j = 0; j < SLAB_UNROLL; ++j) {
+                const float t = (float)(k0 + j) - Q.half;
+                const float ax = qx + t * Q.dw[0], ay = qy + t * Q.dw[1], az = qz + t * Q.dw[2];
+                const float dx = POW2 ? ax + 0.5f : ((ax + 0.5f) / P.size[0]) * P.size[0];
+                const float dy = POW2 ? ay + 0.5f : ((ay + 0.5f) / P.size[1]) * P.size[1];
+                const float dz = POW2 ? az + 0.5f : ((az + 0.5f) / P.size[2]) * P.size[2];
+                in[j] = k0 + j < Q.samples && dx >= 0.0f && dx < P.size[0] && dy >= 0.0f && dy < P.size[1] &&
+                        dz >= 0.0f && dz < P.size[2];
+                sl[j] = NL;                                        // no LOD holds it
+                addr[j] = static_cast<const char*>(Ls[0].density);    // a valid address for the unused gather
+                ridx[j] = 0;
+                bool done = !in[j];
+#pragma unroll
+                for (int l = 0; l < NL; ++l) {
+                    uint32_t wx, wy, wz;
+                    if (done || !lod_slot(Ls[l], dx, dy, dz, wx, wy, wz)) continue;
+                    const SliceLod& L = Ls[l];
+                    done = true;
+                    sl[j] = l;
+                    ridx[j] = ((size_t)wz * L.ring[1] + wy) * (size_t)L.ring[0] + wx;
+                    addr[j] = L.twin ? static_cast<const char*>(L.twin) + (svr_blocked_index(ESH, L.ring[0], L.ring[1], wx, wy, wz) << ESH)
+                                     : static_cast<const char*>(L.density) + (ridx[j] << ESH);
+                }
+            }
+            float vals[SLAB_UNROLL];
+#pragma unroll
+            for (int j = 0; j < SLAB_UNROLL; ++j) vals[j] = load_global<ESH>(addr[j]);
+#pragma unroll
+            for (int j = 0; j < SLAB_UNROLL; ++j) {
+                inside |= in[j];
+                if (sl[j] == NL) continue;
+                const float key = __uint_as_float(__float_as_uint(vals[j]) ^ Q.smask);
+                if (hits == 0 || key > best) { best = key; best_k = k0 + j; best_l = sl[j]; best_idx = ridx[j]; }
+                sum += vals[j];
+                ++hits;
+            }
+        }
+        if (hits > 0) {
+            cls = SVR_PIX_HIT;
+            value = Q.mean ? sum / (float)hits : __uint_as_float(__float_as_uint(best) ^ Q.smask);
+            lod = (uint8_t)best_l;
+#pragma unroll
+            for (int l = 0; l < NL; ++l)
+                if (best_l == l && P.L[l].labels) label = P.L[l].labels[best_idx];
+            depth = ((float)best_k - Q.half) * Q.w_len;
+            float s = (value - P.clim0) / (P.clim1 - P.clim0);
+            if (P.gamma != 1.0f) s = powf(s, P.gamma);
+            const float phys = P.colorspace_srgb ? srgb2physical(s) : s;
+            const float* hs = P.colors + 4u * (label % P.color_count);
+            const f3 rgb = hsv_to_rgb(hs[0], hs[1], phys);
+            color = make_float4(rgb.x, rgb.y, rgb.z, P.opacity);
+        } else if (inside) {
+            cls = SVR_PIX_MISS;
+            color.w = 1.0f;
+        }
+    }
+    reinterpret_cast<float4*>(P.rgba)[o] = color;
+    if (P.depth) P.depth[o] = depth;
+    if (P.label) P.label[o] = label;
+    if (P.flags) P.flags[o] = cls;
+    if (P.value) P.value[o] = value;
+    if (P.lod) P.lod[o] = lod;
+}
+
+template <int NL, bool POW2>
+hipError_t launch_slab_nl(const SlabParams& Q, dim3 grid, hipStream_t stream) {
+    if (Q.S.esh == 0) hipLaunchKernelGGL((slab_kernel<NL, 0, POW2>), grid, dim3(256), 0, stream, Q);
+    else if (Q.S.esh == 1) hipLaunchKernelGGL((slab_kernel<NL, 1, POW2>), grid, dim3(256), 0, stream, Q);
+    else hipLaunchKernelGGL((slab_kernel<NL, 2, POW2>), grid, dim3(256), 0, stream, Q);
+    return hipGetLastError();
+}
+
+template <bool POW2>
+hipError_t launch_slab(const SlabParams& Q, int num_lods, dim3 grid, hipStream_t stream) {
+    switch (num_lods) {
+        case 1: return launch_slab_nl<1, POW2>(Q, grid, stream);
+        case 2: return launch_slab_nl<2, POW2>(Q, grid, stream);
+        case 3: return launch_slab_nl<3, POW2>(Q, grid, stream);
+        case 4: return launch_slab_nl<4, POW2>(Q, grid, stream);
+        case 5: return launch_slab_nl<5, POW2>(Q, grid, stream);
+        case 6: return launch_slab_nl<6, POW2>(Q, grid, stream);
+        case 7: return launch_slab_nl<7, POW2>(Q, grid, stream);
+        default: return launch_slab_nl<8, POW2>(Q, grid, stream);
+    }
+}
+
 // 128-byte lines a 16 x 4 wave tile touches, estimated from the bounding box of its footprint in ring voxels (extent
-// e per axis) for a layout of b-voxel lines: prod(e_k / b_k + 1), at most one per lane
-float lines_per_tile(const float e[3], float bx, float by, float bz) {
-    return fminf(64.0f, (e[0] / bx + 1.0f) * (e[1] / by + 1.0f) * (e[2] / bz + 1.0f));
+// e per axis) for a layout of b-voxel lines: prod(e_k / b_k + 1), at most one per lane (cap 64; a slab's N gathers: 64 N)
+float lines_per_tile(const float e[3], float bx, float by, float bz, float cap = 64.0f) {
+    return fminf(cap, (e[0] / bx + 1.0f) * (e[1] / by + 1.0f) * (e[2] / bz + 1.0f));
 }
 
 }  // namespace
 
-// Declared in svr_api.hip (which validates the arguments, orders the launch against the uploads and marks it as a
-// render).  twin_mode: 0 rows only, 2 the micro-block copy wherever there is one, 1 per LOD the fewer lines.
-hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const svr_frame& fr, const svr_slice_outputs& out,
-                            int twin_mode, hipStream_t stream) {
-    SliceParams P;
+namespace {
+
+// The kernel arguments svr_slice and svr_slab share (everything but the micro-block copy routing), and the data-space
+// voxel steps per column (du) and per row (dv): the linear part of world_inv applied to u and v.
+void fill_slice_params(const svr_ctx* c, const svr_slice_plane& pl, const svr_frame& fr, const svr_slice_outputs& out,
+                       SliceParams& P, float du[3], float dv[3]) {
     memset(&P, 0, sizeof(P));
     memcpy(P.world_inv, pl.world_inv, sizeof(P.world_inv));
     for (int a = 0; a < 3; ++a) {
@@ -193,8 +356,6 @@ hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const s
     P.color_count = m.color_count; P.colors = c->colors_dev;
     P.esh = c->density_storage == SVR_U8 ? 0 : (c->density_storage == SVR_U16 ? 1 : 2);
     P.rgba = out.rgba; P.depth = out.depth; P.label = out.label; P.flags = out.flags; P.value = out.value; P.lod = out.lod;
-    // data-space voxel steps per column and per row (the linear part of world_inv applied to u and v)
-    float du[3], dv[3];
     for (int k = 0; k < 3; ++k) {
         du[k] = (pl.world_inv[k] * pl.u[0] + pl.world_inv[4 + k] * pl.u[1]) + pl.world_inv[8 + k] * pl.u[2];
         dv[k] = (pl.world_inv[k] * pl.v[0] + pl.world_inv[4 + k] * pl.v[1]) + pl.world_inv[8 + k] * pl.v[2];
@@ -211,15 +372,35 @@ hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const s
             Q.scale[a] = S.state.scale[a];
         }
         Q.twin = nullptr;
+    }
+}
+
+// 128-byte lines of the micro-block copy / of the rows that a footprint of extent e (ring voxels) touches
+float block_lines(int esh, const float e[3], float cap = 64.0f) {
+    return esh == 0 ? lines_per_tile(e, 8.0f, 4.0f, 4.0f, cap)
+         : esh == 1 ? lines_per_tile(e, 4.0f, 4.0f, 4.0f, cap) : lines_per_tile(e, 4.0f, 4.0f, 2.0f, cap);
+}
+float row_lines(int esh, const float e[3], float cap = 64.0f) {
+    return lines_per_tile(e, 128.0f / (float)(1 << esh), 1.0f, 1.0f, cap);
+}
+
+}  // namespace
+
+// Declared in svr_api.hip (which validates the arguments, orders the launch against the uploads and marks it as a
+// render).  twin_mode: 0 rows only, 2 the micro-block copy wherever there is one, 1 per LOD the fewer lines.
+hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const svr_frame& fr, const svr_slice_outputs& out,
+                            int twin_mode, hipStream_t stream) {
+    SliceParams P;
+    float du[3], dv[3];
+    fill_slice_params(c, pl, fr, out, P, du, dv);
+    for (int l = 0; l < c->num_lods; ++l) {
+        const LodStorage& S = c->lod[l];
+        SliceLod& Q = P.L[l];
         if (S.twin && twin_mode == 2) Q.twin = S.twin;
         if (S.twin && twin_mode == 1) {
             float e[3];
             for (int k = 0; k < 3; ++k) e[k] = (15.0f * fabsf(du[k]) + 3.0f * fabsf(dv[k])) * Q.scale[k];
-            const float es = (float)(1 << P.esh);
-            const float rows = lines_per_tile(e, 128.0f / es, 1.0f, 1.0f);
-            const float blocks = P.esh == 0 ? lines_per_tile(e, 8.0f, 4.0f, 4.0f)
-                               : P.esh == 1 ? lines_per_tile(e, 4.0f, 4.0f, 4.0f) : lines_per_tile(e, 4.0f, 4.0f, 2.0f);
-            if (blocks < rows) Q.twin = S.twin;
+            if (block_lines(P.esh, e) < row_lines(P.esh, e)) Q.twin = S.twin;
         }
     }
     const dim3 grid((unsigned)((fr.out_w + 15) / 16), (unsigned)((fr.out_h + 15) / 16));
@@ -233,4 +414,50 @@ hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const s
         case 7: return launch_nl<7>(P, P.esh, grid, stream);
         default: return launch_nl<8>(P, P.esh, grid, stream);
     }
+}
+
+// Declared in svr_api.hip, like svr_launch_slice; svr_slab has validated the arguments and computed dw.
+// Micro-block copy routing per LOD over the whole slab (twin_mode 1).  A wave's N gathers of 64 lanes cost, per layout,
+//   the lines each gather walks (the slice's estimate of the tile on one plane: a gather touching 64 lines takes the
+//   texture unit 64 passes even when they are cached), summed over the N samples, plus
+//   the distinct lines of the bounding box of the 16 x 4 tile x N samples (what has to reach the CU at least once).
+// The copy is read where that total is lower.
+hipError_t svr_launch_slab(const svr_ctx* c, const svr_slab_params& sp, const float dw[3], const svr_frame& fr,
+                           const svr_slice_outputs& out, int twin_mode, hipStream_t stream) {
+    SlabParams Q;
+    memset(&Q, 0, sizeof(Q));
+    float du[3], dv[3];
+    fill_slice_params(c, sp.plane, fr, out, Q.S, du, dv);
+    const int N = sp.samples;
+    for (int k = 0; k < 3; ++k) Q.dw[k] = dw[k];
+    Q.half = 0.5f * (float)(N - 1);
+    Q.w_len = sp.w_len;
+    Q.samples = N;
+    Q.smask = sp.mode == SVR_SLAB_MIN ? 0x80000000u : 0u;
+    Q.mean = sp.mode == SVR_SLAB_MEAN;
+    for (int l = 0; l < c->num_lods; ++l) {
+        const LodStorage& S = c->lod[l];
+        SliceLod& L = Q.S.L[l];
+        if (S.twin && twin_mode == 2) L.twin = S.twin;
+        if (S.twin && twin_mode == 1) {
+            float plane[3], slab[3];
+            for (int k = 0; k < 3; ++k) {
+                plane[k] = (15.0f * fabsf(du[k]) + 3.0f * fabsf(dv[k])) * L.scale[k];
+                slab[k] = plane[k] + (float)(N - 1) * fabsf(dw[k]) * L.scale[k];
+            }
+            const float lanes = 64.0f * (float)N;
+            const float rows = (float)N * row_lines(Q.S.esh, plane) + row_lines(Q.S.esh, slab, lanes);
+            const float blocks = (float)N * block_lines(Q.S.esh, plane) + block_lines(Q.S.esh, slab, lanes);
+            if (blocks < rows) L.twin = S.twin;
+        }
+    }
+    // sizes that are powers of two up to 2^24 let the kernel skip the (x / size) * size round trip (exact there)
+    bool pow2 = true;
+    for (int a = 0; a < 3; ++a) {
+        int e2;
+        const float mant = frexpf(Q.S.size[a], &e2);
+        pow2 = pow2 && mant == 0.5f && e2 <= 25;
+    }
+    const dim3 grid((unsigned)((fr.out_w + 15) / 16), (unsigned)((fr.out_h + 15) / 16));
+    return pow2 ? launch_slab<true>(Q, c->num_lods, grid, stream) : launch_slab<false>(Q, c->num_lods, grid, stream);
 }

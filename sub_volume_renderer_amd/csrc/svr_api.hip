@@ -46,6 +46,9 @@ hipError_t svr_launch_outline(const float* rgba, const float* depth, const uint3
 // slice_kernels.hip (same reason).  twin_mode: 0 rows only, 1 per LOD the layout with fewer lines per wave, 2 the copy.
 hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const svr_frame& fr, const svr_slice_outputs& out,
                             int twin_mode, hipStream_t stream);
+// slice_kernels.hip (same reason).  dw: the data-space sample step, computed and checked by svr_slab.
+hipError_t svr_launch_slab(const svr_ctx* c, const svr_slab_params& sp, const float dw[3], const svr_frame& fr,
+                           const svr_slice_outputs& out, int twin_mode, hipStream_t stream);
 
 extern "C" {
 
@@ -1166,6 +1169,42 @@ int svr_slice(svr_ctx* c, const svr_slice_plane* plane, const svr_frame* fr, con
     // ordered like a render: behind the published uploads, and later uploads behind this slice (mark_render)
     if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
     SVR_HIP_TRY(svr_launch_slice(c, *plane, f, *out, twin_mode, s));
+    return mark_render(c, s);
+}
+
+int svr_slab(svr_ctx* c, const svr_slab_params* sp, const svr_frame* fr, const svr_slice_outputs* out, void* stream) {
+    SVR_REQUIRE(c && sp && fr && out && out->rgba, "svr_slab: null argument");
+    SVR_REQUIRE(c->material_set, "svr_slab: svr_set_material has not been called");
+    SVR_REQUIRE(fr->frame_w > 0 && fr->frame_h > 0 && fr->out_w > 0 && fr->out_h > 0, "svr_slab: empty frame");
+    SVR_REQUIRE(fr->x0 >= 0 && fr->y0 >= 0, "svr_slab: negative tile origin");
+    const svr_slice_plane& plane = sp->plane;
+    for (int a = 0; a < 3; ++a) {
+        SVR_REQUIRE(plane.volume_dimensions[a] >= 1.0f, "svr_slab: volume_dimensions must be >= 1");
+        SVR_REQUIRE(isfinite(plane.origin[a]) && isfinite(plane.u[a]) && isfinite(plane.v[a]),
+                    "svr_slab: origin, u and v must be finite");
+        SVR_REQUIRE(isfinite(sp->w[a]), "svr_slab: w must be finite");
+    }
+    SVR_REQUIRE(isfinite(sp->w_len) && sp->w_len >= 0.0f, "svr_slab: w_len must be finite and >= 0");
+    SVR_REQUIRE(sp->samples >= 1 && sp->samples <= SVR_SLAB_MAX_SAMPLES, "svr_slab: samples must be in 1 .. 4096");
+    SVR_REQUIRE(sp->mode == SVR_SLAB_MAX || sp->mode == SVR_SLAB_MIN || sp->mode == SVR_SLAB_MEAN,
+                "svr_slab: unknown mode");
+    // the data-space sample step (include/svr.h), as the slice launcher forms du / dv: an overflow to inf would make
+    // 0 * dw NaN and break the N = 1 identity with svr_slice
+    float dw[3];
+    const float* m = plane.world_inv;
+    for (int k = 0; k < 3; ++k) {
+        dw[k] = (m[k] * sp->w[0] + m[4 + k] * sp->w[1]) + m[8 + k] * sp->w[2];
+        SVR_REQUIRE(isfinite(dw[k]), "svr_slab: the data-space step of w must be finite");
+    }
+    SVR_REQUIRE((uintptr_t)out->rgba % 16 == 0, "svr_slab: rgba must be 16-byte aligned");
+    svr_frame f = *fr;
+    if (f.band_h <= 0) { f.band_h = fr->out_h; f.band_pitch = fr->out_h; }
+    const int twin_mode = (c->variant & 256) ? 0 : ((c->variant & 512) ? 2 : 1);
+    DeviceGuard guard(c->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // ordered like svr_slice: behind the published uploads, and later uploads behind this slab (mark_render)
+    if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
+    SVR_HIP_TRY(svr_launch_slab(c, *sp, dw, f, *out, twin_mode, s));
     return mark_render(c, s);
 }
 
