@@ -79,6 +79,12 @@ typedef struct svr_lod_desc {
                                       element per voxel of HBM and of upload traffic; results are identical.  The copies have an
                                       allocation of their own (they never push the rings over the 4 GiB below which one buffer
                                       resource reaches every LOD).  ring_dims must be multiples of (8, 4, 4), else SVR_ERR_INVALID.
+                                      A ring of 4 GiB or more is reached through parts of whole z planes, and the copy through
+                                      the same parts: the march uses the copy only where every part holds whole blocks (one
+                                      part, or parts of a multiple of 4 planes for 1- and 2-byte voxels, of 2 for 4-byte), and
+                                      otherwise reads that LOD's rows (planes of 1 GiB or more can give parts of 1 - 3 planes);
+                                      results are the same.  svr_slice and svr_slab index the copy with 64-bit offsets and use
+                                      it at any split.
                                       The Python mirror's "auto": 1 on the finest LOD; "all": also 2 on the others. */
 } svr_lod_desc;
 

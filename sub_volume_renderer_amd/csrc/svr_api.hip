@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "svr_internal.h"
+#include "ring_parts.h"
 
 static thread_local std::string g_err;
 void svr_set_error(const std::string& msg) { g_err = msg; }
@@ -860,20 +861,25 @@ static int tile_order_by_cost_for(svr_ctx* c, const MarchParams& P, int tile_w, 
     return SVR_OK;
 }
 
-// Can the span kernel address this context's rings?  Every LOD's ring must stay below 4 GiB (32-bit byte offsets
-// into its buffer resource) and within the 24-bit row index and row pitch of the exact general path; otherwise
-// every render takes the straightforward kernel's 64-bit addressing.
+// The experiments-only part size of SVR_FORCE_ZSPLIT (see rings_need_big); 0 in production builds.
+static int forced_zsplit() {
+    static const int force_zsplit = svr_exp_env_int("SVR_FORCE_ZSPLIT", 0);
+    return force_zsplit;
+}
+
+// How LOD l's density ring is cut into buffer resources (ring_parts.h decides; nothing else re-derives the split).
+static RingParts lod_ring_parts(const svr_ctx* c, int l) {
+    const LodStorage& L = c->lod[l];
+    return ring_parts((uint32_t)L.ring[0], (uint32_t)L.ring[1], (uint32_t)L.ring[2], (uint32_t)svr_dtype_size(c->density_storage),
+                      L.twin != nullptr, forced_zsplit());
+}
+
+// Can the span kernel address this context's rings?  Every LOD's ring must be reached through at most 8 resources of
+// whole z planes, each below 4 GiB (32-bit byte offsets), and stay within the 24-bit row index and row pitch of the
+// exact general path; otherwise every render takes the straightforward kernel's 64-bit addressing.
 static bool span_addressable(const svr_ctx* c) {
-    const uint64_t des = svr_dtype_size(c->density_storage);
-    for (int l = 0; l < c->num_lods; ++l) {
-        // (a ring of 4 GiB or more is reached through up to 8 resources of whole z planes, each below 4 GiB: 32 GiB)
-        const uint64_t plane = (uint64_t)c->lod[l].ring[0] * (uint64_t)c->lod[l].ring[1] * des;
-        uint64_t zsplit = plane ? std::min<uint64_t>((uint64_t)c->lod[l].ring[2], (((uint64_t)1 << 32) - 128) / plane) : 0;
-        if (zsplit < (uint64_t)c->lod[l].ring[2] && zsplit >= 4) zsplit &= ~(uint64_t)3;      // (parts of whole micro-blocks: fill_params)
-        if (zsplit == 0 || ((uint64_t)c->lod[l].ring[2] + zsplit - 1) / zsplit > 8 ||
-            (uint64_t)c->lod[l].ring[1] * (uint64_t)c->lod[l].ring[2] >= (1u << 24) ||
-            (uint64_t)c->lod[l].ring[0] * des >= (1u << 24)) return false;
-    }
+    for (int l = 0; l < c->num_lods; ++l)
+        if (!lod_ring_parts(c, l).span_ok) return false;
     return true;
 }
 
@@ -1079,34 +1085,19 @@ static int fill_params(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, c
         LodParams& Q = P.lod[l];
         Q.nparts = 1u; Q.zsplit = Q.ring[2]; Q.part_bytes = 0u; Q.rbytes_last = 0u;
         // the micro-block copy of the ring (svr_lod_desc::blocked_twin): always behind a resource of its own, which is cut
-        // into parts exactly like the ring's where that is (parts of whole blocks: zsplit is a multiple of 4 planes)
+        // into parts exactly like the ring's where that is (the march may use it only where the parts hold whole blocks)
         // (the march addresses it from the packed voxel index y | z << 16: both below 2^16, whatever the ray)
         Q.twin = (c->lod[l].twin && P.size[1] * Q.scale[1] < 65536.0f && P.size[2] * Q.scale[2] < 65536.0f) ? (uint32_t)c->lod[l].twin_policy : 0u;
         Q.twin_rbase = c->lod[l].twin;
         Q.twin_rbytes = (uint32_t)std::min<uint64_t>((uint64_t)c->lod[l].voxels * svr_dtype_size(c->density_storage) + 64, 0xFFFFFFFFull);
         if (P.per_lod_rsrc) {
-            const uint64_t des64 = svr_dtype_size(c->density_storage);
-            const uint64_t plane = (uint64_t)Q.ring[0] * (uint64_t)Q.ring[1] * des64, bytes = (uint64_t)c->lod[l].voxels * des64;
+            // one resource per LOD, or parts of whole ring z planes for a ring of 4 GiB or more (span_addressable checked the count)
+            const RingParts R = lod_ring_parts(c, l);
             Q.rbase = c->lod[l].density; Q.base_bytes = 0u;
-            static const int force_zsplit = svr_exp_env_int("SVR_FORCE_ZSPLIT", 0);      // (see rings_need_big)
-            if (force_zsplit > 0 && Q.ring[2] > 1u) {
-                Q.zsplit = std::max<uint32_t>((uint32_t)force_zsplit, (Q.ring[2] + 7u) / 8u);
-                if (Q.twin) Q.zsplit = (Q.zsplit + 3u) & ~3u;
-                Q.zsplit = std::min<uint32_t>(Q.zsplit, Q.ring[2]);
-                Q.nparts = (Q.ring[2] + Q.zsplit - 1u) / Q.zsplit;
-                Q.part_bytes = Q.rbytes = (uint32_t)((uint64_t)Q.zsplit * plane);
-                Q.rbytes_last = (uint32_t)(bytes - (uint64_t)(Q.nparts - 1) * Q.part_bytes + 64);
-                if (Q.nparts == 1u) { Q.rbytes = Q.rbytes_last; Q.part_bytes = 0u; }
-            } else if (bytes + 64 < ((uint64_t)1 << 32)) {
-                Q.rbytes = Q.rbytes_last = (uint32_t)(bytes + 64);
-            } else {                                         // parts of whole ring z planes (span_addressable checked the count)
-                Q.zsplit = (uint32_t)std::min<uint64_t>((uint64_t)Q.ring[2], (((uint64_t)1 << 32) - 128) / plane);
-                if (Q.zsplit < Q.ring[2] && Q.zsplit >= 4u) Q.zsplit &= ~3u;
-                Q.nparts = (uint32_t)(((uint64_t)Q.ring[2] + Q.zsplit - 1) / Q.zsplit);
-                Q.part_bytes = Q.rbytes = (uint32_t)((uint64_t)Q.zsplit * plane);
-                Q.rbytes_last = (uint32_t)(bytes - (uint64_t)(Q.nparts - 1) * Q.part_bytes + 64);
-            }
+            Q.nparts = R.nparts; Q.zsplit = R.zsplit; Q.part_bytes = R.part_bytes;
+            Q.rbytes = R.rbytes; Q.rbytes_last = R.rbytes_last;
             Q.twin_rbytes = Q.rbytes;                       // (a full part's size where the ring is cut; part_rsrc sizes the last one)
+            if (!R.twin_ok) Q.twin = 0u;                    // a part boundary inside a block: the march reads rows
         } else {
             Q.rbase = c->density_all; Q.rbytes = P.density_all_bytes;
         }
