@@ -11,7 +11,7 @@ from ._geometry import Coordinate, Roi
 from .compose import compose
 from .outline import outline
 from ._material import SubVolumeMaterial
-from ._transform import AffineTransform, PerspectiveCamera
+from ._transform import AffineTransform, OrthographicCamera, PerspectiveCamera
 from ._wobject import FrameRegion, RenderResult, SliceResult, SubVolume
 from ._wrapping_buffer import WrappingBuffer, subtract_rois
 
@@ -23,6 +23,7 @@ __all__ = [
     "Roi",
     "Coordinate",
     "PerspectiveCamera",
+    "OrthographicCamera",
     "AffineTransform",
     "FrameRegion",
     "RenderResult",

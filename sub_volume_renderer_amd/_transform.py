@@ -1,7 +1,7 @@
-"""Affine transform + perspective camera: the caller-side objects the path needs.
+"""Affine transform + perspective and orthographic cameras: the caller-side objects the path needs.
 
 In the reference these come from pygfx (``WorldObject.world`` /
-``gfx.PerspectiveCamera``, built on pylinalg 0.6.7) and only their matrices
+``gfx.PerspectiveCamera`` / ``gfx.OrthographicCamera``, built on pylinalg 0.6.7) and only their matrices
 reach the hot path: ``world.matrix`` / ``world.inverse_matrix``
 (``_wobject.py:186``; ``u_wobject.world_transform[_inv]``) and the camera's view /
 projection matrices (``u_stdinfo`` in vs_main.wgsl:19-22).  These small classes
@@ -171,6 +171,77 @@ class PerspectiveCamera(_HasWorld):
         m[2, 2] = far / (near - far)
         m[2, 3] = near * far / (near - far)
         m[3, 2] = -1.0
+        return m
+
+    @property
+    def projection_matrix_inverse(self) -> np.ndarray:
+        return np.linalg.inv(self.projection_matrix)
+
+
+class OrthographicCamera(_HasWorld):
+    """Orthographic (parallel-ray) camera producing the ``u_stdinfo`` matrices.
+
+    Arguments follow pygfx's ``OrthographicCamera``: ``width`` / ``height`` are the visible extent in world units,
+    divided by ``zoom``.  ``aspect`` is width / height of the frame (there is no canvas to read it from, as for
+    :class:`PerspectiveCamera`); with ``maintain_aspect`` the extent grows along one axis until its ratio is
+    ``aspect``, and is never shrunk.  Same conventions as :class:`PerspectiveCamera`: looks down its local -z with +y
+    up, depth maps linearly to [0, 1] with near -> 0 and far -> 1, and ``w`` is 1 for every point.
+
+    ``depth_range=(near, far)`` in world units along the view direction; near may be negative (a plane behind the
+    camera).  Without it, near / far = -1000 / +1000 times ``depth`` (default: the mean of width and height).  That
+    default is restated from pygfx's published text and is *parity unpinned*; tests always pass ``depth_range``.
+    """
+
+    def __init__(self, width: float = 1.0, height: float = 1.0, aspect: float = 1.0, *, zoom: float = 1.0,
+                 maintain_aspect: bool = True, depth: float | None = None,
+                 depth_range: tuple[float, float] | None = None):
+        super().__init__()
+        self.width = float(width)
+        self.height = float(height)
+        self.aspect = float(aspect)
+        self.zoom = float(zoom)
+        self.maintain_aspect = bool(maintain_aspect)
+        self.depth = depth
+        self.depth_range = depth_range
+
+    @property
+    def near_far(self) -> tuple[float, float]:
+        if self.depth_range is not None:
+            return float(self.depth_range[0]), float(self.depth_range[1])
+        d = 0.5 * (self.width + self.height) if self.depth is None else float(self.depth)
+        return -1000.0 * d, 1000.0 * d
+
+    @property
+    def extent(self) -> tuple[float, float]:
+        """The visible (width, height) in world units after ``zoom`` and ``maintain_aspect``."""
+        w, h = self.width / self.zoom, self.height / self.zoom
+        if self.maintain_aspect:
+            if w < h * self.aspect:
+                w = h * self.aspect
+            elif w > h * self.aspect:
+                h = w / self.aspect
+        return w, h
+
+    @property
+    def view_matrix(self) -> np.ndarray:
+        """``u_stdinfo.cam_transform`` = inverse of the camera's world matrix."""
+        return self.world.inverse_matrix
+
+    @property
+    def camera_matrix(self) -> np.ndarray:
+        """``u_stdinfo.cam_transform_inv``."""
+        return self.world.matrix
+
+    @property
+    def projection_matrix(self) -> np.ndarray:
+        near, far = self.near_far
+        w, h = self.extent
+        m = np.zeros((4, 4))
+        m[0, 0] = 2.0 / w
+        m[1, 1] = 2.0 / h
+        m[2, 2] = -1.0 / (far - near)           # view z = -near -> 0, view z = -far -> 1
+        m[2, 3] = -near / (far - near)
+        m[3, 3] = 1.0
         return m
 
     @property

@@ -402,10 +402,13 @@ class SubVolume(_HasWorld):
         self._material_version_pushed = m._version
 
     def _camera_key(self, camera):
+        # the projection enters as the bytes of its matrix, whatever kind of camera made it: every parameter of
+        # any projection (fov, width, height, zoom, aspect, depth range) changes the key exactly when it changes
+        # the matrix
         w, cw = self.world, camera.world
         return (id(camera), w._position.tobytes(), w._rot.tobytes(), w._scale.tobytes(),
                 cw._position.tobytes(), cw._rot.tobytes(), cw._scale.tobytes(),
-                camera.fov, camera.aspect, camera.zoom, camera.near_far, self._volume_dimensions.tobytes())
+                np.asarray(camera.projection_matrix, np.float64).tobytes(), self._volume_dimensions.tobytes())
 
     def camera_block(self, camera) -> "N.Camera":
         """The uniforms vs_main/fs_main read, as ``svr_camera`` (cached while nothing moved)."""

@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._material import SubVolumeMaterial
-from ._transform import AffineTransform, PerspectiveCamera
+from ._transform import AffineTransform, OrthographicCamera, PerspectiveCamera
 from ._wobject import FrameRegion, RenderResult, SubVolume
 
 
@@ -36,9 +36,16 @@ class SceneSpec:
     colorspace: str = "srgb"
     ring_storage: str = "native"
     blocked_twin: object = "auto"
+    projection: str = "perspective"               # or "orthographic"
+    ortho_size: tuple = (1.0, 1.0)                # visible (width, height) in world units of an orthographic camera
 
-    def camera(self) -> PerspectiveCamera:
-        cam = PerspectiveCamera(self.fov, self.width / self.height, depth_range=self.depth_range)
+    def camera(self) -> PerspectiveCamera | OrthographicCamera:
+        if self.projection == "orthographic":
+            cam = OrthographicCamera(self.ortho_size[0], self.ortho_size[1], self.width / self.height,
+                                     depth_range=self.depth_range)
+        else:
+            assert self.projection == "perspective", self.projection
+            cam = PerspectiveCamera(self.fov, self.width / self.height, depth_range=self.depth_range)
         cam.world.position = self.cam_position
         cam.look_at(self.cam_target)
         return cam
@@ -64,7 +71,7 @@ class SceneSpec:
 class BuiltScene:
     spec: SceneSpec
     volume: SubVolume
-    camera: PerspectiveCamera
+    camera: PerspectiveCamera | OrthographicCamera
     width: int
     height: int
 

@@ -310,3 +310,125 @@ def test_single_voxel_lands_where_the_camera_conventions_say(offset):
     # depth: the voxel's centre through proj * cam * world as fs_main.wgsl:61-72 writes it: (coord - 0.5) is a NORMALISED
     # coordinate there, so the depth belongs to a point next to the volume's origin corner: only its range is checked here
     assert np.all((r.depth[r.flags == 2] > 0) & (r.depth[r.flags == 2] < 1))
+
+
+# ---- orthographic cameras: parallel rays, exact-zero ray components, pixel centres on faces ------------------------
+import ortho_scenes as ortho  # noqa: E402
+
+
+def _restatements_agree(spec, pick_id=0x2A):
+    a = lmip.render_spec(spec, nthreads=2, pick_id=pick_id)
+    b = lmip_numpy.render_spec(spec, pick_id=pick_id)
+    for plane in ("flags", "steps", "label", "pick", "depth"):
+        np.testing.assert_array_equal(getattr(a, plane), b[plane], err_msg=plane)
+    np.testing.assert_allclose(a.rgba, b["rgba"], rtol=0, atol=2e-6)      # libm pow / exp may differ by an ulp
+    return a
+
+
+def _ortho_pairs(n=32, nlod=2):
+    from sub_volume_renderer_amd import synth
+
+    return [synth.volume(n, k, 64) for k in range(nlod)]
+
+
+def _ortho_base(width=64, height=64, **material):
+    # LOD 0's window (16^3 around a point off the centre) wraps around its ring and ends inside the view; LOD 1 covers
+    # the rest
+    return ortho.base_spec(_ortho_pairs(), [(8, 8, 8), (4, 4, 4)], [(2, 2, 2), (4, 4, 4)], width, height,
+                           centre=(13.0, 18.0, 11.0), **{"lmip_threshold": 120.0, **material})
+
+
+@pytest.mark.parametrize("view", ["+x", "-x", "+y", "-y", "+z", "-z"])
+@pytest.mark.parametrize("ppv,face", [(1, False), (1, True), (2, True)], ids=["centres", "faces", "faces-2ppv"])
+def test_orthographic_axis_views_restatements_agree(view, ppv, face):
+    spec = ortho.axis_view(_ortho_base(64 * ppv, 64 * ppv), view, ppv=ppv, face=face)   # 64 voxels wide: past both box faces
+    a_, s_ = ortho.AXES[view]
+    # two of the three direction components are exactly zero in the matrices both sides receive
+    d = ortho.direction_column(spec)
+    assert np.count_nonzero(d) == 1 and np.sign(d[a_]) == s_, d
+    near, ray = ortho.pixel_rays(spec)
+    assert np.all(np.delete(ray, a_, axis=0) == 0.0)
+    others = [k for k in range(3) if k != a_]
+    size = ortho.size_xyz(spec)
+    on_face = np.zeros(near.shape[1:], bool)
+    for k in others:
+        on_face |= ortho.face_distance(near[k]) == 0.0
+    if face:
+        assert on_face.sum() >= spec.width * spec.height // (2 if ppv == 2 else 1)
+        for k in others:                                   # ... the box faces among them: the 0/0 rays
+            assert np.any(near[k] == -0.5) and np.any(near[k] == size[k] - 0.5)
+    else:
+        assert not on_face.any()
+    r = _restatements_agree(spec)
+    assert (r.flags == 2).sum() > 100 and (r.flags == 0).sum() > 100
+
+
+@pytest.mark.parametrize("axis", [0, 1, 2])
+def test_orthographic_view_rotated_about_one_axis(axis):
+    """An exact rotation about one axis (3-4-5 triangle) set through rotation_matrix: about x or y the direction keeps
+    one exact zero and the two others are oblique; about z (the view axis) the screen axes are rolled."""
+    spec = _ortho_base(64, 32)
+    spec.projection, spec.ortho_size = "orthographic", (48.0, 24.0)
+    c, s = 0.6, 0.8
+    R = np.eye(3)
+    i, j = [k for k in range(3) if k != axis]
+    R[i, i], R[i, j], R[j, i], R[j, j] = c, -s, s, c
+    cam = spec.camera()
+    centre = np.array([15.5, 15.5, 15.5])
+    back = R @ np.array([0.0, 0.0, 1.0])                  # the camera's local +z (it looks down local -z)
+    cam.world.position = tuple(centre + 60.0 * back)
+    cam.world.rotation_matrix = R
+    spec.depth_range = (1.0, 200.0)
+    spec.camera = lambda cam=cam: cam                     # the hand-set pose, for the product and the oracle alike
+    d = ortho.direction_column(spec)
+    if axis == 2:                                         # a roll about the view axis: both screen axes oblique,
+        assert np.count_nonzero(d) == 1 and d[2] < 0, d   # the direction still exactly -z
+    else:
+        assert np.count_nonzero(d) == 2 and d[axis] == 0.0, d
+    r = _restatements_agree(spec)
+    assert (r.flags == 2).sum() > 100
+
+
+def test_orthographic_oblique_view():
+    spec = _ortho_base(64, 48)
+    spec.projection, spec.ortho_size = "orthographic", (50.0, 37.5)
+    spec.cam_position, spec.cam_target = (70.0, -35.0, 52.0), (15.5, 15.5, 15.5)
+    spec.depth_range = (1.0, 200.0)
+    assert np.all(ortho.direction_column(spec) != 0.0)
+    r = _restatements_agree(spec)
+    assert (r.flags == 2).sum() > 100 and (r.flags == 0).sum() > 100
+
+
+@pytest.mark.parametrize("view", ["-z", "+y", "oblique"])
+def test_orthographic_camera_inside_with_the_near_plane_behind_it(view):
+    spec = _ortho_base(64, 64)
+    eye = np.array([14.0, 17.0, 12.0])
+    d = {"-z": (0, 0, -1.0), "+y": (0, 1.0, 0), "oblique": (0.5, -0.3, 0.8)}[view]
+    spec.projection, spec.ortho_size = "orthographic", (24.0, 24.0)
+    spec.cam_position, spec.cam_target = tuple(eye), tuple(eye + np.array(d))
+    spec.depth_range = (-6.0, 40.0)                       # the near plane 6 units behind the camera, inside the volume
+    M = spec.matrices()
+    P = np.asarray(M["proj"], np.float64)
+    assert P[2, 3] > 0.0                                  # view z = 0 (the camera) maps to depth 6 / 46 > 0
+    r = _restatements_agree(spec)
+    assert (r.flags == 2).sum() > 100
+
+
+def test_orthographic_single_voxel_covers_exactly_the_predicted_pixel():
+    """The orthographic counterpart of test_single_voxel_lands_where_the_camera_conventions_say: one voxel per pixel,
+    a camera on the +x axis looking down -x with +y up (screen right is -z world, screen up is +y).  Where the voxel
+    lands follows from those conventions and the extent alone, and at one voxel per pixel it covers exactly one pixel."""
+    size, frame = 33, 32
+    for off in [(0, 5, 0), (0, 0, 5), (0, -7, 3), (6, 4, -9)]:
+        spec = testing.single_voxel_spec(off, size=size, frame=frame)
+        c = size // 2
+        spec.projection, spec.ortho_size = "orthographic", (float(frame), float(frame))
+        # the view's centre sits on a voxel corner: pixel centres fall on voxel centres (0.5 + integer offsets)
+        spec.cam_position, spec.cam_target = (c + 80.0, c + 0.5, c - 0.5), (float(c), c + 0.5, c - 0.5)
+        r = lmip.render_spec(spec)
+        rows, cols = np.nonzero(r.flags == 2)
+        # column: screen x = -z world; pixel i's centre is at z = (c - 0.5) - (i + 0.5 - 16) = c + 15 - i
+        # row: screen y = +y world; pixel j's centre is at y = (c + 0.5) + (16 - j - 0.5) = c + 16 - j
+        want_col, want_row = 15 - off[2], 16 - off[1]
+        assert rows.tolist() == [want_row] and cols.tolist() == [want_col], (off, rows, cols)
+        assert r.label[want_row, want_col] == 7

@@ -4,7 +4,9 @@ tests feed the SAME matrices to both sides, so a wrong convention would be invis
 are what stands in for that."""
 import numpy as np
 
-from sub_volume_renderer_amd._transform import AffineTransform, PerspectiveCamera
+import pytest
+
+from sub_volume_renderer_amd._transform import AffineTransform, OrthographicCamera, PerspectiveCamera
 
 
 def test_projection_matrix_fov_applies_to_the_mean_extent_and_depth_maps_to_0_1():
@@ -61,3 +63,72 @@ def test_affine_transform_composes_translate_rotate_scale():
     np.testing.assert_allclose(t.matrix @ np.array([1.0, 1.0, 1.0, 1.0]), [2, 3, 9, 1])
     np.testing.assert_allclose(t.inverse_matrix @ t.matrix, np.eye(4), atol=1e-12)
     assert t.scale_z == 6.0
+
+
+# ---- orthographic camera (pygfx OrthographicCamera conventions) ---------------------------------------------------
+def _ortho_want(w, h, near, far):
+    """x, y: [-w/2, w/2] x [-h/2, h/2] -> [-1, 1]^2;  view z = -near -> 0, view z = -far -> 1;  w = 1."""
+    return np.array([[2.0 / w, 0, 0, 0],
+                     [0, 2.0 / h, 0, 0],
+                     [0, 0, -1.0 / (far - near), -near / (far - near)],
+                     [0, 0, 0, 1.0]])
+
+
+@pytest.mark.parametrize("w,h,aspect,maintain,zoom,want_wh", [
+    (16.0, 16.0, 1.0, True, 1.0, (16.0, 16.0)),          # square extent, square frame
+    (16.0, 16.0, 1.0, False, 1.0, (16.0, 16.0)),
+    (20.0, 10.0, 2.0, True, 1.0, (20.0, 10.0)),          # non-square extent that already has the frame's ratio
+    (20.0, 10.0, 1.0, True, 1.0, (20.0, 20.0)),          # frame squarer than the extent: the height grows
+    (20.0, 10.0, 4.0, True, 1.0, (40.0, 10.0)),          # frame wider than the extent: the width grows
+    (20.0, 10.0, 1.0, False, 1.0, (20.0, 10.0)),         # maintain_aspect off: stretched, nothing grows
+    (20.0, 10.0, 4.0, False, 1.0, (20.0, 10.0)),
+    (16.0, 8.0, 2.0, True, 2.0, (8.0, 4.0)),             # zoom 2 halves the extent
+    (16.0, 8.0, 1.0, True, 0.5, (32.0, 32.0)),           # zoom 1/2 doubles it, then the height grows to the ratio
+])
+def test_orthographic_projection_known_answers(w, h, aspect, maintain, zoom, want_wh):
+    cam = OrthographicCamera(w, h, aspect, zoom=zoom, maintain_aspect=maintain, depth_range=(2.0, 10.0))
+    assert cam.extent == want_wh
+    P = cam.projection_matrix
+    np.testing.assert_array_equal(P, _ortho_want(*want_wh, 2.0, 10.0))      # every entry exact (powers of two etc.)
+    np.testing.assert_allclose(cam.projection_matrix_inverse @ P, np.eye(4), atol=1e-12)
+    # the corners of the visible extent at the near plane -> NDC (+-1, +-1, 0); on the far plane z = 1
+    hw, hh = want_wh[0] / 2.0, want_wh[1] / 2.0
+    for sx in (-1.0, 1.0):
+        for sy in (-1.0, 1.0):
+            np.testing.assert_allclose(P @ np.array([sx * hw, sy * hh, -2.0, 1.0]), [sx, sy, 0.0, 1.0], atol=1e-12)
+            np.testing.assert_allclose(P @ np.array([sx * hw, sy * hh, -10.0, 1.0]), [sx, sy, 1.0, 1.0], atol=1e-12)
+
+
+def test_orthographic_depth_is_linear_and_w_is_one_everywhere():
+    cam = OrthographicCamera(12.0, 6.0, 2.0, depth_range=(-4.0, 12.0))     # near plane 4 units BEHIND the camera
+    P = cam.projection_matrix
+    rng = np.random.default_rng(0)
+    pts = np.concatenate([rng.uniform(-50, 50, (200, 3)), np.ones((200, 1))], axis=1)
+    c = pts @ P.T
+    np.testing.assert_array_equal(c[:, 3], 1.0)                             # no perspective divide at all
+    np.testing.assert_allclose(c[:, 2], (-pts[:, 2] + 4.0) / 16.0, rtol=0, atol=1e-12)     # linear in distance
+    assert (P @ np.array([0, 0, 4.0, 1]))[2] == 0.0                          # near plane (behind the camera)
+    assert (P @ np.array([0, 0, -12.0, 1]))[2] == 1.0                        # far plane
+    # x / y do not depend on depth: parallel rays
+    a, b = P @ np.array([1.5, -2.0, -1.0, 1.0]), P @ np.array([1.5, -2.0, -11.0, 1.0])
+    assert a[0] == b[0] == 0.25 and a[1] == b[1] == -2.0 / 3.0
+
+
+def test_orthographic_camera_pose_conventions_match_the_perspective_camera():
+    o, p = OrthographicCamera(8.0, 8.0, 1.0, depth_range=(1.0, 9.0)), PerspectiveCamera(45.0, 1.0, depth_range=(1.0, 9.0))
+    for cam in (o, p):
+        cam.world.position = (3.0, 4.0, 20.0)
+        cam.look_at((3.0, 4.0, 0.0))
+    np.testing.assert_array_equal(o.view_matrix, p.view_matrix)
+    np.testing.assert_array_equal(o.camera_matrix, p.camera_matrix)
+    # a point 5 units in front of the camera, 1 unit to its right and 2 up: NDC x = 1 / 4, y = 2 / 4, depth (5-1)/8
+    c = o.projection_matrix @ o.view_matrix @ np.array([4.0, 6.0, 15.0, 1.0])
+    np.testing.assert_allclose(c, [0.25, 0.5, 0.5, 1.0], atol=1e-12)
+
+
+def test_orthographic_default_depth_range():
+    """The default near / far (no depth_range) is restated and parity unpinned; this only pins what it is here."""
+    cam = OrthographicCamera(10.0, 30.0)
+    assert cam.near_far == (-20000.0, 20000.0)
+    cam.depth = 2.0
+    assert cam.near_far == (-2000.0, 2000.0)

@@ -5,7 +5,7 @@ inside / grazing), materials (LMIP, MIP and weighted average, clipping planes), 
 (empty-space skipping on and off, bricks always / never / by probe, tile shapes, placements).  Integer planes must be identical, float planes within 1e-4.
 Every case runs BOTH instantiations of the march (`production`: count_steps off, the code object bench.py times;
 `instrumented`: the COUNT build with exact step counts) unless `kernel=` names one.
-usage: fuzz_parity.py [cases] [first_seed] [brick] [kernel=both|production|instrumented]
+usage: fuzz_parity.py [cases] [first_seed] [brick] [ortho] [kernel=both|production|instrumented]
 (prints one line per failing case, then a summary)"""
 import os
 import sys
@@ -22,9 +22,11 @@ VARIANTS = [0x000, 0x000, 0x200, 0x100, 0x002, 0x2000, 0x4000, 0x250, 0x230, 0x0
 BRICK_VARIANTS = [0x200, 0x200, 0x204, 0x230, 0x250, 0xA202, 0x2200, 0x000, 0x208]
 
 
-def random_spec(seed, brick=False):
+def random_spec(seed, brick=False, ortho=False):
     """``brick=True`` biases the draw towards scenes that stage LDS bricks: 16-voxel chunks along x, byte
-    data, larger volumes and frames, variants that always stage."""
+    data, larger volumes and frames, variants that always stage.  ``ortho=True`` replaces the perspective camera by
+    an orthographic one (axis-aligned, axis-aligned with small tilts, or oblique; outside or inside the volume;
+    1/2 to 3 voxels per pixel), drawn after everything else: ``ortho=False`` draws exactly the scenes it always did."""
     rng = np.random.default_rng(seed)
     nl = int(rng.integers(1, 5))
     chunk0 = [int(rng.choice([4, 8])), int(rng.choice([4, 8])), int(rng.choice([8, 16, 12]))]
@@ -130,7 +132,38 @@ def random_spec(seed, brick=False):
     if last[0] < 0.08 and spec.material.get("render_mode", "lmip") == "lmip":
         spec.material["render_mode"] = "weighted_average"
         spec.material["weight_falloff"] = float(rng.choice([0.0, 0.5, last[1] * 6.0]))
+    if ortho:
+        _orthographic_camera(spec, rng, size_xyz)
     return spec, region, variant
+
+
+def _orthographic_camera(spec, rng, size_xyz):
+    """An orthographic camera for `spec` (data coordinates mapped through the spec's world transform)."""
+    kind = int(rng.integers(0, 3))                  # 0 axis-aligned, 1 axis-aligned with small tilts, 2 oblique
+    inside = rng.random() < 0.3
+    if kind == 2:
+        d = rng.normal(size=3)
+    else:
+        d = np.zeros(3)
+        d[int(rng.integers(0, 3))] = rng.choice([-1.0, 1.0])
+        if kind == 1:
+            d += rng.choice([0.0, 0.01, 0.05], 3) * rng.normal(size=3)
+    d /= np.linalg.norm(d)
+    if inside:
+        eye = size_xyz * rng.uniform(0.15, 0.85, 3)
+    else:
+        eye = size_xyz * rng.uniform(0.2, 0.8, 3) - d * size_xyz.max() * rng.uniform(0.8, 2.0)
+    if kind == 0 and rng.random() < 0.6:            # screen-plane position on voxel centres / faces / quarters
+        eye = np.where(d == 0.0, np.floor(eye) + rng.choice([0.0, 0.25, 0.5]), eye)
+    vpp = float(rng.uniform(0.5, 3.0))              # voxels per pixel
+    ws, wp = np.array(spec.world_scale), np.array(spec.world_position)
+    scale = float(np.mean(ws))
+    spec.projection = "orthographic"
+    spec.ortho_size = (spec.width * vpp * scale, spec.height * vpp * scale)
+    spec.cam_position = tuple(float(v) for v in eye * ws + wp)
+    spec.cam_target = tuple(float(v) for v in (eye + d) * ws + wp)
+    reach = float(size_xyz.max()) * 4.0 * float(ws.max())
+    spec.depth_range = (-float(rng.uniform(0.0, 0.5)) * reach, reach) if inside else (float(rng.uniform(0.0, 1.0)), reach)
 
 
 def main():
@@ -139,6 +172,7 @@ def main():
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     first = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     brick = "brick" in sys.argv[3:]
+    ortho = "ortho" in sys.argv[3:]
     kernel = ([a.split("=", 1)[1] for a in sys.argv[3:] if a.startswith("kernel=")] or ["both"])[0]
     assert kernel in ("both", "production", "instrumented"), kernel
     runs = {"both": (False, True), "production": (False,), "instrumented": (True,)}[kernel]
@@ -148,7 +182,7 @@ def main():
         if (seed - first) % 1000 == 999:                     # long campaigns: a sign of life once a minute or so
             print(f"... {seed - first + 1} of {cases} cases, {bad} mismatching so far", file=sys.stderr, flush=True)
         try:
-            spec, region, variant = random_spec(seed, brick)
+            spec, region, variant = random_spec(seed, brick, ortho)
             ovol = lmip.oracle_volume(spec)
         except Exception as e:          # a configuration the reference's own assertions reject
             skipped += 1
@@ -185,7 +219,7 @@ def main():
         hits += rep["n_hit"] > 0
         bad += not ok
         del scene
-    print(f"fuzz{' (brick-biased)' if brick else ''} kernel={kernel}: {cases} cases from seed {first}: {bad} mismatching, {skipped} rejected by both, "
+    print(f"fuzz{' (brick-biased)' if brick else ''}{' (orthographic)' if ortho else ''} kernel={kernel}: {cases} cases from seed {first}: {bad} mismatching, {skipped} rejected by both, "
           f"{hits} with hits, {bricks} staged LDS bricks, {twins} gathered from a micro-block copy", flush=True)
     sys.exit(1 if bad else 0)
 
