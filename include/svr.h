@@ -456,6 +456,51 @@ typedef struct svr_slab_params {
 int  svr_slab(svr_ctx* ctx, const svr_slab_params* params, const svr_frame* frame, const svr_slice_outputs* out,
               void* stream);
 
+/* ---- composite render mode: front-to-back emission-absorption compositing (direct volume rendering) through a
+ * transfer function, along the march's rays (no counterpart in the reference; FUTURE.md's "swappable rendering
+ * pipeline").  An addition within ABI version 9: new symbols only; svr_material, svr_outputs and svr_render keep their
+ * layout and behaviour.  Defined HERE (numpy restatement: tests/composite_twin.py), in f32, in this order, with no
+ * fused operations.  Per pixel:
+ *   ray      the march's: pixel -> frame through svr_frame, the DISCARD rules, the clipping planes (ANY / ALL), start,
+ *            step and nsteps exactly as svr_render's setup (orthographic cameras included).
+ *   samples  i = 0 .. nsteps-1 where the march puts them: off = iter * step, coord = start + off (iter the float
+ *            counter of the march), dx = coord * size; the first LOD whose ROI holds dx gives the value s and the label
+ *            lab (0 without label rings).  A sample that no LOD holds contributes nothing (it is counted in steps).
+ *   table    T of K entries (2 <= K <= SVR_TF_MAX_ENTRIES), RGBA with RGB in linear light and alpha already corrected
+ *            for the step (svr_set_transfer_function):
+ *              v   = (s - clim[0]) / (clim[1] - clim[0])
+ *              x   = fminf(fmaxf(v * (float)(K-1), 0.0f), (float)(K-1))          (NaN -> 0)
+ *              j   = min((int)x, K-2);  f = x - (float)j
+ *              e_c = T[j].c + f * (T[j+1].c - T[j].c)                              c = r, g, b, a
+ *   tint     color_by_label: q = hsv_to_rgb(h, s, 1.0f) of colors[lab % color_count];  e_rgb = e_rgb * q per component
+ *   compose  R = G = B = A = 0, w_best = 0, then per sample in order:
+ *              w = (1.0f - A) * e_a
+ *              R = R + w * e_r;  G = G + w * e_g;  B = B + w * e_b;  A = A + w
+ *              if (w > w_best)  { w_best = w; best = i }                           (strict: the first wins)
+ *              if (first unset and w > 0)  first = i
+ *              if (A >= alpha_cutoff)  stop after this sample
+ *   outputs  HIT when A > 0: rgba = (R/A, G/A, B/A, A * opacity) (straight alpha); depth = the march's depth formula
+ *              at the coordinate of `first`; label = the label at the coordinate of `best`; pick = the march's packing
+ *              of `best`'s coordinate.
+ *            MISS when the ray ran but A == 0: rgba (0,0,0,0) (transparent, unlike LMIP's opaque black), depth, label
+ *              and pick 0.
+ *            DISCARD as in the march.
+ *            steps (when not NULL; written by this kernel, no instrumented build): the samples visited.
+ * The material's clim, opacity, colors and clipping planes are read; gamma, fog, colorspace_srgb, the lmip_* fields
+ * and render_mode are not.  A render-thread call like svr_render: it waits for published uploads, later uploads wait
+ * for it.  Enqueued on `stream`; asynchronous.  SVR_ERR_INVALID, with nothing enqueued, when no material or no table
+ * has been set, alpha_cutoff is not in (0, 1], or any frame or camera check of svr_render fails. */
+#define SVR_TF_MAX_ENTRIES 4096
+/* rgba: HOST pointer to K x 4 floats, each finite and in [0, 1], else SVR_ERR_INVALID.  Copied to the device; ordered
+ * like svr_set_material (composites enqueued earlier keep the table they were enqueued with). */
+int  svr_set_transfer_function(svr_ctx* ctx, const float* rgba, int32_t K);
+typedef struct svr_composite_params {
+    float   alpha_cutoff;          /* (0, 1]: the ray stops once its accumulated opacity reaches it */
+    int32_t color_by_label;        /* 1: tint each sample's colour by its label's hue */
+} svr_composite_params;
+int  svr_composite(svr_ctx* ctx, const svr_camera* cam, const svr_frame* frame, const svr_composite_params* params,
+                   const svr_outputs* out, void* stream);
+
 /* ---- sync */
 int  svr_sync(svr_ctx* ctx);                 /* both streams idle */
 int  svr_sync_uploads(svr_ctx* ctx);         /* upload stream idle */

@@ -11,6 +11,7 @@ from ._geometry import Coordinate, Roi
 from .compose import compose
 from .outline import outline
 from ._material import SubVolumeMaterial
+from ._transfer import TransferFunction
 from ._transform import AffineTransform, OrthographicCamera, PerspectiveCamera
 from ._wobject import FrameRegion, RenderResult, SliceResult, SubVolume
 from ._wrapping_buffer import WrappingBuffer, subtract_rois
@@ -18,6 +19,7 @@ from ._wrapping_buffer import WrappingBuffer, subtract_rois
 __all__ = [
     "SubVolume",
     "SubVolumeMaterial",
+    "TransferFunction",
     "WrappingBuffer",
     # replacements for what the reference imports from funlib.geometry / pygfx
     "Roi",

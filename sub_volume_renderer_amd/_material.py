@@ -75,6 +75,9 @@ class SubVolumeMaterial:
         self.clipping_mode = "ANY"
         self.render_mode = "lmip"
         self.weight_falloff = 0.5
+        self.transfer_function = None
+        self.alpha_cutoff = 0.99
+        self.color_by_label = False
         arguments = dict(clim=clim, gamma=gamma, opacity=opacity, lmip_threshold=lmip_threshold,
                          lmip_fall_off=lmip_fall_off, lmip_max_samples=lmip_max_samples, fog_density=fog_density,
                          fog_color=fog_color,
@@ -151,7 +154,7 @@ class SubVolumeMaterial:
         self._store("clipping_mode", mode)
 
     # -- render mode: the swappable raycast the reference wishes for (FUTURE.md:97-120) -------------------------
-    RENDER_MODES = ("lmip", "mip", "weighted_average")
+    RENDER_MODES = ("lmip", "mip", "weighted_average", "composite")
 
     @property
     def render_mode(self) -> str:
@@ -164,7 +167,11 @@ class SubVolumeMaterial:
         "weighted_average": the mode FUTURE.md:97-109 wishes for ("weight each sample by distance ... sampling a
         finite number of points based on distance") and gives no formula for; defined in ``include/svr.h``
         (``SVR_MODE_WEIGHTED_AVERAGE``): sample i weighs ``max(1 - weight_falloff * d_i, 0) ** 2``, the pixel shows
-        the weighted mean of the ray's samples at the sample that contributes most."""
+        the weighted mean of the ray's samples at the sample that contributes most.
+
+        "composite": direct volume rendering — front-to-back emission-absorption compositing of every sample's colour
+        and opacity from ``transfer_function`` until the ray's opacity reaches ``alpha_cutoff`` (``svr_composite`` in
+        ``include/svr.h``).  Hit pixels carry straight alpha; rays that gather no opacity are transparent misses."""
         return self._u["render_mode"]
 
     @render_mode.setter
@@ -187,6 +194,50 @@ class SubVolumeMaterial:
         if not (0.0 <= value < float("inf")):
             raise ValueError(f"weight_falloff must be finite and >= 0, not {value!r}")
         self._store("weight_falloff", np.float32(value))
+
+    # -- composite mode (svr_composite) --------------------------------------------------------------------
+    @property
+    def transfer_function(self):
+        """The ``TransferFunction`` of the "composite" mode; None (the default) means ``TransferFunction.linear()``."""
+        return self._u["transfer_function"]
+
+    @transfer_function.setter
+    def transfer_function(self, tf) -> None:
+        from ._transfer import TransferFunction
+
+        if tf is not None and not isinstance(tf, TransferFunction):
+            raise ValueError(f"transfer_function must be a TransferFunction or None, not {type(tf).__name__}")
+        self._store("transfer_function", tf)
+
+    def effective_transfer_function(self):
+        """``transfer_function``, or the default one when it is None."""
+        from ._transfer import default_transfer_function
+
+        tf = self._u["transfer_function"]
+        return default_transfer_function() if tf is None else tf
+
+    @property
+    def alpha_cutoff(self) -> float:
+        """"composite" mode: a ray stops once its accumulated opacity reaches this value, in (0, 1]."""
+        return float(self._u["alpha_cutoff"])
+
+    @alpha_cutoff.setter
+    def alpha_cutoff(self, value) -> None:
+        if isinstance(value, (str, bytes)) or not isinstance(value, numbers.Real):
+            raise ValueError(f"alpha_cutoff must be a number in (0, 1], not {value!r}")
+        v = np.float32(float(value))
+        if not (0.0 < v <= 1.0):
+            raise ValueError(f"alpha_cutoff must be in (0, 1] (as float32), not {value!r}")
+        self._store("alpha_cutoff", v)
+
+    @property
+    def color_by_label(self) -> bool:
+        """"composite" mode: tint each sample's colour by the hue of its label (``colors``)."""
+        return bool(self._u["color_by_label"])
+
+    @color_by_label.setter
+    def color_by_label(self, value) -> None:
+        self._store("color_by_label", bool(value))
 
     def lmip_uniforms(self) -> tuple[float, float, int]:
         """(threshold, fall_off, max_samples) as the draw sends them for the current render mode."""

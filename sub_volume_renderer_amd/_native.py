@@ -147,6 +147,13 @@ SLAB_MODES = {"max": 0, "min": 1, "mean": 2}        # SVR_SLAB_*
 SLAB_MAX_SAMPLES = 4096
 
 
+class CompositeParams(C.Structure):
+    _fields_ = [("alpha_cutoff", C.c_float), ("color_by_label", C.c_int32)]
+
+
+TF_MAX_ENTRIES = 4096                               # SVR_TF_MAX_ENTRIES
+
+
 _I3 = C.c_int32 * 3
 _L3 = C.c_int64 * 3
 
@@ -191,6 +198,9 @@ SIGNATURES = {
                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "svr_slice": (C.c_int, [C.c_void_p, C.POINTER(SlicePlane), C.POINTER(Frame), C.POINTER(SliceOutputs), C.c_void_p]),
     "svr_slab": (C.c_int, [C.c_void_p, C.POINTER(SlabParams), C.POINTER(Frame), C.POINTER(SliceOutputs), C.c_void_p]),
+    "svr_set_transfer_function": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "svr_composite": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Frame), C.POINTER(CompositeParams),
+                                C.POINTER(Outputs), C.c_void_p]),
     "svr_sync": (C.c_int, [C.c_void_p]),
     "svr_sync_uploads": (C.c_int, [C.c_void_p]),
     "svr_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),

@@ -185,6 +185,7 @@ class SubVolume(_HasWorld):
         self._volume_dimensions = np.zeros(3, np.float32)
         self.volume_dimensions = base_data.shape
         self._material_version_pushed = -1
+        self._tf_pushed = None            # (TransferFunction, volume_dimensions bytes) of the table on the device
         # pygfx gives every world object a process-wide id (the shader packs its low 20 bits into the pick word)
         SubVolume._next_id = getattr(SubVolume, "_next_id", 0) + 1
         self.id = SubVolume._next_id
@@ -396,10 +397,24 @@ class SubVolume(_HasWorld):
         cm.clipping_plane_count = int(planes.shape[0])
         cm.clipping_mode_all = 1 if u["clipping_mode"] == "ALL" else 0
         cm.clipping_planes = planes.ctypes.data_as(C.POINTER(C.c_float))
+        # "composite" sends LMIP here: svr_composite does not read the mode (its table goes through _push_transfer_function)
         cm.render_mode = N.SVR_MODE_WEIGHTED_AVERAGE if u["render_mode"] == "weighted_average" else N.SVR_MODE_LMIP
         cm.weight_falloff = float(u["weight_falloff"])
         N.check(N.lib().svr_set_material(self._rings.handle, C.byref(cm)), "svr_set_material")
         self._material_version_pushed = m._version
+
+    def _push_transfer_function(self):
+        """Send the composite mode's table (alpha corrected for this volume's sample spacing) when the transfer
+        function or ``volume_dimensions`` changed since the last one sent."""
+        tf = self.material.effective_transfer_function()
+        key = (tf, self._volume_dimensions.tobytes())
+        pushed = self._tf_pushed
+        if pushed is not None and pushed[0] is key[0] and pushed[1] == key[1]:
+            return
+        table = np.ascontiguousarray(tf.device_table(self._volume_dimensions), np.float32)
+        N.check(N.lib().svr_set_transfer_function(self._rings.handle, table.ctypes.data, table.shape[0]),
+                "svr_set_transfer_function")
+        self._tf_pushed = key
 
     def _camera_key(self, camera):
         # the projection enters as the bytes of its matrix, whatever kind of camera made it: every parameter of
@@ -504,6 +519,14 @@ class SubVolume(_HasWorld):
             self._ob_cache[okey] = (res, ob)
         if stream is None:
             stream = torch.cuda.current_stream(self._rings.device).cuda_stream
+        if self.material.render_mode == "composite":
+            # direct volume rendering (svr_composite): same camera block, frame and outputs; its steps plane is
+            # written by the production kernel
+            self._push_transfer_function()
+            cp = N.CompositeParams(self.material.alpha_cutoff, 1 if self.material.color_by_label else 0)
+            N.check(N.lib().svr_composite(handle, C.byref(cb), C.byref(fb), C.byref(cp), C.byref(ob), C.c_void_p(stream)),
+                    "svr_composite")
+            return res
         N.check(
             N.lib().svr_render(handle, C.byref(cb), C.byref(fb), C.byref(ob), C.c_void_p(stream)),
             "svr_render",

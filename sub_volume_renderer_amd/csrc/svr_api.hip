@@ -50,6 +50,42 @@ hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const s
 // slice_kernels.hip (same reason).  dw: the data-space sample step, computed and checked by svr_slab.
 hipError_t svr_launch_slab(const svr_ctx* c, const svr_slab_params& sp, const float dw[3], const svr_frame& fr,
                            const svr_slice_outputs& out, int twin_mode, hipStream_t stream);
+// composite_kernels.hip (same reason).  table: the device copy of the transfer function, K entries of RGBA.
+hipError_t svr_launch_composite(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr,
+                                const svr_composite_params& cp, const svr_outputs& out, const float* table, int K,
+                                hipStream_t stream);
+
+namespace {
+
+// Transfer functions of svr_set_transfer_function, per context.  Kept here rather than in svr_ctx (svr_internal.h is
+// part of the kernel-source stamp).  Like the colour table of svr_set_material, every new table goes into a fresh
+// device buffer; the replaced ones are freed once the device has drained (or with the context).
+struct TransferTable {
+    const svr_ctx* ctx;
+    float* dev;
+    int K;
+    std::vector<float*> retired;
+};
+std::mutex g_tf_mu;
+std::vector<TransferTable> g_tf;
+
+TransferTable* transfer_table(const svr_ctx* c) {       // (under g_tf_mu)
+    for (auto& t : g_tf) if (t.ctx == c) return &t;
+    return nullptr;
+}
+
+void drop_transfer_table(const svr_ctx* c) {
+    std::lock_guard<std::mutex> lock(g_tf_mu);
+    for (size_t k = 0; k < g_tf.size(); ++k) {
+        if (g_tf[k].ctx != c) continue;
+        if (g_tf[k].dev) (void)hipFree(g_tf[k].dev);
+        for (float* p : g_tf[k].retired) (void)hipFree(p);
+        g_tf.erase(g_tf.begin() + (long)k);
+        return;
+    }
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -206,6 +242,7 @@ int svr_destroy(svr_ctx* c) {
     }
     if (c->colors_dev) (void)hipFree(c->colors_dev);
     for (float* p : c->colors_retired) (void)hipFree(p);
+    drop_transfer_table(c);
     if (c->dbg_dev) (void)hipFree(c->dbg_dev);
     for (auto& t : c->tile_orders) if (t.dev) (void)hipFree(t.dev);
     for (auto& t : c->cost_orders) {
@@ -1196,6 +1233,64 @@ int svr_slab(svr_ctx* c, const svr_slab_params* sp, const svr_frame* fr, const s
     // ordered like svr_slice: behind the published uploads, and later uploads behind this slab (mark_render)
     if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
     SVR_HIP_TRY(svr_launch_slab(c, *sp, dw, f, *out, twin_mode, s));
+    return mark_render(c, s);
+}
+
+int svr_set_transfer_function(svr_ctx* c, const float* rgba, int32_t K) {
+    SVR_REQUIRE(c && rgba, "svr_set_transfer_function: null argument");
+    SVR_REQUIRE(K >= 2 && K <= SVR_TF_MAX_ENTRIES, "svr_set_transfer_function: K must be in 2 .. 4096");
+    for (int32_t k = 0; k < 4 * K; ++k)
+        SVR_REQUIRE(rgba[k] >= 0.0f && rgba[k] <= 1.0f, "svr_set_transfer_function: every entry must be finite and in [0, 1]");
+    DeviceGuard guard(c->device);
+    float* fresh = nullptr;
+    if (hipMalloc((void**)&fresh, (size_t)K * 4 * sizeof(float)) != hipSuccess) {
+        svr_set_error("svr_set_transfer_function: out of device memory"); return SVR_ERR_NOMEM;
+    }
+    if (hipMemcpy(fresh, rgba, (size_t)K * 4 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(fresh);
+        svr_set_error("svr_set_transfer_function: hipMemcpy failed"); return SVR_ERR_HIP;
+    }
+    std::lock_guard<std::mutex> lock(g_tf_mu);
+    TransferTable* t = transfer_table(c);
+    if (!t) {
+        g_tf.push_back(TransferTable{ c, nullptr, 0, {} });
+        t = &g_tf.back();
+    }
+    if (t->dev) t->retired.push_back(t->dev);        // composites still in flight keep reading the old table
+    if (t->retired.size() > 32) {                    // bounded: drain once in a long while
+        SVR_HIP_TRY(hipDeviceSynchronize());
+        for (float* p : t->retired) (void)hipFree(p);
+        t->retired.clear();
+    }
+    t->dev = fresh;
+    t->K = K;
+    return SVR_OK;
+}
+
+int svr_composite(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, const svr_composite_params* cp,
+                  const svr_outputs* out, void* stream) {
+    SVR_REQUIRE(c && cam && fr && cp && out && out->rgba, "svr_composite: null argument");
+    SVR_REQUIRE(c->material_set, "svr_composite: svr_set_material has not been called");
+    SVR_REQUIRE(fr->frame_w > 0 && fr->frame_h > 0 && fr->out_w > 0 && fr->out_h > 0, "svr_composite: empty frame");
+    SVR_REQUIRE(fr->x0 >= 0 && fr->y0 >= 0, "svr_composite: negative tile origin");
+    for (int a = 0; a < 3; ++a)
+        SVR_REQUIRE(cam->volume_dimensions[a] >= 1.0f, "svr_composite: volume_dimensions must be >= 1");
+    SVR_REQUIRE(cp->alpha_cutoff > 0.0f && cp->alpha_cutoff <= 1.0f, "svr_composite: alpha_cutoff must be in (0, 1]");
+    const float* table = nullptr;
+    int K = 0;
+    {
+        std::lock_guard<std::mutex> lock(g_tf_mu);
+        const TransferTable* t = transfer_table(c);
+        if (t) { table = t->dev; K = t->K; }
+    }
+    SVR_REQUIRE(table, "svr_composite: svr_set_transfer_function has not been called");
+    svr_frame f = *fr;
+    if (f.band_h <= 0) { f.band_h = fr->out_h; f.band_pitch = fr->out_h; }
+    DeviceGuard guard(c->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);         // NULL = default stream, as in svr_render
+    // ordered like a render: behind the published uploads, and later uploads behind this composite (mark_render)
+    if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
+    SVR_HIP_TRY(svr_launch_composite(c, *cam, f, *cp, *out, table, K, s));
     return mark_render(c, s);
 }
 

@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""Time svr_composite (the composite render mode, include/svr.h) at 1920 x 1080 on the BASELINE config 2 scene (1024^3,
+the bench's workload) seen from camera K1, for two transfer functions:
+  a  faint: alpha <= 0.02 over the whole range, cutoff 1.0 — no ray terminates early, so every ray visits every sample
+     (the count is checked against the instrumented march's steps in full LMIP mode, the same rays);
+  b  opaque: alpha 0 below 0.3 of the range, rising to 1 at 0.6, cutoff 0.99 — rays stop at the first dense structure.
+Called through the C ABI with prebuilt argument structs (steps = NULL: the production call), timed as
+tools/slab_time.py times slabs:
+  call_ms  HIP events around back-to-back calls;
+  gpu_ms   the same calls queued behind a sleep kernel (GPU time per call, free of host pacing).
+Per case also the samples the kernel visits (the sum of the steps plane of one render with count_steps=True) and
+samples per second at gpu_ms.  Kernel durations proper come from a separate traced run, one case per run:
+
+usage: python tools/composite_time.py [--case a|b|all] [--storage native|float32] [--calls 20] [--boxes 3]
+       rocprofv3 --kernel-trace --stats --kernel-include-regex composite -d DIR -o comp --output-format csv -- \\
+           python tools/composite_time.py --case a --calls 20 --boxes 1
+       python tools/composite_time.py --stats DIR          (no GPU needed: the composite kernels of DIR's *kernel_stats.csv)
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def transfer_functions():
+    from sub_volume_renderer_amd import TransferFunction
+
+    return {
+        "a": (TransferFunction.linear(color=(1.0, 0.9, 0.7), opacity=0.02), 1.0),
+        "b": (TransferFunction.from_points([(0.0, (0.0, 0.0, 0.0, 0.0)), (0.3, (0.2, 0.3, 0.8, 0.0)),
+                                            (0.6, (1.0, 0.7, 0.3, 1.0))]), 0.99),
+    }
+
+
+def stats(path):
+    for name in sorted(glob.glob(os.path.join(path, "**", "*kernel_stats.csv"), recursive=True)):
+        with open(name) as f:
+            for row in csv.DictReader(f):
+                if "composite" in row.get("Name", ""):
+                    print(json.dumps({"file": os.path.relpath(name, path), "kernel": row["Name"][:80],
+                                      "calls": int(row["Calls"]), "average_ms": round(float(row["AverageNs"]) / 1e6, 4),
+                                      "min_ms": round(float(row["MinNs"]) / 1e6, 4),
+                                      "max_ms": round(float(row["MaxNs"]) / 1e6, 4)}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--case", default="all", choices=("a", "b", "all"))
+    ap.add_argument("--storage", default="native", choices=("native", "float32"))
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--boxes", type=int, default=3)
+    ap.add_argument("--volume-n", type=int, default=1024)
+    ap.add_argument("--stats", default=None, help="print the composite kernels of a --stats run's CSV instead of timing")
+    args = ap.parse_args()
+    if args.stats:
+        return stats(args.stats)
+
+    import ctypes as C
+
+    import torch
+
+    import bench
+    from sub_volume_renderer_amd import _native as N, synth, testing
+
+    if not torch.cuda.is_available():
+        raise SystemExit("composite_time.py needs a GPU")
+    dev = torch.device("cuda", 0)
+    n_vol, W, H = args.volume_n, 1920, 1080
+    pairs = [synth.volume(n_vol, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
+    torch.cuda.synchronize()
+    stream = torch.cuda.current_stream(dev)
+    lib = N.lib()
+
+    def window(calls, hold_cycles=0):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        if hold_cycles:
+            torch.cuda._sleep(hold_cycles)
+        a.record(stream)
+        calls()
+        b.record(stream)
+        b.synchronize()
+        return a.elapsed_time(b) / 1e3
+
+    probe = 10_000_000
+    per_cycle = window(lambda: torch.cuda._sleep(probe)) / probe
+
+    spec = bench.config2_spec(n_vol, W, H, "K1", pairs)
+    spec.ring_storage = args.storage
+    scene = testing.build(spec)
+    vol, cam = scene.volume, scene.camera
+    m = vol.material
+    print(json.dumps({"storage": vol._rings.density_storage, "frame": [W, H], "volume_n": n_vol, "camera": "K1"}), flush=True)
+    lmip_full = None
+    for case, (tf, cutoff) in transfer_functions().items():
+        if args.case not in ("all", case):
+            continue
+        if case == "a":
+            # the instrumented march in full LMIP mode (threshold +inf: no sample is significant) visits every sample
+            m.render_mode, threshold = "lmip", m.lmip_threshold
+            m.lmip_threshold = float("inf")
+            lmip_full = int(vol.render(cam, W, H, count_steps=True).steps.to(torch.int64).sum())
+            m.lmip_threshold = threshold
+        m.render_mode, m.transfer_function, m.alpha_cutoff, m.color_by_label = "composite", tf, cutoff, False
+        res = vol.render(cam, W, H, count_steps=True)
+        samples = int(res.steps.to(torch.int64).sum())
+        hits = int((res.flags == N.SVR_PIX_HIT).sum())
+        handle = vol.prepare()
+        vol._push_transfer_function()
+        cb, fb = vol.camera_block(cam), vol.frame_block(W, H, None)
+        cp = N.CompositeParams(cutoff, 0)
+        ob = N.Outputs()
+        ob.rgba, ob.depth, ob.label, ob.flags = (getattr(res, k).data_ptr() for k in ("rgba", "depth", "label", "flags"))
+        ob.steps, ob.pick, ob.pick_id = None, None, vol.id
+        argv = (handle, C.byref(cb), C.byref(fb), C.byref(cp), C.byref(ob), C.c_void_p(stream.cuda_stream))
+
+        def calls(k=args.calls):
+            for _ in range(k):
+                N.check(lib.svr_composite(*argv), "svr_composite")
+
+        calls(5)
+        call_s = [window(calls) / args.calls for _ in range(args.boxes)]
+        hold = int(max(4.0 * max(call_s) * args.calls, 0.02) / per_cycle)
+        gpu_s = [window(calls, hold) / args.calls for _ in range(args.boxes)]
+        torch.cuda.synchronize()
+        gpu = float(np.median(gpu_s))
+        row = {"case": case, "storage": vol._rings.density_storage, "table_entries": tf.size, "alpha_cutoff": cutoff,
+               "call_ms": round(float(np.median(call_s)) * 1e3, 4), "gpu_ms": round(gpu * 1e3, 4),
+               "calls_per_box": args.calls, "samples": samples, "samples_per_s": float(f"{samples / gpu:.4g}"),
+               "hit_pixels": hits}
+        if case == "a":
+            row["lmip_full_samples"] = lmip_full
+        print(json.dumps(row), flush=True)
+    vol.close()
+
+
+if __name__ == "__main__":
+    main()
