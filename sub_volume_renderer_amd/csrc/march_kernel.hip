@@ -544,15 +544,30 @@ __device__ __forceinline__ uint32_t twin_offset_packed(uint32_t x, uint32_t yz, 
 typedef short short2_t __attribute__((ext_vector_type(2)));
 typedef float float2_t __attribute__((ext_vector_type(2)));
 
+// The per-axis coordinate chain of the fast paths, ic = i32((start + f32(i) * step) * ss), ss = size * scale
+// (scale = 2^-k, see the caller).  SC (scaled ray): the caller has multiplied start and step by ss, an exact power of
+// two >= 1 (MarchParams::ss_pow2), and the chain is start' + f32(i) * step' — the same bits in two IEEE ops instead of
+// three ("Scaled ray"); ss is then not read.
+template <bool SC>
+__device__ __forceinline__ float2_t coord_pair(float2_t iter, float s, float t, float ss) {
+    if constexpr (SC) return iter * t + s;                       // -ffp-contract=off: mul, add
+    else return (iter * t + s) * ss;                             // mul, add, mul
+}
+template <bool SC>
+__device__ __forceinline__ float coord_one(float iter, float s, float t, float ss) {
+    if constexpr (SC) return iter * t + s;
+    else return (iter * t + s) * ss;
+}
+
 // Voxel indices of TWO consecutive samples (iterations it, it+1) of one ray, with packed f32 math
-// (v_pk_mul_f32 / v_pk_add_f32 are IEEE-exact per component, no fusing): per axis
-//   ic = i32((start + f32(i) * step) * ss),   ss = size * scale (scale = 2^-k, see the caller)
+// (v_pk_mul_f32 / v_pk_add_f32 are IEEE-exact per component, no fusing): coord_pair per axis
 struct Idx2 { uint32_t x0, y0, z0, x1, y1, z1; };
+template <bool SC>
 __device__ __forceinline__ Idx2 voxel_pair(float sx, float sy, float sz, float tx, float ty, float tz, float2_t iter,
                                            float ssx, float ssy, float ssz) {
-    const float2_t cx = (iter * tx + sx) * ssx;                  // -ffp-contract=off: mul, add, mul
-    const float2_t cy = (iter * ty + sy) * ssy;
-    const float2_t cz = (iter * tz + sz) * ssz;
+    const float2_t cx = coord_pair<SC>(iter, sx, tx, ssx);
+    const float2_t cy = coord_pair<SC>(iter, sy, ty, ssy);
+    const float2_t cz = coord_pair<SC>(iter, sz, tz, ssz);
     Idx2 r;
     r.x0 = (uint32_t)(int)cx.x; r.x1 = (uint32_t)(int)cx.y;
     r.y0 = (uint32_t)(int)cy.x; r.y1 = (uint32_t)(int)cy.y;
@@ -564,11 +579,12 @@ __device__ __forceinline__ Idx2 voxel_pair(float sx, float sy, float sz, float t
 // the upper half of the register directly): operand of the v_dot2_u32_u16 brick address below.
 // Indices are < 2^15 here (checked by the caller through the packed-i16 box reduction).
 struct Idx2p { uint32_t x0, yz0, x1, yz1; };
+template <bool SC>
 __device__ __forceinline__ Idx2p voxel_pair_packed(float sx, float sy, float sz, float tx, float ty, float tz, float2_t iter,
                                                    float ssx, float ssy, float ssz) {
-    const float2_t cx = (iter * tx + sx) * ssx;
-    const float2_t cy = (iter * ty + sy) * ssy;
-    const float2_t cz = (iter * tz + sz) * ssz;
+    const float2_t cx = coord_pair<SC>(iter, sx, tx, ssx);
+    const float2_t cy = coord_pair<SC>(iter, sy, ty, ssy);
+    const float2_t cz = coord_pair<SC>(iter, sz, tz, ssz);
     Idx2p r;
     r.x0 = (uint32_t)(int)cx.x; r.x1 = (uint32_t)(int)cx.y;
     r.yz0 = (uint32_t)(int)cy.x; r.yz1 = (uint32_t)(int)cy.y;
@@ -673,8 +689,14 @@ struct LodEvents {
 
 // LDS bricks: one private region of MarchParams::brick_bytes per wave (dynamic LDS, see launch_nl)
 
-template <int NL, int U, bool COUNT, int ESH, bool BIG, bool WAVG = false>
-__global__ __launch_bounds__(256) void march_span(const MarchParams P) {
+// SCALED (host: MarchParams::ss_pow2, every LOD's size * scale an exact power of two >= 1; not with WAVG, whose batch
+// reducer reads the step, nor with BIG: launch_nl): a run on one LOD keeps the ray multiplied by that LOD's size * scale ("Scaled ray")
+// (SCALED: 5 waves per SIMD, the occupancy of the other production instantiations, is asked for explicitly — left to
+// itself the scheduler of the shorter chain settles at 99 VGPRs and 4 waves.  1 is the default of a 256-lane block: the
+// other instantiations come out as before, and the instrumented one, at 4 waves anyway, keeps them without scratch)
+template <int NL, int U, bool COUNT, int ESH, bool BIG, bool WAVG = false, bool SCALED = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !COUNT ? 5 : 1))) void march_span(const MarchParams P) {
+    static_assert(!(SCALED && WAVG), "the weighted-average reducer reads the unscaled step");
     // dynamic LDS: kBrickBytes per wave of the block (u8 rings), see launch_nl
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_all[];
     const int nblocks = P.tiles_x * P.tiles_y;
@@ -725,8 +747,9 @@ __global__ __launch_bounds__(256) void march_span(const MarchParams P) {
     Rs.nsteps = 0; Rs.start = { 0.f, 0.f, 0.f }; Rs.step = { 0.f, 0.f, 0.f };
     const bool frag = inside && (x < P.frame.frame_w && y < P.frame.frame_h) && setup_ray(P, x, y, Rs);
     const int nsteps = frag ? Rs.nsteps : 0;
-    const float Rsx = frag ? Rs.start.x : 0.f, Rsy = frag ? Rs.start.y : 0.f, Rsz = frag ? Rs.start.z : 0.f;
-    const float Rtx = frag ? Rs.step.x : 0.f, Rty = frag ? Rs.step.y : 0.f, Rtz = frag ? Rs.step.z : 0.f;
+    // (SCALED: multiplied by size * scale of the LOD for the length of a fast run, and back — exactly — after it)
+    float Rsx = frag ? Rs.start.x : 0.f, Rsy = frag ? Rs.start.y : 0.f, Rsz = frag ? Rs.start.z : 0.f;
+    float Rtx = frag ? Rs.step.x : 0.f, Rty = frag ? Rs.step.y : 0.f, Rtz = frag ? Rs.step.z : 0.f;
 
     // ---- exact per-LOD event iterations
     // ic is monotone along the ray, so its values at the first and last sample bound every other
@@ -1055,6 +1078,9 @@ __global__ __launch_bounds__(256) void march_span(const MarchParams P) {
             // scale is 2^-k here, so (coord*size)*scale == coord*(size*scale) bit for bit (scaling by a
             // power of two commutes with rounding): one multiply per axis instead of two
             const float ssx = L.ss[0], ssy = L.ss[1], ssz = L.ss[2];      // size * scale, multiplied on the host
+            // SCALED: ss = 2^m with m >= 0, so start * ss and step * ss are exact, and the chain start' + f32(i) * step'
+            // gives the bits of (start + f32(i) * step) * ss ("Scaled ray"); undone after the run
+            if constexpr (SCALED) { Rsx *= ssx; Rsy *= ssy; Rsz *= ssz; Rtx *= ssx; Rty *= ssy; Rtz *= ssz; }
             // the buffer resource this LOD's texels come through (hardware range check returns 0 beyond it)
             __amdgpu_buffer_rsrc_t rsrc = rsrc_all;
             if constexpr (BIG) rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(L.rbase), 0, (int)L.rbytes, 0x00020000);
@@ -1083,7 +1109,8 @@ __global__ __launch_bounds__(256) void march_span(const MarchParams P) {
                 if (sb > 0 && run >= 4 * sb) {
                     const float reach = (float)(8 * sb);
                     const uint32_t cs = (uint32_t)Ps->lod[first].cshift;
-                    const bool slow = fmaxf(fmaxf(fabsf(Rtx * ssx), fabsf(Rty * ssy)), fabsf(Rtz * ssz)) * reach <=
+                    const float vx = SCALED ? Rtx : Rtx * ssx, vy = SCALED ? Rty : Rty * ssy, vz = SCALED ? Rtz : Rtz * ssz;
+                    const bool slow = fmaxf(fmaxf(fabsf(vx), fabsf(vy)), fabsf(vz)) * reach <=
                                       (float)(1u << cs) - 0.5f;
                     __amdgpu_buffer_rsrc_t crsrc = __builtin_amdgcn_make_buffer_rsrc(
                         const_cast<void*>(Ps->cells_all), 0, (int)Ps->cells_all_bytes, 0x00020000);
@@ -1095,9 +1122,9 @@ __global__ __launch_bounds__(256) void march_span(const MarchParams P) {
                     uint32_t c0x, c0y, c0z;
                     {
                         const float i0 = fminf((float)n, (float)(nsteps - 1));
-                        c0x = ((uint32_t)(int)((i0 * Rtx + Rsx) * ssx) + (uint32_t)L.addw[0]) >> cs;
-                        c0y = ((uint32_t)(int)((i0 * Rty + Rsy) * ssy) + (uint32_t)L.addw[1]) >> cs;
-                        c0z = ((uint32_t)(int)((i0 * Rtz + Rsz) * ssz) + (uint32_t)L.addw[2]) >> cs;
+                        c0x = ((uint32_t)(int)coord_one<SCALED>(i0, Rsx, Rtx, ssx) + (uint32_t)L.addw[0]) >> cs;
+                        c0y = ((uint32_t)(int)coord_one<SCALED>(i0, Rsy, Rty, ssy) + (uint32_t)L.addw[1]) >> cs;
+                        c0z = ((uint32_t)(int)coord_one<SCALED>(i0, Rsz, Rtz, ssz) + (uint32_t)L.addw[2]) >> cs;
                     }
                     while (run >= 4 * sb) {
                         const bool live = alive && !finished && n < nsteps;
@@ -1113,7 +1140,7 @@ __global__ __launch_bounds__(256) void march_span(const MarchParams P) {
                         for (int g = 1; g < 5; g += 2) {
                             const float i0 = (float)n + reach * (float)g;
                             const float2_t iter = { fminf(i0, lastf), fminf(i0 + reach, lastf) };
-                            const Idx2 q = voxel_pair(Rsx, Rsy, Rsz, Rtx, Rty, Rtz, iter, ssx, ssy, ssz);
+                            const Idx2 q = voxel_pair<SCALED>(Rsx, Rsy, Rsz, Rtx, Rty, Rtz, iter, ssx, ssy, ssz);
                             px[g] = (q.x0 + (uint32_t)L.addw[0]) >> cs; py[g] = (q.y0 + (uint32_t)L.addw[1]) >> cs; pz[g] = (q.z0 + (uint32_t)L.addw[2]) >> cs;
                             px[g + 1] = (q.x1 + (uint32_t)L.addw[0]) >> cs; py[g + 1] = (q.y1 + (uint32_t)L.addw[1]) >> cs;
                             pz[g + 1] = (q.z1 + (uint32_t)L.addw[2]) >> cs;
@@ -1170,9 +1197,9 @@ __global__ __launch_bounds__(256) void march_span(const MarchParams P) {
                     const bool live = alive && !finished && n < nsteps;
                     // first and last existing sample of the slab, both at once with the packed chain
                     const float2_t it = { (float)n, (float)min(n + slab - 1, nsteps - 1) };
-                    const float2_t ex = (it * Rtx + Rsx) * ssx;
-                    const float2_t ey = (it * Rty + Rsy) * ssy;
-                    const float2_t ez = (it * Rtz + Rsz) * ssz;
+                    const float2_t ex = coord_pair<SCALED>(it, Rsx, Rtx, ssx);
+                    const float2_t ey = coord_pair<SCALED>(it, Rsy, Rty, ssy);
+                    const float2_t ez = coord_pair<SCALED>(it, Rsz, Rtz, ssz);
                     // exact box of the wave's samples: min / max per axis over the live lanes
                     const int big = 0x7fffffff;
                     int lx = live ? min((int)ex.x, (int)ex.y) : big, hx = live ? max((int)ex.x, (int)ex.y) : -big;
@@ -1260,7 +1287,7 @@ __global__ __launch_bounds__(256) void march_span(const MarchParams P) {
                         float2_t iter = { (float)n, (float)n + 1.0f };
 #pragma unroll
                         for (int u = 0; u < U; u += 2) {
-                            const Idx2p v = voxel_pair_packed(Rsx, Rsy, Rsz, Rtx, Rty, Rtz, iter, ssx, ssy, ssz);
+                            const Idx2p v = voxel_pair_packed<SCALED>(Rsx, Rsy, Rsz, Rtx, Rty, Rtz, iter, ssx, ssy, ssz);
                             iter += 2.0f;
                             const uint32_t a0 = dot2_u16(v.yz0, kyz, shl_add_c<ESH>(v.x0, bk));
                             const uint32_t a1 = dot2_u16(v.yz1, kyz, shl_add_c<ESH>(v.x1, bk));
@@ -1306,7 +1333,7 @@ __global__ __launch_bounds__(256) void march_span(const MarchParams P) {
                     const uint32_t KbS = Kb << 7;
 #pragma unroll
                     for (int u = 0; u < U; u += 2) {
-                        const Idx2p v = voxel_pair_packed(Rsx, Rsy, Rsz, Rtx, Rty, Rtz, iter, ssx, ssy, ssz);
+                        const Idx2p v = voxel_pair_packed<SCALED>(Rsx, Rsy, Rsz, Rtx, Rty, Rtz, iter, ssx, ssy, ssz);
                         iter += 2.0f;
                         off[u] = twin_offset_packed<ESH>(v.x0, v.yz0, tc, KbS);
                         off[u + 1] = twin_offset_packed<ESH>(v.x1, v.yz1, tc, KbS);
@@ -1314,7 +1341,7 @@ __global__ __launch_bounds__(256) void march_span(const MarchParams P) {
                 } else {
 #pragma unroll
                 for (int u = 0; u < U; u += 2) {
-                    const Idx2 v = voxel_pair(Rsx, Rsy, Rsz, Rtx, Rty, Rtz, iter, ssx, ssy, ssz);
+                    const Idx2 v = voxel_pair<SCALED>(Rsx, Rsy, Rsz, Rtx, Rty, Rtz, iter, ssx, ssy, ssz);
                     iter += 2.0f;
                     off[u] = mad24(mad24(v.z0, L.ring[1], v.y0), L.rx4, shl_add_c<ESH>(v.x0, Kc));
                     off[u + 1] = mad24(mad24(v.z1, L.ring[1], v.y1), L.rx4, shl_add_c<ESH>(v.x1, Kc));
@@ -1334,7 +1361,7 @@ __global__ __launch_bounds__(256) void march_span(const MarchParams P) {
                         return q;
                     };
                     const float2_t ends = { (float)n, (float)min(n + U - 1, nsteps - 1) };     // (samples beyond the ray's end are never looked at)
-                    const float2_t ez2 = (ends * Rtz + Rsz) * ssz;
+                    const float2_t ez2 = coord_pair<SCALED>(ends, Rsz, Rtz, ssz);
                     const uint32_t pa = part_of((int)ez2.x), pb = part_of((int)ez2.y);
                     const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)pa, (int)__builtin_ctzll(__builtin_amdgcn_ballot_w64(live)));
                     if (__builtin_amdgcn_ballot_w64(live && (pa != p0 || pb != p0)) == 0) {
@@ -1346,7 +1373,7 @@ __global__ __launch_bounds__(256) void march_span(const MarchParams P) {
                     float2_t it2 = { (float)n, (float)n + 1.0f };
 #pragma unroll
                     for (int u = 0; u < U; u += 2) {
-                        const float2_t cz = (it2 * Rtz + Rsz) * ssz;      // the z index of the pair again (this path is rare)
+                        const float2_t cz = coord_pair<SCALED>(it2, Rsz, Rtz, ssz);      // the z index of the pair again (this path is rare)
                         it2 += 2.0f;
 #pragma unroll
                         for (int h = 0; h < 2; ++h) {
@@ -1385,6 +1412,12 @@ __global__ __launch_bounds__(256) void march_span(const MarchParams P) {
                 direct_batches(std::false_type{});
             }
             } while (held > 0 && __builtin_amdgcn_ballot_w64(alive && !finished && n < nsteps) != 0);
+            if constexpr (SCALED) {
+                // back to the ray of the reference (1 / ss = 2^-m, read from the host: the product is the original value)
+                const kparams_t Pu = fresh_params(P);
+                const float ux = Pu->lod[first].rss[0], uy = Pu->lod[first].rss[1], uz = Pu->lod[first].rss[2];
+                Rsx *= ux; Rsy *= uy; Rsz *= uz; Rtx *= ux; Rty *= uy; Rtz *= uz;
+            }
             lap(6);
         }
     }
@@ -1438,15 +1471,22 @@ hipError_t launch_nl(const MarchParams& p, int kind, hipStream_t stream) {
     } else {
         const int threads = 64 << (2 * p.block_waves_log2);
         const size_t lds = (size_t)p.brick_bytes * (threads / 64);
-#define SVR_LAUNCH_SPAN(ESH_)                                                                                              \
-    do {                                                                                                                   \
-        if (p.per_lod_rsrc) {                                                                                              \
+#define SVR_LAUNCH_SPAN_SC(ESH_, SC_)                                                                                              \
+    do {                                                                                                                           \
+        if (p.per_lod_rsrc) {                                                                                                      \
             if (p.steps) hipLaunchKernelGGL((march_span<NL, 8, true, ESH_, true>), dim3(nblocks), dim3(threads), lds, stream, p);   \
             else         hipLaunchKernelGGL((march_span<NL, 8, false, ESH_, true>), dim3(nblocks), dim3(threads), lds, stream, p);  \
-        } else {                                                                                                           \
-            if (p.steps) hipLaunchKernelGGL((march_span<NL, 8, true, ESH_, false>), dim3(nblocks), dim3(threads), lds, stream, p);  \
-            else         hipLaunchKernelGGL((march_span<NL, 8, false, ESH_, false>), dim3(nblocks), dim3(threads), lds, stream, p); \
-        }                                                                                                                  \
+        } else {                                                                                                                   \
+            if (p.steps) hipLaunchKernelGGL((march_span<NL, 8, true, ESH_, false, false, SC_>), dim3(nblocks), dim3(threads), lds, stream, p);  \
+            else         hipLaunchKernelGGL((march_span<NL, 8, false, ESH_, false, false, SC_>), dim3(nblocks), dim3(threads), lds, stream, p); \
+        }                                                                                                                          \
+    } while (0)
+    // (the scaled-ray kernels where every LOD's size * scale is a power of two >= 1; the others are those of before.  Not for
+    // rings of 4 GiB or more: at 5 waves per SIMD their scaled instantiations spill VGPRs to scratch)
+#define SVR_LAUNCH_SPAN(ESH_)                                                                                              \
+    do {                                                                                                                   \
+        if (p.ss_pow2 && !p.per_lod_rsrc) SVR_LAUNCH_SPAN_SC(ESH_, true);                                                  \
+        else           SVR_LAUNCH_SPAN_SC(ESH_, false);                                                                    \
     } while (0)
 #define SVR_LAUNCH_WAVG(ESH_)                                                                                              \
     do {                                                                                                                   \
@@ -1463,6 +1503,7 @@ hipError_t launch_nl(const MarchParams& p, int kind, hipStream_t stream) {
         else SVR_LAUNCH_SPAN(2);
 #undef SVR_LAUNCH_WAVG
 #undef SVR_LAUNCH_SPAN
+#undef SVR_LAUNCH_SPAN_SC
     }
     return hipGetLastError();
 }

@@ -13,6 +13,7 @@
 
 #include "svr_internal.h"
 #include "ring_parts.h"
+#include "march_pow2.h"
 
 static thread_local std::string g_err;
 void svr_set_error(const std::string& msg) { g_err = msg; }
@@ -1057,6 +1058,7 @@ static int fill_params(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, c
         Q.rx4 = Q.ring[0] * des;
         Q.base_bytes = (uint32_t)(c->lod_base_bytes[l] * des);
         for (int a = 0; a < 3; ++a) Q.ss[a] = P.size[a] * Q.scale[a];          // one IEEE multiply, as the kernel did
+        for (int a = 0; a < 3; ++a) Q.rss[a] = 1.0f / Q.ss[a];
         {   // brick slabs (u8 rings): about 12 ring voxels of travel per slab (coarser LODs advance less per
             // iteration); rows in 16-byte groups, indices below 2^15 for the packed (y, z) brick address
             const float smax = fmaxf(Q.scale[0], fmaxf(Q.scale[1], Q.scale[2]));
@@ -1080,6 +1082,9 @@ static int fill_params(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, c
             }
         }
     }
+    P.ss_pow2 = 1;
+    for (int l = 0; l < c->num_lods; ++l)
+        for (int a = 0; a < 3; ++a) P.ss_pow2 = P.ss_pow2 && svr_ss_pow2(P.lod[l].ss[a]);
     // skip only when some texel value can reach the threshold and not every one does: threshold = +inf (or NaN)
     // is the "full" march, whose point is the traversal itself; variant bit 3 switches skipping off (A/B)
     // A state machine that can never stop (no fall-off, no sample limit: MIP, _material.py lmip_uniforms) is the running

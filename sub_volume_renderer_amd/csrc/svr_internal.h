@@ -44,6 +44,7 @@ struct LodParams {
     int32_t  addw[3];          // wrap0 - off: ring slot = wrap(ic + addw)
     uint32_t rx4;              // row pitch of the density ring in bytes (ring[0] * element size)
     float    ss[3];            // size * scale (the fused per-axis factor of the fast paths when scale = 2^-k)
+    float    rss[3];           // 1 / ss, exact where MarchParams::ss_pow2 is set (the scaled ray is multiplied back by it)
     int32_t  slab;             // brick slab length in iterations (0: this LOD never stages bricks)
     // empty-space skipping: the 2x2x2-block maxima of this LOD's macro cells inside MarchParams::cells_all
     // the buffer resource this LOD's texels are fetched through: the one allocation of all LODs' rings while it is
@@ -128,6 +129,8 @@ struct MarchParams {
     float   xdir[4];               // clip-space image of the data-space direction (1,0,0,0)
     int32_t lod_pow2[SVR_MAX_LODS];// 1: all three scale factors of the LOD are powers of two and the
                                    //    voxel indices fit the 24-bit multiplier (fast path eligible)
+    int32_t ss_pow2;               // 1: every LOD's ss is an exact power of two >= 1 (march_pow2.h): the march runs its
+                                   //    scaled-ray instantiation (fast runs keep start and step multiplied by ss)
     LodParams lod[SVR_MAX_LODS];
 };
 
