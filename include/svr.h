@@ -501,6 +501,79 @@ typedef struct svr_composite_params {
 int  svr_composite(svr_ctx* ctx, const svr_camera* cam, const svr_frame* frame, const svr_composite_params* params,
                    const svr_outputs* out, void* stream);
 
+/* ---- iso-surface render mode: the first point along each of the march's rays where the density reaches a level,
+ * shaded from the local gradient (pygfx's VolumeIsoMaterial; no counterpart in the reference; FUTURE.md's "swappable
+ * rendering pipeline").  An addition within ABI version 9: new symbols only; svr_material, svr_outputs, svr_camera,
+ * svr_frame and svr_render keep their layout and behaviour.  Defined HERE (numpy restatement: tests/iso_twin.py), in
+ * f32, in this order, with no fused operations; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.  Per pixel:
+ *   ray      the march's, exactly as svr_composite takes it: pixel -> frame through svr_frame, the DISCARD rules, the
+ *            clipping planes (ANY / ALL), start, step and nsteps (orthographic cameras included).
+ *   S(iter)  the sample at the float counter iter: coord = start + iter * step, d = coord * size (per component); the
+ *            first LOD l whose ROI holds (int)(d * scale_l) gives the value s (the ring's element converted to f32: u8
+ *            and u16 exactly, unnormalised like lmip_threshold) and the label (0 without label rings).  A point that
+ *            no LOD holds has no value and cannot hit.
+ *   coarse   i = 0 .. nsteps-1 in order, iter = (float)i; the candidate is the first i with s >= iso_value.
+ *   refine   none when i == 0 or refine <= 1: the hit is at iter = (float)i.  Else k = 1 .. refine-1 in order,
+ *            iter = (float)(i-1) + (float)k / (float)refine; the first with s >= iso_value is the hit, else iter =
+ *            (float)i.  A linear search: sampling is nearest-texel, the field along a ray is a step function and a
+ *            bisection may miss the first crossing.
+ *   gradient at the hit (coordinate c, data point d = c * size, LOD l that gave its value), central differences of one
+ *            voxel of that LOD per axis: h_a = 1.0f / scale_l[a];  D(p) = the value the LOD cascade gives for the data
+ *            point p (computed like d above from p directly), 0 where no LOD holds it;
+ *              g_x = (D(d.x + h_x, d.y, d.z) - D(d.x - h_x, d.y, d.z)) * scale_l[x]      (y, z alike)
+ *            to world space with the inverse-transpose of world (m = cam->world_inv, column-major):
+ *              G_x = (m[0]*g_x + m[1]*g_y) + m[2]*g_z;  G_y = (m[4]*g_x + m[5]*g_y) + m[6]*g_z;  G_z = (m[8].. m[10])
+ *              len = sqrtf(dot(G, G));  n = (-G_x / len, -G_y / len, -G_z / len)   (towards falling density)
+ *            A len that is 0 or not finite gives n = v (below).
+ *   view     sd = step * size (per component);  w = world's upper 3 x 3 times sd:
+ *              w_x = (world[0]*sd_x + world[4]*sd_y) + world[8]*sd_z  (w_y from world[1], [5], [9]; w_z from [2], [6], [10])
+ *              vl = sqrtf(dot(w, w));  v = (-w_x / vl, -w_y / vl, -w_z / vl)   (towards the viewer along the pixel's ray)
+ *            A vl that is 0 or not finite gives v = (0, 0, 0).
+ *   light    l = v (a headlight) when headlight != 0, else light_direction (world space, from the surface towards the
+ *            light).  hv = l + v per component;  hl = sqrtf(dot(hv, hv));  h = hv / hl, or (0,0,0) when hl is 0 or
+ *            not finite.
+ *   shading  two-sided Blinn-Phong in linear light:
+ *              ndl = fabsf(dot(n, l));  sp = fabsf(dot(n, h));  repeat shininess_log2 times: sp = sp * sp
+ *              t = ambient + diffuse * ndl
+ *              rgb_c = fminf(fmaxf(base_c * t + specular * sp, 0.0f), 1.0f)
+ *            base = iso_color, or with color_by_label hsv_to_rgb(h, s, 1.0f) of colors[label % color_count] (the hue
+ *            conversion of the other modes).  The specular power is repeated squaring, not powf.
+ *   outputs  HIT: rgba = (rgb, opacity); depth = the march's depth formula at c; label = the label S gave at the hit;
+ *              pick = the march's packing of c; normal = n.
+ *            MISS when the ray ran and nothing reached the level: rgba (0,0,0,0) (transparent, like svr_composite),
+ *              depth, label, pick and normal 0.
+ *            DISCARD as in the march (normal 0).
+ *            steps (when not NULL; written by this kernel, no instrumented build): the coarse samples up to and
+ *              including the candidate, i + 1, or nsteps on a MISS; independent of refine and of skipping.
+ * Empty-space skipping: before each stretch of 8 coarse samples the kernel looks the stretch's index box up in the
+ * macro-cell maxima the uploads maintain ("iso_kernel"); a stretch in which no lane of the wave can reach
+ * iso_value is passed without fetching texels.  It never changes an output plane; no_skip switches it off (A/B).
+ * The material's opacity, colors and clipping planes are read; clim, gamma, fog, colorspace_srgb, the lmip_* fields,
+ * render_mode and the transfer function are not.  A render-thread call like svr_render: it waits for published
+ * uploads, later uploads wait for it.  Enqueued on `stream`; asynchronous.  SVR_ERR_INVALID, with nothing enqueued,
+ * when no material has been set, iso_value is NaN, refine is outside 0 .. SVR_ISO_MAX_REFINE, shininess_log2 is
+ * outside 0 .. SVR_ISO_MAX_SHININESS_LOG2, ambient, diffuse, specular or a component of iso_color is negative or not
+ * finite (iso_color: above 1), headlight is 0 and light_direction is not finite or not of unit length (within 1e-3),
+ * or any frame or camera check of svr_render fails. */
+#define SVR_ISO_MAX_REFINE 16
+#define SVR_ISO_MAX_SHININESS_LOG2 10
+typedef struct svr_iso_params {
+    float    iso_value;            /* the level, in the ring's own units (compared like lmip_threshold) */
+    int32_t  refine;               /* 0 .. 16: sub-samples per coarse step searched before the candidate (<= 1: none) */
+    float    iso_color[3];         /* base colour, linear light, each in [0, 1] */
+    int32_t  color_by_label;       /* 1: base colour = the hue of the hit's label */
+    float    ambient, diffuse, specular;   /* each finite and >= 0 */
+    int32_t  shininess_log2;       /* 0 .. 10: the specular exponent is 2^shininess_log2 */
+    int32_t  headlight;            /* != 0: the light sits at the viewer; 0: light_direction */
+    float    light_direction[3];   /* world space, unit length, towards the light (read when headlight == 0) */
+    int32_t  no_skip;              /* != 0: march every stretch (same planes, bit for bit) */
+    float*   normal;               /* device, out_h * out_w * 3 floats, or NULL: the unit world-space normal n */
+    uint32_t* skip_counters;       /* device, 2 words, or NULL: the kernel ADDS the wave-stretches it [0] marched and
+                                      [1] skipped (diagnostics: the share of empty space passed) */
+} svr_iso_params;
+int  svr_iso(svr_ctx* ctx, const svr_camera* cam, const svr_frame* frame, const svr_iso_params* params,
+             const svr_outputs* out, void* stream);
+
 /* ---- sync */
 int  svr_sync(svr_ctx* ctx);                 /* both streams idle */
 int  svr_sync_uploads(svr_ctx* ctx);         /* upload stream idle */

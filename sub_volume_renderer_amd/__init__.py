@@ -13,7 +13,7 @@ from .outline import outline
 from ._material import SubVolumeMaterial
 from ._transfer import TransferFunction
 from ._transform import AffineTransform, OrthographicCamera, PerspectiveCamera
-from ._wobject import FrameRegion, RenderResult, SliceResult, SubVolume
+from ._wobject import FrameRegion, IsoResult, RenderResult, SliceResult, SubVolume
 from ._wrapping_buffer import WrappingBuffer, subtract_rois
 
 __all__ = [
@@ -30,6 +30,7 @@ __all__ = [
     "FrameRegion",
     "RenderResult",
     "SliceResult",
+    "IsoResult",
     "subtract_rois",
     # display-side output of a render (pygfx's job in the reference)
     "compose",

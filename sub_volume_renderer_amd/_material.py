@@ -78,6 +78,14 @@ class SubVolumeMaterial:
         self.transfer_function = None
         self.alpha_cutoff = 0.99
         self.color_by_label = False
+        self.iso_value = 0.5
+        self.iso_color = (0.8, 0.8, 0.8)
+        self.iso_refine = 4
+        self.ambient = 0.2
+        self.diffuse = 0.7
+        self.specular = 0.3
+        self.shininess_log2 = 5
+        self.light_direction = None
         arguments = dict(clim=clim, gamma=gamma, opacity=opacity, lmip_threshold=lmip_threshold,
                          lmip_fall_off=lmip_fall_off, lmip_max_samples=lmip_max_samples, fog_density=fog_density,
                          fog_color=fog_color,
@@ -154,7 +162,7 @@ class SubVolumeMaterial:
         self._store("clipping_mode", mode)
 
     # -- render mode: the swappable raycast the reference wishes for (FUTURE.md:97-120) -------------------------
-    RENDER_MODES = ("lmip", "mip", "weighted_average", "composite")
+    RENDER_MODES = ("lmip", "mip", "weighted_average", "composite", "iso")
 
     @property
     def render_mode(self) -> str:
@@ -171,7 +179,13 @@ class SubVolumeMaterial:
 
         "composite": direct volume rendering — front-to-back emission-absorption compositing of every sample's colour
         and opacity from ``transfer_function`` until the ray's opacity reaches ``alpha_cutoff`` (``svr_composite`` in
-        ``include/svr.h``).  Hit pixels carry straight alpha; rays that gather no opacity are transparent misses."""
+        ``include/svr.h``).  Hit pixels carry straight alpha; rays that gather no opacity are transparent misses.
+
+        "iso": the iso-surface — the first point along each ray where the density reaches ``iso_value`` (searched
+        with ``iso_refine`` sub-samples per step), lit from the local gradient by two-sided Blinn-Phong (``ambient``,
+        ``diffuse``, ``specular``, ``shininess_log2``, ``light_direction``) over ``iso_color`` or, with
+        ``color_by_label``, the hit label's hue (``svr_iso`` in ``include/svr.h``).  Rays that never reach the level
+        are transparent misses."""
         return self._u["render_mode"]
 
     @render_mode.setter
@@ -238,6 +252,118 @@ class SubVolumeMaterial:
     @color_by_label.setter
     def color_by_label(self, value) -> None:
         self._store("color_by_label", bool(value))
+
+    # -- iso mode (svr_iso) ----------------------------------------------------------------------------------
+    @staticmethod
+    def _real(name, value):
+        if isinstance(value, (str, bytes, bool)) or not isinstance(value, numbers.Real):
+            raise ValueError(f"{name} must be a number, not {value!r}")
+        with np.errstate(over="ignore"):
+            return np.float32(float(value))
+
+    @staticmethod
+    def _integer(name, value, lo, hi):
+        if isinstance(value, bool) or not isinstance(value, numbers.Integral) or not lo <= int(value) <= hi:
+            raise ValueError(f"{name} must be an integer in {lo} .. {hi}, not {value!r}")
+        return np.int32(int(value))
+
+    @property
+    def iso_value(self) -> float:
+        """"iso" mode: the level, in the units of the data (compared with the sampled value like ``lmip_threshold``:
+        0 .. 255 for uint8 volumes).  +-inf is allowed (nothing / everything reaches it), NaN is not."""
+        return float(self._u["iso_value"])
+
+    @iso_value.setter
+    def iso_value(self, value) -> None:
+        v = self._real("iso_value", value)
+        if np.isnan(v):
+            raise ValueError("iso_value must not be NaN")
+        self._store("iso_value", v)
+
+    @property
+    def iso_color(self) -> tuple[float, float, float]:
+        """"iso" mode: the surface's base colour, linear-light RGB, each component in [0, 1]."""
+        return tuple(float(c) for c in self._u["iso_color"])
+
+    @iso_color.setter
+    def iso_color(self, rgb) -> None:
+        if isinstance(rgb, (str, bytes)) or not isinstance(rgb, (tuple, list, np.ndarray)) or len(rgb) != 3:
+            raise ValueError(f"iso_color must be three numbers in [0, 1], not {rgb!r}")
+        vals = np.array([self._real("iso_color", c) for c in rgb], np.float32)
+        if not np.all((vals >= 0.0) & (vals <= 1.0)):
+            raise ValueError(f"iso_color must be three numbers in [0, 1], not {rgb!r}")
+        self._store("iso_color", vals)
+
+    @property
+    def iso_refine(self) -> int:
+        """"iso" mode: sub-samples per step searched, in order, between the last sample below the level and the first
+        one at it (0 or 1: none; at most 16)."""
+        return int(self._u["iso_refine"])
+
+    @iso_refine.setter
+    def iso_refine(self, value) -> None:
+        self._store("iso_refine", self._integer("iso_refine", value, 0, 16))
+
+    def _shading_coefficient(self, name, value):
+        v = self._real(name, value)
+        if not (0.0 <= v < np.inf):
+            raise ValueError(f"{name} must be finite (as float32) and >= 0, not {value!r}")
+        self._store(name, v)
+
+    @property
+    def ambient(self) -> float:
+        """"iso" mode: the share of the base colour shown regardless of the light."""
+        return float(self._u["ambient"])
+
+    @ambient.setter
+    def ambient(self, value) -> None:
+        self._shading_coefficient("ambient", value)
+
+    @property
+    def diffuse(self) -> float:
+        """"iso" mode: the weight of the Lambert term ``|n . l|``."""
+        return float(self._u["diffuse"])
+
+    @diffuse.setter
+    def diffuse(self, value) -> None:
+        self._shading_coefficient("diffuse", value)
+
+    @property
+    def specular(self) -> float:
+        """"iso" mode: the weight of the (white) Blinn-Phong highlight ``|n . h| ** (2 ** shininess_log2)``."""
+        return float(self._u["specular"])
+
+    @specular.setter
+    def specular(self, value) -> None:
+        self._shading_coefficient("specular", value)
+
+    @property
+    def shininess_log2(self) -> int:
+        """"iso" mode: log2 of the specular exponent, 0 .. 10 (the kernel squares that many times)."""
+        return int(self._u["shininess_log2"])
+
+    @shininess_log2.setter
+    def shininess_log2(self, value) -> None:
+        self._store("shininess_log2", self._integer("shininess_log2", value, 0, 10))
+
+    @property
+    def light_direction(self):
+        """"iso" mode: the world-space direction from the surface towards the light, or None (the default): a
+        headlight at the viewer.  Any non-zero finite vector; stored normalised."""
+        d = self._u["light_direction"]
+        return None if d is None else tuple(float(c) for c in d)
+
+    @light_direction.setter
+    def light_direction(self, direction) -> None:
+        if direction is None:
+            return self._store("light_direction", None)
+        if isinstance(direction, (str, bytes)) or not isinstance(direction, (tuple, list, np.ndarray)) or len(direction) != 3:
+            raise ValueError(f"light_direction must be None or three numbers, not {direction!r}")
+        d = np.array([float(self._real("light_direction", c)) for c in direction], np.float64)
+        length = float(np.sqrt((d * d).sum()))
+        if not np.all(np.isfinite(d)) or not (0.0 < length < np.inf):
+            raise ValueError(f"light_direction must be a finite, non-zero vector, not {direction!r}")
+        self._store("light_direction", (d / length).astype(np.float32))
 
     def lmip_uniforms(self) -> tuple[float, float, int]:
         """(threshold, fall_off, max_samples) as the draw sends them for the current render mode."""

@@ -154,6 +154,28 @@ class CompositeParams(C.Structure):
 TF_MAX_ENTRIES = 4096                               # SVR_TF_MAX_ENTRIES
 
 
+class IsoParams(C.Structure):
+    _fields_ = [
+        ("iso_value", C.c_float),
+        ("refine", C.c_int32),
+        ("iso_color", C.c_float * 3),
+        ("color_by_label", C.c_int32),
+        ("ambient", C.c_float),
+        ("diffuse", C.c_float),
+        ("specular", C.c_float),
+        ("shininess_log2", C.c_int32),
+        ("headlight", C.c_int32),
+        ("light_direction", C.c_float * 3),
+        ("no_skip", C.c_int32),
+        ("normal", C.c_void_p),
+        ("skip_counters", C.c_void_p),
+    ]
+
+
+ISO_MAX_REFINE = 16                                 # SVR_ISO_MAX_REFINE
+ISO_MAX_SHININESS_LOG2 = 10                         # SVR_ISO_MAX_SHININESS_LOG2
+
+
 _I3 = C.c_int32 * 3
 _L3 = C.c_int64 * 3
 
@@ -201,6 +223,8 @@ SIGNATURES = {
     "svr_set_transfer_function": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "svr_composite": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Frame), C.POINTER(CompositeParams),
                                 C.POINTER(Outputs), C.c_void_p]),
+    "svr_iso": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Frame), C.POINTER(IsoParams), C.POINTER(Outputs),
+                          C.c_void_p]),
     "svr_sync": (C.c_int, [C.c_void_p]),
     "svr_sync_uploads": (C.c_int, [C.c_void_p]),
     "svr_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),

@@ -66,6 +66,15 @@ class RenderResult:
 
 
 @dataclass
+class IsoResult(RenderResult):
+    """A ``RenderResult`` with the extra planes only the "iso" render mode writes.  Pass one as ``out=`` to
+    ``SubVolume.render`` (``SubVolume.iso_outputs`` allocates it): the other modes leave the extra planes alone."""
+
+    normal: "object | None" = None          # torch f32 [h, w, 3]  unit world-space surface normal, 0 on non-hits
+    skip_counters: "object | None" = None   # torch i32 [2]        wave-stretches marched / skipped, ADDED per render
+
+
+@dataclass
 class SliceResult(RenderResult):
     """Device tensors written by one cross-section (``svr_slice``): the planes of a render (``steps`` and ``pick`` are
     None, depth is 0) plus the density texel each pixel shows and the LOD it came from."""
@@ -185,6 +194,7 @@ class SubVolume(_HasWorld):
         self._volume_dimensions = np.zeros(3, np.float32)
         self.volume_dimensions = base_data.shape
         self._material_version_pushed = -1
+        self.iso_no_skip = False          # "iso" mode: march every stretch (A/B of the empty-space skipping; same frame)
         self._tf_pushed = None            # (TransferFunction, volume_dimensions bytes) of the table on the device
         # pygfx gives every world object a process-wide id (the shader packs its low 20 bits into the pick word)
         SubVolume._next_id = getattr(SubVolume, "_next_id", 0) + 1
@@ -476,6 +486,46 @@ class SubVolume(_HasWorld):
             self._out_cache = {key: res}
         return res
 
+    def iso_outputs(self, width: int, height: int, *, count_steps: bool = False, pick: bool = False,
+                    normal: bool = True, skip_counters: bool = False) -> "IsoResult":
+        """Fresh output tensors for an "iso" render of ``height`` x ``width`` output pixels, with the normal plane
+        and / or the two skip counters (zeroed; every render adds to them), for ``render(..., out=...)``."""
+        import torch
+
+        dev = torch.device("cuda", self._rings.device if self._rings.device is not None else torch.cuda.current_device())
+        h, w = int(height), int(width)
+        return IsoResult(
+            rgba=torch.empty((h, w, 4), dtype=torch.float32, device=dev),
+            depth=torch.empty((h, w), dtype=torch.float32, device=dev),
+            label=torch.empty((h, w), dtype=torch.int32, device=dev),
+            flags=torch.empty((h, w), dtype=torch.uint8, device=dev),
+            steps=torch.empty((h, w), dtype=torch.int32, device=dev) if count_steps else None,
+            pick=torch.empty((h, w), dtype=torch.int64, device=dev) if pick else None,
+            normal=torch.empty((h, w, 3), dtype=torch.float32, device=dev) if normal else None,
+            skip_counters=torch.zeros(2, dtype=torch.int32, device=dev) if skip_counters else None,
+        )
+
+    def _iso_params(self, res) -> "N.IsoParams":
+        """The ``svr_iso_params`` of the material's "iso" settings; ``res``: the outputs (an ``IsoResult``'s extra
+        planes are written)."""
+        m = self.material
+        ip = N.IsoParams()
+        ip.iso_value = m.iso_value
+        ip.refine = m.iso_refine
+        ip.iso_color[:] = m.iso_color
+        ip.color_by_label = 1 if m.color_by_label else 0
+        ip.ambient, ip.diffuse, ip.specular = m.ambient, m.diffuse, m.specular
+        ip.shininess_log2 = m.shininess_log2
+        light = m.light_direction
+        ip.headlight = 1 if light is None else 0
+        ip.light_direction[:] = (0.0, 0.0, 1.0) if light is None else light
+        ip.no_skip = 1 if self.iso_no_skip else 0
+        normal = getattr(res, "normal", None)
+        counters = getattr(res, "skip_counters", None)
+        ip.normal = normal.data_ptr() if normal is not None else None
+        ip.skip_counters = counters.data_ptr() if counters is not None else None
+        return ip
+
     def prepare(self):
         """Push pending uniforms (material, per-LOD ROI/scale) to the device."""
         handle = self._rings.handle  # creates the context on first use
@@ -526,6 +576,12 @@ class SubVolume(_HasWorld):
             cp = N.CompositeParams(self.material.alpha_cutoff, 1 if self.material.color_by_label else 0)
             N.check(N.lib().svr_composite(handle, C.byref(cb), C.byref(fb), C.byref(cp), C.byref(ob), C.c_void_p(stream)),
                     "svr_composite")
+            return res
+        if self.material.render_mode == "iso":
+            # lit iso-surface (svr_iso): same camera block, frame and outputs; its steps plane is written by the
+            # production kernel
+            ip = self._iso_params(res)
+            N.check(N.lib().svr_iso(handle, C.byref(cb), C.byref(fb), C.byref(ip), C.byref(ob), C.c_void_p(stream)), "svr_iso")
             return res
         N.check(
             N.lib().svr_render(handle, C.byref(cb), C.byref(fb), C.byref(ob), C.c_void_p(stream)),

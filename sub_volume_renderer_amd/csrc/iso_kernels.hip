@@ -1,0 +1,546 @@
+// Iso-surface render mode (svr_iso, include/svr.h): the first sample along each of the march's rays whose value reaches
+// iso_value, refined by a linear sub-sample search, shaded (two-sided Blinn-Phong) from the central-difference gradient
+// at the hit.  One lane = one pixel; a workgroup of 256 threads is a 16 x 16 pixel tile of four 8 x 8 wave tiles, placed
+// on the XCDs like composite_kernels.hip's (march_simple's layout and fallback placement).
+//
+// Per wave, coarse samples go in stretches of ISO_UNROLL.  Before a stretch each live lane looks the index box of its
+// ISO_UNROLL samples up in the macro-cell maxima the uploads maintain (ring_kernels.hip: `blk`, the maximum over the
+// 2 x 2 x 2 block of cells starting at a cell); when no live lane of the wave can reach iso_value the wave moves on
+// without a texel fetch.  Otherwise: the LOD and address of every sample of the stretch first, then their gathers (all
+// in flight together), then the serial "first >= iso" pick.  A lane is live until it has a candidate or its ray ends;
+// a wave leaves the loop when no lane is live.  Refinement, gradient and shading run once per wave, after the loop.
+//
+// Arithmetic contract: strict IEEE f32 without contraction (-ffp-contract=off), operation order as written in svr.h.
+// The device helpers below are copies of the march's (march_kernel.hip) as composite_kernels.hip restates them; the
+// march sources are the kernel-source stamp bench.py records and stay untouched.  tests/test_gpu_iso.py holds this
+// kernel to tests/iso_twin.py.
+#include <math.h>
+#include <string.h>
+
+#include "svr_internal.h"
+
+namespace {
+
+struct f3 { float x, y, z; };
+struct f4 { float x, y, z, w; };
+
+struct IsoLod {
+    const void*     density;   // ring [z][y][x], element type per the kernel's ESH
+    const uint32_t* labels;    // null: no label rings
+    const void*     cells;     // `blk` maxima of this LOD's macro cells (element type = the ring's), null: none
+    int32_t  off[3];           // current_logical_offset_in_pixels
+    uint32_t shape[3];         // current_logical_shape_in_pixels
+    uint32_t wrap0[3];         // ring slot of the ROI's first voxel
+    uint32_t ring[3];
+    float    scale[3];
+    uint32_t cdim[3];          // cells per axis
+    int32_t  cshift;           // log2 of the cell size
+};
+
+struct IsoParams {
+    float ndc_to_data[16];     // world_inv * cam_inv * proj_inv, as svr_render forms it
+    float pc[16];              // proj * cam
+    float world[16];
+    float world_inv[16];
+    float size[3];
+    float rel_step;
+    svr_frame frame;
+    float opacity;
+    uint32_t clip_count;
+    int32_t  clip_all;
+    float    clip[SVR_MAX_CLIP_PLANES][4];
+    uint32_t color_count;
+    const float* colors;       // device, color_count x vec4 (h, s, v, pad)
+    float    iso;
+    int32_t  refine;
+    float    base[3];
+    int32_t  tint;
+    float    ambient, diffuse, specular;
+    int32_t  shininess_log2;
+    int32_t  headlight;
+    float    light[3];
+    int32_t  skip;             // 1: test the cell maxima before each stretch
+    int32_t  tiles_x, tiles_y;
+    float*    rgba;
+    float*    depth;
+    uint32_t* label;
+    uint8_t*  flags;
+    uint32_t* steps;
+    unsigned long long* pick; uint32_t pick_id;
+    float*    normal;
+    uint32_t* counters;
+    IsoLod L[SVR_MAX_LODS];
+};
+
+// march_kernel.hip `mat_vec`
+__device__ __forceinline__ f4 mat_vec(const float* m, float x, float y, float z, float w) {
+    f4 r;
+    r.x = ((m[0] * x + m[4] * y) + m[8]  * z) + m[12] * w;
+    r.y = ((m[1] * x + m[5] * y) + m[9]  * z) + m[13] * w;
+    r.z = ((m[2] * x + m[6] * y) + m[10] * z) + m[14] * w;
+    r.w = ((m[3] * x + m[7] * y) + m[11] * z) + m[15] * w;
+    return r;
+}
+
+__device__ __forceinline__ float dot3(f3 a, f3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+
+// march_kernel.hip `wrap`
+__device__ __forceinline__ uint32_t wrap(uint32_t t, uint32_t wrap0, uint32_t ring) {
+    const uint32_t w = t + wrap0;
+    return min(w, w - ring);
+}
+
+// march_kernel.hip `lod_texel` (sample_vol.wgsl:4-25), with a 64-bit element index (a float ring can exceed 4 GiB)
+__device__ __forceinline__ bool lod_index(const IsoLod& L, float dx, float dy, float dz, size_t& idx) {
+    const float sx = dx * L.scale[0], sy = dy * L.scale[1], sz = dz * L.scale[2];
+    const int ix = (int)sx, iy = (int)sy, iz = (int)sz;
+    const uint32_t tx = (uint32_t)(ix - L.off[0]), ty = (uint32_t)(iy - L.off[1]), tz = (uint32_t)(iz - L.off[2]);
+    if (!(tx < L.shape[0] && ty < L.shape[1] && tz < L.shape[2])) return false;
+    const uint32_t wx = wrap(tx, L.wrap0[0], L.ring[0]);
+    const uint32_t wy = wrap(ty, L.wrap0[1], L.ring[1]);
+    const uint32_t wz = wrap(tz, L.wrap0[2], L.ring[2]);
+    idx = ((size_t)wz * L.ring[1] + wy) * (size_t)L.ring[0] + wx;
+    return true;
+}
+
+// march_kernel.hip `pick_field`
+__device__ __forceinline__ uint32_t pick_field(float c) {
+    const float f = c * 16383.0f;
+    uint32_t u = 0u;
+    if (f > 0.0f) u = f >= 4294967296.0f ? 0xFFFFFFFFu : (uint32_t)f;
+    return min(u, 16383u);
+}
+
+// march_kernel.hip `hsv_to_rgb` (hsv_selection.wgsl:7-41)
+__device__ __forceinline__ f3 hsv_to_rgb(float h, float s, float v) {
+    f3 r;
+    if (s == 0.0f) { r.x = v; r.y = v; r.z = v; return r; }
+    const float h_scaled = h * 6.0f;
+    const float fl = floorf(h_scaled);
+    const int sector = (int)fl;
+    const float fr = h_scaled - fl;
+    const float p = v * (1.0f - s);
+    const float q = v * (1.0f - s * fr);
+    const float t = v * (1.0f - s * (1.0f - fr));
+    if (sector == 0)      { r.x = v; r.y = t; r.z = p; }
+    else if (sector == 1) { r.x = q; r.y = v; r.z = p; }
+    else if (sector == 2) { r.x = p; r.y = v; r.z = t; }
+    else if (sector == 3) { r.x = p; r.y = q; r.z = v; }
+    else if (sector == 4) { r.x = t; r.y = p; r.z = v; }
+    else                  { r.x = v; r.y = p; r.z = q; }
+    return r;
+}
+
+struct Ray {
+    f3 start, step;
+    int nsteps;
+};
+
+// march_kernel.hip `setup_ray` (vs_main.wgsl:36-47 + fs_main.wgsl:20-48) for the pixel (i, j) of the full frame.
+// Returns false when no fragment runs for this pixel (discard).
+__device__ __forceinline__ bool setup_ray(const IsoParams& P, int i, int j, Ray& R) {
+    const float W = (float)P.frame.frame_w, H = (float)P.frame.frame_h;
+    const float px = (2.0f * ((float)i + 0.5f)) / W - 1.0f;
+    const float py = 1.0f - (2.0f * ((float)j + 0.5f)) / H;
+    const f4 n4 = mat_vec(P.ndc_to_data, px, py, -1.0f, 1.0f);
+    const f4 f4_ = mat_vec(P.ndc_to_data, px, py, 1.0f, 1.0f);
+    const f3 far_pos  = { f4_.x / f4_.w, f4_.y / f4_.w, f4_.z / f4_.w };
+    const f3 near_pos = { n4.x / n4.w, n4.y / n4.w, n4.z / n4.w };
+    const f3 dir = { far_pos.x - near_pos.x, far_pos.y - near_pos.y, far_pos.z - near_pos.z };
+    const float len = sqrtf(dot3(dir, dir));
+    const f3 ray = { dir.x / len, dir.y / len, dir.z / len };
+
+    const float lo = -0.5f;
+    const float hx = P.size[0] - 0.5f, hy = P.size[1] - 0.5f, hz = P.size[2] - 0.5f;
+    const float tx1 = (lo - near_pos.x) / ray.x, tx2 = (hx - near_pos.x) / ray.x;
+    const float ty1 = (lo - near_pos.y) / ray.y, ty2 = (hy - near_pos.y) / ray.y;
+    const float tz1 = (lo - near_pos.z) / ray.z, tz2 = (hz - near_pos.z) / ray.z;
+    const float t_exit  = fminf(fminf(fmaxf(tx1, tx2), fmaxf(ty1, ty2)), fmaxf(tz1, tz2));
+    const float t_enter = fmaxf(fmaxf(fminf(tx1, tx2), fminf(ty1, ty2)), fminf(tz1, tz2));
+    if (!(t_enter <= t_exit)) return false;
+    const f3 back = { near_pos.x + ray.x * t_exit, near_pos.y + ray.y * t_exit, near_pos.z + ray.z * t_exit };
+    const f4 bw = mat_vec(P.world, back.x, back.y, back.z, 1.0f);
+    const f4 bc = mat_vec(P.pc, bw.x, bw.y, bw.z, bw.w);
+    if (!(bc.w > 0.0f) || !(bc.z >= 0.0f) || !(bc.z <= bc.w)) return false;
+    if (P.clip_count) {
+        const bool all = P.clip_all != 0;
+        bool clipped = all;
+        for (uint32_t k = 0; k < P.clip_count; ++k) {
+            const bool behind = ((bw.x * P.clip[k][0] + bw.y * P.clip[k][1]) + bw.z * P.clip[k][2]) < P.clip[k][3];
+            clipped = all ? (clipped && behind) : (clipped || behind);
+        }
+        if (clipped) return false;
+    }
+
+    const f3 nb = { near_pos.x - back.x, near_pos.y - back.y, near_pos.z - back.z };
+    float dist = dot3(nb, ray);
+    dist = fmaxf(dist, fminf((-0.5f - back.x) / ray.x, (P.size[0] - 0.5f - back.x) / ray.x));
+    dist = fmaxf(dist, fminf((-0.5f - back.y) / ray.y, (P.size[1] - 0.5f - back.y) / ray.y));
+    dist = fmaxf(dist, fminf((-0.5f - back.z) / ray.z, (P.size[2] - 0.5f - back.z) / ray.z));
+    const f3 front = { back.x + ray.x * dist, back.y + ray.y * dist, back.z + ray.z * dist };
+    float nf = -dist / P.rel_step + 0.5f;
+    if (!(nf >= 1.0f)) return false;
+    if (nf > 16777216.0f) nf = 16777216.0f;
+    R.nsteps = (int)nf;
+    const float nstepsf = (float)R.nsteps;
+    R.start = { (front.x + 0.5f) / P.size[0], (front.y + 0.5f) / P.size[1], (front.z + 0.5f) / P.size[2] };
+    R.step = { ((back.x - front.x) / P.size[0]) / nstepsf,
+               ((back.y - front.y) / P.size[1]) / nstepsf,
+               ((back.z - front.z) / P.size[2]) / nstepsf };
+    return true;
+}
+
+// march_kernel.hip `xcd_remap`: workgroups b and b + 8 share an XCD; each XCD gets one contiguous run of tiles
+__device__ __forceinline__ int xcd_remap(int b, int nblocks) {
+    const int per = nblocks >> 3;
+    const int body = per << 3;
+    if (b >= body) return b;
+    return (b & 7) * per + (b >> 3);
+}
+
+// a texel at a byte address known to be in global memory (slice_kernels.hip `load_global`)
+template <int ESH>
+__device__ __forceinline__ float load_global(const char* a) {
+    typedef __attribute__((address_space(1))) const uint8_t G8;
+    typedef __attribute__((address_space(1))) const uint16_t G16;
+    typedef __attribute__((address_space(1))) const float G32;
+    if (ESH == 0) return (float)*(G8*)a;
+    if (ESH == 1) return (float)*(G16*)a;
+    return *(G32*)a;
+}
+
+using IsoArgs = const IsoParams __attribute__((address_space(4)));     // the kernel arguments' own address space
+
+constexpr int ISO_UNROLL = 8;     // coarse samples per stretch: one cell test, then 8 gathers in flight per lane
+
+// The sample S / D of svr.h for a data point: the first LOD whose ROI holds it gives lod and element index.
+template <int NL>
+__device__ __forceinline__ bool cascade(const IsoLod* Ls, float dx, float dy, float dz, int& lod, size_t& idx) {
+#pragma unroll
+    for (int l = 0; l < NL; ++l)
+        if (lod_index(Ls[l], dx, dy, dz, idx)) { lod = l; return true; }
+    return false;
+}
+
+template <int NL, int ESH>
+__device__ __forceinline__ bool value_at(const IsoLod* Ls, float dx, float dy, float dz, float& v, int& lod, size_t& idx) {
+    if (!cascade<NL>(Ls, dx, dy, dz, lod, idx)) return false;
+#pragma unroll
+    for (int l = 0; l < NL; ++l)
+        if (lod == l) v = load_global<ESH>(static_cast<const char*>(Ls[l].density) + (idx << ESH));
+    return true;
+}
+
+// a cell maximum as the sample's conversion would deliver it: (float) of u8 / u16 is exact; float rings keep max |v|,
+// which bounds v from above (the host turns skipping off unless iso_value > 0)
+template <int ESH>
+__device__ __forceinline__ float load_cell(const void* cells, uint32_t i) {
+    typedef __attribute__((address_space(1))) const uint8_t G8;
+    typedef __attribute__((address_space(1))) const uint16_t G16;
+    typedef __attribute__((address_space(1))) const float G32;
+    if (ESH == 0) return (float)((G8*)cells)[i];
+    if (ESH == 1) return (float)((G16*)cells)[i];
+    return ((G32*)cells)[i];
+}
+
+// Can a sample of the stretch [i0, i0 + ISO_UNROLL) of this lane's ray reach iso?  Along a ray every voxel index is
+// monotone per axis (start + iter * step, the two multiplies and the truncation are monotone in iter), so the samples
+// of the stretch lie in the index box spanned by its two ends, at every LOD.  A LOD matters while no finer LOD's ROI
+// holds the whole box (then every sample resolves there or finer).  For a LOD that matters the part of the box inside
+// its ROI is looked up: when it spans at most two cells per axis, the `blk` maximum at the lower cell covers it (on
+// the torus, like the ring: ring extents are whole cells); wider boxes, and LODs without a cell grid, answer "maybe".
+template <int NL, int ESH>
+__device__ __forceinline__ bool stretch_may_reach(const IsoLod* Ls, const IsoParams& P, const Ray& R, int i0) {
+    const float ia = (float)i0, ib = (float)(i0 + (ISO_UNROLL - 1));
+    const float ax = (R.start.x + ia * R.step.x) * P.size[0], bx = (R.start.x + ib * R.step.x) * P.size[0];
+    const float ay = (R.start.y + ia * R.step.y) * P.size[1], by = (R.start.y + ib * R.step.y) * P.size[1];
+    const float az = (R.start.z + ia * R.step.z) * P.size[2], bz = (R.start.z + ib * R.step.z) * P.size[2];
+    bool maybe = false, open = true;
+    uint32_t cell[NL];
+    bool look[NL];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        const IsoLod& L = Ls[l];
+        const float a[3] = { ax * L.scale[0], ay * L.scale[1], az * L.scale[2] };
+        const float b[3] = { bx * L.scale[0], by * L.scale[1], bz * L.scale[2] };
+        bool inter = true, whole = true, wide = false;
+        uint32_t c[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int p = (int)a[k], q = (int)b[k];
+            const int lo = min(p, q), hi = max(p, q);
+            const int first = L.off[k], last = L.off[k] + (int)L.shape[k] - 1;
+            const int clo = max(lo, first), chi = min(hi, last);
+            inter = inter && clo <= chi;
+            whole = whole && lo >= first && hi <= last;
+            // ring slots before the wrap: below 2 * ring, so the cell coordinate is below 2 * cdim
+            const uint32_t ulo = (uint32_t)(clo - first) + L.wrap0[k], uhi = (uint32_t)(chi - first) + L.wrap0[k];
+            const uint32_t cl = ulo >> L.cshift, ch = uhi >> L.cshift;
+            wide = wide || ch > cl + 1u;
+            c[k] = min(cl, cl - L.cdim[k]);
+        }
+        const bool matters = open && inter;
+        look[l] = matters && !wide && L.cells != nullptr;
+        maybe = maybe || (matters && !look[l]);
+        cell[l] = look[l] ? (c[2] * L.cdim[1] + c[1]) * L.cdim[0] + c[0] : 0u;
+        open = open && !whole;
+    }
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        if (Ls[l].cells == nullptr) continue;                            // (uniform)
+        const float m = load_cell<ESH>(Ls[l].cells, cell[l]);
+        maybe = maybe || (look[l] && m >= P.iso);
+    }
+    return maybe;
+}
+
+template <int NL, int ESH>
+__global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
+    const int nblocks = P.tiles_x * P.tiles_y;
+    const int t = xcd_remap((int)blockIdx.x, nblocks);
+    const int tile_x = t % P.tiles_x, tile_y = t / P.tiles_x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int c = tile_x * 16 + (wave & 1) * 8 + (lane & 7);
+    const int r = tile_y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (c >= P.frame.out_w || r >= P.frame.out_h) return;
+    const size_t o = (size_t)r * (size_t)P.frame.out_w + (size_t)c;
+    const int x = P.frame.x0 + c;
+    const int y = P.frame.y0 + (r / P.frame.band_h) * P.frame.band_pitch + (r % P.frame.band_h);
+
+    Ray R;
+    R.start = { 0.f, 0.f, 0.f }; R.step = { 0.f, 0.f, 0.f }; R.nsteps = 0;
+    const bool frag = (x < P.frame.frame_w && y < P.frame.frame_h) && setup_ray(P, x, y, R);
+    const int nsteps = frag ? R.nsteps : 0;
+    const float iso = P.iso;
+    const IsoArgs* kq = (const IsoArgs*)__builtin_amdgcn_kernarg_segment_ptr();     // P itself: the only argument
+
+    int cand = -1;                       // the coarse candidate
+    uint32_t marched = 0u, skipped = 0u; // wave-uniform
+    for (int i0 = 0; ; i0 += ISO_UNROLL) {
+        const bool live = cand < 0 && i0 < nsteps;
+        if (!__any(live)) break;
+        // The LOD table is read from the kernel arguments afresh in each stretch (scalar loads from the constant
+        // cache) instead of being held in SGPRs across the loop (composite_kernels.hip does the same).
+        asm volatile("" : "+s"(kq));
+        const IsoLod* Ls = (const IsoLod*)kq->L;
+        if (P.skip) {
+            const bool veto = live && stretch_may_reach<NL, ESH>(Ls, P, R, i0);
+            if (!__any(veto)) { ++skipped; continue; }
+        }
+        ++marched;
+        if (live) {
+            const char* addr[ISO_UNROLL];
+            bool held[ISO_UNROLL];
+#pragma unroll
+            for (int j = 0; j < ISO_UNROLL; ++j) {
+                const float iter = (float)(i0 + j);                  // == the march's float counter (nsteps <= 2^24)
+                const float cx = R.start.x + iter * R.step.x;
+                const float cy = R.start.y + iter * R.step.y;
+                const float cz = R.start.z + iter * R.step.z;
+                const float dx = cx * P.size[0], dy = cy * P.size[1], dz = cz * P.size[2];
+                held[j] = false;                                     // no LOD holds it (or past the ray's end)
+                addr[j] = static_cast<const char*>(Ls[0].density);   // a valid address for the unused gather
+                bool done = i0 + j >= nsteps;
+#pragma unroll
+                for (int l = 0; l < NL; ++l) {
+                    size_t idx;
+                    if (done || !lod_index(Ls[l], dx, dy, dz, idx)) continue;
+                    done = true;
+                    held[j] = true;
+                    addr[j] = static_cast<const char*>(Ls[l].density) + (idx << ESH);
+                }
+            }
+            float vals[ISO_UNROLL];
+#pragma unroll
+            for (int j = 0; j < ISO_UNROLL; ++j) vals[j] = load_global<ESH>(addr[j]);
+#pragma unroll
+            for (int j = ISO_UNROLL - 1; j >= 0; --j)                // the first one wins
+                if (held[j] && vals[j] >= iso) cand = i0 + j;
+        }
+    }
+    if (P.counters && lane == 0) {       // lane 0 is the tile's top-left pixel: inside the frame whenever the wave is
+        atomicAdd(P.counters, marched);
+        atomicAdd(P.counters + 1, skipped);
+    }
+
+    float4 color = make_float4(0.f, 0.f, 0.f, 0.f);
+    float depth = 0.0f;
+    f3 n = { 0.f, 0.f, 0.f };
+    uint32_t label = 0u;
+    uint8_t cls = frag ? SVR_PIX_MISS : SVR_PIX_DISCARD;
+    unsigned long long pk = 0ull;
+    if (cand >= 0) {
+        cls = SVR_PIX_HIT;
+        const IsoLod* Ls = (const IsoLod*)kq->L;
+        // refine: the first sub-sample between the samples cand - 1 and cand that reaches the level
+        float iter = (float)cand;
+        if (cand > 0 && P.refine > 1) {
+            const float base = (float)(cand - 1), rf = (float)P.refine;
+            for (int k = 1; k < P.refine; ++k) {
+                const float it = base + (float)k / rf;
+                const float cx = R.start.x + it * R.step.x, cy = R.start.y + it * R.step.y, cz = R.start.z + it * R.step.z;
+                float v = 0.0f; int lod = 0; size_t idx = 0;
+                if (value_at<NL, ESH>(Ls, cx * P.size[0], cy * P.size[1], cz * P.size[2], v, lod, idx) && v >= iso) {
+                    iter = it;
+                    break;
+                }
+            }
+        }
+        const float cx = R.start.x + iter * R.step.x, cy = R.start.y + iter * R.step.y, cz = R.start.z + iter * R.step.z;
+        const float dx = cx * P.size[0], dy = cy * P.size[1], dz = cz * P.size[2];
+        int hl = 0; size_t hidx = 0;
+        (void)cascade<NL>(Ls, dx, dy, dz, hl, hidx);                 // holds: this very point gave the hit value
+        float sx = 1.0f, sy = 1.0f, sz = 1.0f;
+#pragma unroll
+        for (int l = 0; l < NL; ++l)
+            if (hl == l) {
+                sx = Ls[l].scale[0]; sy = Ls[l].scale[1]; sz = Ls[l].scale[2];
+                label = Ls[l].labels ? Ls[l].labels[hidx] : 0u;
+            }
+        // gradient: central differences, one voxel of the hit's LOD per axis
+        const float hx = 1.0f / sx, hy = 1.0f / sy, hz = 1.0f / sz;
+        float tap[6];
+        {
+            const float px[6] = { dx + hx, dx - hx, dx, dx, dx, dx };
+            const float py[6] = { dy, dy, dy + hy, dy - hy, dy, dy };
+            const float pz[6] = { dz, dz, dz, dz, dz + hz, dz - hz };
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                float v = 0.0f; int lod = 0; size_t idx = 0;
+                tap[k] = value_at<NL, ESH>(Ls, px[k], py[k], pz[k], v, lod, idx) ? v : 0.0f;
+            }
+        }
+        const f3 g = { (tap[0] - tap[1]) * sx, (tap[2] - tap[3]) * sy, (tap[4] - tap[5]) * sz };
+        const float* m = P.world_inv;
+        const f3 G = { (m[0] * g.x + m[1] * g.y) + m[2] * g.z,
+                       (m[4] * g.x + m[5] * g.y) + m[6] * g.z,
+                       (m[8] * g.x + m[9] * g.y) + m[10] * g.z };
+        // towards the viewer along the pixel's ray, in world space
+        const f3 sd = { R.step.x * P.size[0], R.step.y * P.size[1], R.step.z * P.size[2] };
+        const f3 w = { (P.world[0] * sd.x + P.world[4] * sd.y) + P.world[8] * sd.z,
+                       (P.world[1] * sd.x + P.world[5] * sd.y) + P.world[9] * sd.z,
+                       (P.world[2] * sd.x + P.world[6] * sd.y) + P.world[10] * sd.z };
+        const float vl = sqrtf(dot3(w, w));
+        f3 v = { 0.f, 0.f, 0.f };
+        if (vl > 0.0f && vl < INFINITY) v = { -w.x / vl, -w.y / vl, -w.z / vl };
+        const float gl = sqrtf(dot3(G, G));
+        n = v;
+        if (gl > 0.0f && gl < INFINITY) n = { -G.x / gl, -G.y / gl, -G.z / gl };
+        f3 l = v;
+        if (!P.headlight) l = { P.light[0], P.light[1], P.light[2] };
+        const f3 hv = { l.x + v.x, l.y + v.y, l.z + v.z };
+        const float hlen = sqrtf(dot3(hv, hv));
+        f3 h = { 0.f, 0.f, 0.f };
+        if (hlen > 0.0f && hlen < INFINITY) h = { hv.x / hlen, hv.y / hlen, hv.z / hlen };
+        const float ndl = fabsf(dot3(n, l));
+        float sp = fabsf(dot3(n, h));
+        for (int k = 0; k < P.shininess_log2; ++k) sp = sp * sp;
+        f3 base = { P.base[0], P.base[1], P.base[2] };
+        if (P.tint) {
+            const float* hs = P.colors + 4u * (label % P.color_count);
+            base = hsv_to_rgb(hs[0], hs[1], 1.0f);
+        }
+        const float tt = P.ambient + P.diffuse * ndl;
+        const float ss = P.specular * sp;
+        color = make_float4(fminf(fmaxf(base.x * tt + ss, 0.0f), 1.0f), fminf(fmaxf(base.y * tt + ss, 0.0f), 1.0f),
+                            fminf(fmaxf(base.z * tt + ss, 0.0f), 1.0f), P.opacity);
+        {   // the march's shade_and_store depth formula at the hit coordinate
+            const f4 wp = mat_vec(P.world, cx - 0.5f, cy - 0.5f, cz - 0.5f, 1.0f);
+            const f4 ndc = mat_vec(P.pc, wp.x, wp.y, wp.z, wp.w);
+            depth = ndc.z / fmaxf(ndc.w, 0.001f);
+        }
+        pk = (unsigned long long)min(P.pick_id, 0xFFFFFu) | ((unsigned long long)pick_field(cx) << 20) |
+             ((unsigned long long)pick_field(cy) << 34) | ((unsigned long long)pick_field(cz) << 48);
+    }
+    reinterpret_cast<float4*>(P.rgba)[o] = color;
+    if (P.depth) P.depth[o] = depth;
+    if (P.label) P.label[o] = label;
+    if (P.flags) P.flags[o] = cls;
+    if (P.steps) P.steps[o] = cand >= 0 ? (uint32_t)(cand + 1) : (uint32_t)nsteps;
+    if (P.pick) P.pick[o] = pk;
+    if (P.normal) { P.normal[3 * o] = n.x; P.normal[3 * o + 1] = n.y; P.normal[3 * o + 2] = n.z; }
+}
+
+template <int NL>
+hipError_t launch_nl(const IsoParams& P, int esh, dim3 grid, hipStream_t stream) {
+    if (esh == 0)      hipLaunchKernelGGL((iso_kernel<NL, 0>), grid, dim3(256), 0, stream, P);
+    else if (esh == 1) hipLaunchKernelGGL((iso_kernel<NL, 1>), grid, dim3(256), 0, stream, P);
+    else               hipLaunchKernelGGL((iso_kernel<NL, 2>), grid, dim3(256), 0, stream, P);
+    return hipGetLastError();
+}
+
+// f32 matrix helpers in the contract's operation order (svr_api.hip's)
+void mat_vec4(const float* m, const float* v, float* r) {
+    for (int i = 0; i < 4; ++i) r[i] = ((m[0 + i] * v[0] + m[4 + i] * v[1]) + m[8 + i] * v[2]) + m[12 + i] * v[3];
+}
+void mat_mul4(const float* a, const float* b, float* out) {
+    for (int c = 0; c < 4; ++c) mat_vec4(a, b + 4 * c, out + 4 * c);
+}
+
+}  // namespace
+
+// Declared in svr_api.hip, which validates the arguments, orders the launch against the uploads and marks it as a
+// render.
+hipError_t svr_launch_iso(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr, const svr_iso_params& ip,
+                          const svr_outputs& out, hipStream_t stream) {
+    IsoParams P;
+    memset(&P, 0, sizeof(P));
+    float tmp[16];
+    mat_mul4(cam.world_inv, cam.cam_inv, tmp);               // as svr_render (vs_main.wgsl:22, left-assoc)
+    mat_mul4(tmp, cam.proj_inv, P.ndc_to_data);
+    mat_mul4(cam.proj, cam.cam, P.pc);
+    memcpy(P.world, cam.world, sizeof(P.world));
+    memcpy(P.world_inv, cam.world_inv, sizeof(P.world_inv));
+    for (int a = 0; a < 3; ++a) P.size[a] = cam.volume_dimensions[a];
+    const float mx = fmaxf(P.size[0], fmaxf(P.size[1], P.size[2]));
+    P.rel_step = fminf(fmaxf(sqrtf(mx) / 20.0f, 0.1f), 0.8f);   // fs_main.wgsl:20
+    P.frame = fr;
+    const svr_material& m = c->material;
+    P.opacity = m.opacity;
+    P.clip_count = m.clipping_plane_count; P.clip_all = m.clipping_mode_all;
+    for (uint32_t k = 0; k < m.clipping_plane_count; ++k)
+        for (int a = 0; a < 4; ++a) P.clip[k][a] = c->clip_host[4 * k + a];
+    P.color_count = m.color_count; P.colors = c->colors_dev;
+    P.iso = ip.iso_value; P.refine = ip.refine;
+    for (int a = 0; a < 3; ++a) { P.base[a] = ip.iso_color[a]; P.light[a] = ip.light_direction[a]; }
+    P.tint = ip.color_by_label != 0 && m.color_count > 0;
+    P.ambient = ip.ambient; P.diffuse = ip.diffuse; P.specular = ip.specular;
+    P.shininess_log2 = ip.shininess_log2; P.headlight = ip.headlight != 0;
+    P.tiles_x = (fr.out_w + 15) / 16; P.tiles_y = (fr.out_h + 15) / 16;
+    P.rgba = out.rgba; P.depth = out.depth; P.label = out.label; P.flags = out.flags; P.steps = out.steps;
+    P.pick = reinterpret_cast<unsigned long long*>(out.pick); P.pick_id = out.pick_id;
+    P.normal = ip.normal; P.counters = ip.skip_counters;
+    // The cell test compares a maximum converted like a sample ((float) of u8 / u16 is exact) with iso_value itself, so
+    // it is exact for integer rings.  Float rings keep max |v|: an upper bound of v, a proof only while iso_value > 0.
+    // At iso_value <= 0 integer rings hit at the first resident sample anyway.
+    bool any_cells = false;
+    for (int l = 0; l < c->num_lods; ++l) {
+        const LodStorage& S = c->lod[l];
+        IsoLod& Q = P.L[l];
+        Q.density = S.density; Q.labels = S.labels;
+        Q.cells = c->cells_dil_all ? S.cells_dil : nullptr;
+        any_cells = any_cells || Q.cells;
+        Q.cshift = S.cshift;
+        for (int a = 0; a < 3; ++a) {
+            Q.off[a] = S.state.offset[a];
+            Q.shape[a] = (uint32_t)S.state.shape[a];
+            Q.ring[a] = (uint32_t)S.ring[a];
+            Q.wrap0[a] = (uint32_t)(S.state.offset[a] % S.ring[a]);     // (svr_set_lod_state: offsets are >= 0)
+            Q.scale[a] = S.state.scale[a];
+            Q.cdim[a] = (uint32_t)S.cdim[a];
+        }
+    }
+    P.skip = any_cells && !ip.no_skip && ip.iso_value > 0.0f;
+    const int esh = c->density_storage == SVR_U8 ? 0 : (c->density_storage == SVR_U16 ? 1 : 2);
+    const dim3 grid((unsigned)(P.tiles_x * P.tiles_y));
+    switch (c->num_lods) {
+        case 1: return launch_nl<1>(P, esh, grid, stream);
+        case 2: return launch_nl<2>(P, esh, grid, stream);
+        case 3: return launch_nl<3>(P, esh, grid, stream);
+        case 4: return launch_nl<4>(P, esh, grid, stream);
+        case 5: return launch_nl<5>(P, esh, grid, stream);
+        case 6: return launch_nl<6>(P, esh, grid, stream);
+        case 7: return launch_nl<7>(P, esh, grid, stream);
+        default: return launch_nl<8>(P, esh, grid, stream);
+    }
+}

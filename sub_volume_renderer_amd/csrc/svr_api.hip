@@ -55,6 +55,9 @@ hipError_t svr_launch_slab(const svr_ctx* c, const svr_slab_params& sp, const fl
 hipError_t svr_launch_composite(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr,
                                 const svr_composite_params& cp, const svr_outputs& out, const float* table, int K,
                                 hipStream_t stream);
+// iso_kernels.hip (same reason).
+hipError_t svr_launch_iso(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr, const svr_iso_params& ip,
+                          const svr_outputs& out, hipStream_t stream);
 
 namespace {
 
@@ -1296,6 +1299,38 @@ int svr_composite(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, const 
     // ordered like a render: behind the published uploads, and later uploads behind this composite (mark_render)
     if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
     SVR_HIP_TRY(svr_launch_composite(c, *cam, f, *cp, *out, table, K, s));
+    return mark_render(c, s);
+}
+
+int svr_iso(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, const svr_iso_params* ip, const svr_outputs* out,
+            void* stream) {
+    SVR_REQUIRE(c && cam && fr && ip && out && out->rgba, "svr_iso: null argument");
+    SVR_REQUIRE(c->material_set, "svr_iso: svr_set_material has not been called");
+    SVR_REQUIRE(fr->frame_w > 0 && fr->frame_h > 0 && fr->out_w > 0 && fr->out_h > 0, "svr_iso: empty frame");
+    SVR_REQUIRE(fr->x0 >= 0 && fr->y0 >= 0, "svr_iso: negative tile origin");
+    for (int a = 0; a < 3; ++a)
+        SVR_REQUIRE(cam->volume_dimensions[a] >= 1.0f, "svr_iso: volume_dimensions must be >= 1");
+    SVR_REQUIRE(ip->iso_value == ip->iso_value, "svr_iso: iso_value must not be NaN");
+    SVR_REQUIRE(ip->refine >= 0 && ip->refine <= SVR_ISO_MAX_REFINE, "svr_iso: refine must be in 0 .. 16");
+    SVR_REQUIRE(ip->shininess_log2 >= 0 && ip->shininess_log2 <= SVR_ISO_MAX_SHININESS_LOG2,
+                "svr_iso: shininess_log2 must be in 0 .. 10");
+    SVR_REQUIRE(ip->ambient >= 0.0f && ip->ambient < INFINITY && ip->diffuse >= 0.0f && ip->diffuse < INFINITY &&
+                ip->specular >= 0.0f && ip->specular < INFINITY,
+                "svr_iso: ambient, diffuse and specular must be finite and >= 0");
+    for (int a = 0; a < 3; ++a)
+        SVR_REQUIRE(ip->iso_color[a] >= 0.0f && ip->iso_color[a] <= 1.0f, "svr_iso: iso_color must be in [0, 1]");
+    if (!ip->headlight) {
+        const float* d = ip->light_direction;
+        const float len2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+        SVR_REQUIRE(fabsf(sqrtf(len2) - 1.0f) <= 1e-3f, "svr_iso: light_direction must be finite and of unit length");
+    }
+    svr_frame f = *fr;
+    if (f.band_h <= 0) { f.band_h = fr->out_h; f.band_pitch = fr->out_h; }
+    DeviceGuard guard(c->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);         // NULL = default stream, as in svr_render
+    // ordered like a render: behind the published uploads, and later uploads behind this draw (mark_render)
+    if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
+    SVR_HIP_TRY(svr_launch_iso(c, *cam, f, *ip, *out, s));
     return mark_render(c, s);
 }
 
