@@ -31,7 +31,8 @@ def main():
         ("warm", warm, 0.99, False),
         ("by_label", TransferFunction.linear(opacity=0.6), 0.99, True),
     ]
-    for name, tf, cutoff, tint in views:
+    for name, tf, cutoff, tint in views + [("warm_linear", warm, 0.99, False)]:
+        m.interpolation = "linear" if name.endswith("_linear") else "nearest"     # the ray's input: eight texels blended
         m.transfer_function, m.alpha_cutoff, m.color_by_label = tf, cutoff, tint
         res = volume.render(camera, scene.width, scene.height, count_steps=True)
         path = os.path.join(out_dir, f"composite_{name}.png")

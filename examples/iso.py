@@ -31,6 +31,8 @@ def main():
         ("low", lo + 0.25 * (hi - lo), dict(color_by_label=False, iso_color=(0.85, 0.75, 0.6), light_direction=None)),
         ("by_label", lo + 0.5 * (hi - lo), dict(color_by_label=True, light_direction=(-0.5, 0.7, 0.5), specular=0.5)),
     ]
+    # the last view again under linear sampling: smooth surfaces and normals instead of voxel staircases
+    views.append(("by_label_linear", views[-1][1], dict(views[-1][2], interpolation="linear")))
     for name, level, settings in views:
         m.iso_value = level
         for key, value in settings.items():

@@ -51,6 +51,11 @@ def main():
             write_png(path, rgba)
             counts = {int(k): int((lod == k).sum()) for k in np.unique(lod)}
             print(f"z-normal by level of detail -> {path}  (pixels per LOD, 255 = not resident / outside: {counts})")
+            # the same plane under linear sampling: the 2 x 2 pixel blocks of pixel size 0.5 become gradients
+            s = volume.render_slice(origin, u, v, width, height, interpolation="linear")
+            path = os.path.join(out_dir, "slice_z_linear.png")
+            write_png(path, compose(volume, s).cpu().numpy())
+            print(f"z-normal, interpolation='linear' -> {path}")
 
 
 if __name__ == "__main__":

@@ -574,6 +574,45 @@ typedef struct svr_iso_params {
 int  svr_iso(svr_ctx* ctx, const svr_camera* cam, const svr_frame* frame, const svr_iso_params* params,
              const svr_outputs* out, void* stream);
 
+/* ---- interpolation: an opt-in trilinear sample for svr_slice, svr_slab, svr_composite and svr_iso (pygfx's volume
+ * materials carry `interpolation`; the reference samples nearest texels because a hardware sampler cannot follow a
+ * wrapping ring, KNOWLEDGE.md "textureLoad vs textureSample" - here the wrap is software in every kernel).  An addition
+ * within ABI version 9: one new symbol, no struct changes.  svr_render (LMIP, weighted average) is not affected: the
+ * march samples nearest texels, the contract with the reference.
+ * THE LINEAR SAMPLE, defined HERE (numpy restatement: tests/linear_twin.py), in f32, in this order, with no fused
+ * operations, for a data point d (what the definitions above call dx = coord * size):
+ *   LOD    unchanged: with s_a = d_a * scale_l[a], the first LOD l whose ROI holds (int)s_a on every axis.  A point no
+ *          LOD holds has no value, as before.  label and lod are the nearest sample's (labels are never interpolated).
+ *   cell   p_a = s_a - 0.5f;  b_a = floorf(p_a);  f_a = p_a - b_a;  i0_a = (int)b_a;  i1_a = i0_a + 1
+ *          (floorf, not a cast: p_a is negative in the first half voxel).
+ *   clamp  i0_a and i1_a each clamped to [offset_l[a], offset_l[a] + shape_l[a] - 1], the LOD's resident window: all
+ *          eight corners come from LOD l, through the same ring wrap as the nearest texel.  Clamp-to-edge at the window
+ *          (which is clipped to the data extent and grown to the chunk grid: at a volume face it ends at, or a partial
+ *          chunk past, the last voxel).  The seam nearest sampling shows at a LOD border remains; fading LODs into one
+ *          another is a different feature.
+ *   blend  v_xyz = the corner texel converted to f32 as for the nearest sample; x first, then y, then z, each as
+ *          a + f * (b - a):
+ *            c00 = v000 + f_x * (v100 - v000);  c10 = v010 + f_x * (v110 - v010)
+ *            c01 = v001 + f_x * (v101 - v001);  c11 = v011 + f_x * (v111 - v011)
+ *            c0  = c00 + f_y * (c10 - c00);     c1  = c01 + f_y * (c11 - c01)
+ *            value = c0 + f_z * (c1 - c0)
+ * At a voxel centre every f_a is 0 and the value is the nearest texel bit for bit (finite data).
+ * With SVR_INTERP_LINEAR the sample replaces the nearest texel, and nothing else in each definition changes, in:
+ *   svr_slice      the value plane and the shading input.
+ *   svr_slab       every sample's value_k; reductions, tie rules and depth are unchanged.
+ *   svr_composite  s of every sample.
+ *   svr_iso        S(iter) of the coarse and refine searches, and D(p) of the gradient (the linear sample at p with its
+ *                  own LOD pick, 0 where no LOD holds p; h_a and the final * scale_l[a] stay those of the hit's LOD).
+ *                  The refine search stays a linear search; the field along a ray is now continuous inside a LOD, so it
+ *                  locates the crossing inside a voxel (to 1 / refine of a step) instead of the face of a voxel.
+ *                  Empty-space skipping stays invisible: the looked-up index box grows by one voxel per side and the
+ *                  cell maximum is compared with a rounding margin ("linear sampling").
+ * Read by the svr_slice, svr_slab, svr_composite and svr_iso calls enqueued after it; a render-thread call like
+ * svr_set_material.  A fresh context is SVR_INTERP_NEAREST.  An unknown mode: SVR_ERR_INVALID, state unchanged. */
+#define SVR_INTERP_NEAREST 0
+#define SVR_INTERP_LINEAR  1
+int  svr_set_interpolation(svr_ctx* ctx, int mode);
+
 /* ---- sync */
 int  svr_sync(svr_ctx* ctx);                 /* both streams idle */
 int  svr_sync_uploads(svr_ctx* ctx);         /* upload stream idle */

@@ -74,6 +74,7 @@ class SubVolumeMaterial:
         self.clipping_planes = ()
         self.clipping_mode = "ANY"
         self.render_mode = "lmip"
+        self.interpolation = "nearest"
         self.weight_falloff = 0.5
         self.transfer_function = None
         self.alpha_cutoff = 0.99
@@ -194,6 +195,25 @@ class SubVolumeMaterial:
         if mode not in self.RENDER_MODES:
             raise ValueError(f"render_mode must be one of {self.RENDER_MODES}, not {mode!r}")
         self._store("render_mode", mode)
+
+    # -- interpolation (pygfx's volume materials carry the same property) ---------------------------------------
+    INTERPOLATIONS = ("nearest", "linear")
+
+    @property
+    def interpolation(self) -> str:
+        """"nearest" (the default): every sample is one ring texel, as the reference's ``textureLoad`` reads it.
+        "linear": the "composite" and "iso" render modes, and ``render_slice`` / ``render_slab``, blend the eight
+        texels around each sample trilinearly inside the LOD the nearest sample picks (``svr_set_interpolation`` in
+        ``include/svr.h``); labels are never interpolated.  The march ("lmip", "mip", "weighted_average") samples
+        nearest texels only: ``SubVolume.render`` refuses those modes while this is "linear"."""
+        return self._u["interpolation"]
+
+    @interpolation.setter
+    def interpolation(self, mode) -> None:
+        mode = str(mode).lower()
+        if mode not in self.INTERPOLATIONS:
+            raise ValueError(f"interpolation must be one of {self.INTERPOLATIONS}, not {mode!r}")
+        self._store("interpolation", mode)
 
     @property
     def weight_falloff(self) -> float:

@@ -172,6 +172,8 @@ class IsoParams(C.Structure):
     ]
 
 
+INTERPOLATIONS = {"nearest": 0, "linear": 1}      # SVR_INTERP_*
+
 ISO_MAX_REFINE = 16                                 # SVR_ISO_MAX_REFINE
 ISO_MAX_SHININESS_LOG2 = 10                         # SVR_ISO_MAX_SHININESS_LOG2
 
@@ -225,6 +227,7 @@ SIGNATURES = {
                                 C.POINTER(Outputs), C.c_void_p]),
     "svr_iso": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Frame), C.POINTER(IsoParams), C.POINTER(Outputs),
                           C.c_void_p]),
+    "svr_set_interpolation": (C.c_int, [C.c_void_p, C.c_int]),
     "svr_sync": (C.c_int, [C.c_void_p]),
     "svr_sync_uploads": (C.c_int, [C.c_void_p]),
     "svr_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),

@@ -426,6 +426,14 @@ class SubVolume(_HasWorld):
                 "svr_set_transfer_function")
         self._tf_pushed = key
 
+    def _push_interpolation(self, interpolation=None):
+        """Set the context's sampling for the next slice / slab / composite / iso call: ``interpolation``, or the
+        material's when it is None."""
+        mode = self.material.interpolation if interpolation is None else str(interpolation).lower()
+        if mode not in N.INTERPOLATIONS:
+            raise ValueError(f"interpolation must be one of {tuple(N.INTERPOLATIONS)} or None, not {interpolation!r}")
+        N.check(N.lib().svr_set_interpolation(self._rings.handle, N.INTERPOLATIONS[mode]), "svr_set_interpolation")
+
     def _camera_key(self, camera):
         # the projection enters as the bytes of its matrix, whatever kind of camera made it: every parameter of
         # any projection (fov, width, height, zoom, aspect, depth range) changes the key exactly when it changes
@@ -547,6 +555,11 @@ class SubVolume(_HasWorld):
         """
         import torch
 
+        if self.material.interpolation == "linear" and self.material.render_mode not in ("composite", "iso"):
+            raise ValueError(
+                f"render_mode {self.material.render_mode!r} is the march, which samples nearest texels (the reference's "
+                "behaviour); interpolation='linear' applies to the render modes 'composite' and 'iso' and to "
+                "render_slice / render_slab (pass interpolation='linear' to those calls to keep this material nearest)")
         handle = self.prepare()
         cb = self.camera_block(camera)
         fb = self.frame_block(width, height, region)
@@ -573,6 +586,7 @@ class SubVolume(_HasWorld):
             # direct volume rendering (svr_composite): same camera block, frame and outputs; its steps plane is
             # written by the production kernel
             self._push_transfer_function()
+            self._push_interpolation()
             cp = N.CompositeParams(self.material.alpha_cutoff, 1 if self.material.color_by_label else 0)
             N.check(N.lib().svr_composite(handle, C.byref(cb), C.byref(fb), C.byref(cp), C.byref(ob), C.c_void_p(stream)),
                     "svr_composite")
@@ -581,6 +595,7 @@ class SubVolume(_HasWorld):
             # lit iso-surface (svr_iso): same camera block, frame and outputs; its steps plane is written by the
             # production kernel
             ip = self._iso_params(res)
+            self._push_interpolation()
             N.check(N.lib().svr_iso(handle, C.byref(cb), C.byref(fb), C.byref(ip), C.byref(ob), C.c_void_p(stream)), "svr_iso")
             return res
         N.check(
@@ -654,17 +669,19 @@ class SubVolume(_HasWorld):
                 raise ValueError(f"out.{name} must be on the volume's GPU device")
 
     def render_slice(self, origin, u, v, width: int, height: int, *, region: FrameRegion | None = None,
-                     out: SliceResult | None = None, stream=None) -> SliceResult:
+                     out: SliceResult | None = None, stream=None, interpolation: str | None = None) -> SliceResult:
         """Sample the multi-LOD rings on a world-space plane into device tensors (definition: ``svr_slice`` in
         include/svr.h).  ``origin`` is the world position of the image centre, ``u`` / ``v`` the world steps from one
         column / row to the next (rows go down the image); world coordinates are those of the camera positions passed
         to :meth:`render` (the volume's ``world`` transform applies).  Every pixel shows the voxel a ray sample at its
-        centre would read: the finest resident LOD's texel.  Asynchronous on the current torch stream.  Unless ``out`` is
+        centre would read: the finest resident LOD's texel, or with ``interpolation`` "linear" (None: the material's
+        setting) the trilinear blend of the eight texels around it.  Asynchronous on the current torch stream.  Unless ``out`` is
         given, the output tensors of a size are reused by the next call of that size (the last few sizes are kept), so
         a result is overwritten by the next slice of its size."""
         origin, u, v, width, height = self._plane_args(origin, u, v, width, height)
         fb = self._plane_frame(region, out, width, height)
         handle = self.prepare()
+        self._push_interpolation(interpolation)
         res = out or self._slice_outputs(fb.out_h, fb.out_w)
         pl = self._plane_struct(origin, u, v)
         N.check(N.lib().svr_slice(handle, C.byref(pl), C.byref(fb), C.byref(self._plane_ob(res)),
@@ -672,14 +689,16 @@ class SubVolume(_HasWorld):
         return res
 
     def render_slab(self, origin, u, v, w, samples: int, width: int, height: int, *, mode: str = "max",
-                    region: FrameRegion | None = None, out: SliceResult | None = None, stream=None) -> SliceResult:
+                    region: FrameRegion | None = None, out: SliceResult | None = None, stream=None,
+                    interpolation: str | None = None) -> SliceResult:
         """Thick-slab projection (definition: ``svr_slab`` in include/svr.h): ``samples`` slices of
         :meth:`render_slice`'s plane stacked along the world step ``w`` and centred on it (sample k lies
         ``k - (samples - 1) / 2`` steps off the plane), reduced per pixel over the samples that hit a resident voxel:
         ``mode`` "max" / "min" (value, label, LOD and depth of the winning sample, ties to the first) or "mean" (the mean
         of the values; label, LOD and depth of the sample "max" picks).  ``depth`` is the winner's signed world offset
         from the centre plane, so ``outline(..., depth_tolerance=)`` applies.  Returns the planes of a slice; its
-        output tensors are kept per size apart from the slices', so a slab never overwrites the last slice."""
+        output tensors are kept per size apart from the slices', so a slab never overwrites the last slice.
+        ``interpolation`` as in :meth:`render_slice`: every sample's value is the linear sample."""
         origin, u, v, width, height = self._plane_args(origin, u, v, width, height)
         w = _vec3("w", w)
         f32 = np.float32
@@ -702,6 +721,7 @@ class SubVolume(_HasWorld):
             raise ValueError("w must have a length and a data-space step that are finite in float32")
         fb = self._plane_frame(region, out, width, height)
         handle = self.prepare()
+        self._push_interpolation(interpolation)
         res = out or self._slab_outputs(fb.out_h, fb.out_w)
         sp = N.SlabParams()
         sp.plane = self._plane_struct(origin, u, v)

@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include "svr_internal.h"
+#include "linear_sample.h"
 
 namespace {
 
@@ -196,9 +197,12 @@ __device__ __forceinline__ float load_global(const char* a) {
 using CompArgs = const CompParams __attribute__((address_space(4)));     // the kernel arguments' own address space
 
 constexpr int COMP_UNROLL = 8;     // samples whose gathers are in flight together per lane
+constexpr int COMP_LIN_UNROLL = 4; // the same under linear sampling: 4 samples x 8 corners = 32 gathers in flight
 
-template <int NL, int ESH, bool TINT>
+// LIN: s of every sample is the linear sample of svr.h (svr_set_interpolation); labels stay the nearest sample's.
+template <int NL, int ESH, bool TINT, bool LIN>
 __global__ __launch_bounds__(256) void composite_kernel(const CompParams P) {
+    constexpr int U = LIN ? COMP_LIN_UNROLL : COMP_UNROLL;
     extern __shared__ float4 lut[];
     for (int k = threadIdx.x; k < P.K; k += 256) lut[k] = reinterpret_cast<const float4*>(P.table)[k];
     __syncthreads();
@@ -224,16 +228,18 @@ __global__ __launch_bounds__(256) void composite_kernel(const CompParams P) {
         const float inv_lo = P.clim0, span = P.clim1 - P.clim0;
         const CompArgs* kq = (const CompArgs*)__builtin_amdgcn_kernarg_segment_ptr();     // P itself: the only argument
         bool alive = true;
-        for (int i0 = 0; alive && i0 < R.nsteps; i0 += COMP_UNROLL) {
+        for (int i0 = 0; alive && i0 < R.nsteps; i0 += U) {
             // The LOD table is read from the kernel arguments afresh in each batch (scalar loads from the constant
             // cache) instead of being held in SGPRs across the loop (slice_kernels.hip does the same).
             asm volatile("" : "+s"(kq));
             const CompLod* Ls = (const CompLod*)kq->L;
-            const char* addr[COMP_UNROLL];
-            const uint32_t* laddr[COMP_UNROLL];
-            int sl[COMP_UNROLL];
+            const uint32_t* laddr[U];
+            int sl[U];
+            float vals[U];
+            if constexpr (!LIN) {
+            const char* addr[U];
 #pragma unroll
-            for (int j = 0; j < COMP_UNROLL; ++j) {
+            for (int j = 0; j < U; ++j) {
                 const float iter = (float)(i0 + j);                  // == the march's float counter (nsteps <= 2^24)
                 const float cx = R.start.x + iter * R.step.x;
                 const float cy = R.start.y + iter * R.step.y;
@@ -253,16 +259,56 @@ __global__ __launch_bounds__(256) void composite_kernel(const CompParams P) {
                     if (TINT && Ls[l].labels) laddr[j] = Ls[l].labels + idx;
                 }
             }
-            float vals[COMP_UNROLL];
-            uint32_t labs[COMP_UNROLL];
 #pragma unroll
-            for (int j = 0; j < COMP_UNROLL; ++j) vals[j] = load_global<ESH>(addr[j]);
+            for (int j = 0; j < U; ++j) vals[j] = load_global<ESH>(addr[j]);
+            } else {
+            const char* addr[U][8];
+            float frac[U][3];
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                const float iter = (float)(i0 + j);
+                const float cx = R.start.x + iter * R.step.x;
+                const float cy = R.start.y + iter * R.step.y;
+                const float cz = R.start.z + iter * R.step.z;
+                const float dx = cx * P.size[0], dy = cy * P.size[1], dz = cz * P.size[2];
+                sl[j] = NL;
+                laddr[j] = nullptr;
+                svr_linear::LaneLod q = svr_linear::lane_lod_zero();
+                const char* base = static_cast<const char*>(Ls[0].density);   // a valid address for the unused gathers
+                bool done = i0 + j >= R.nsteps;
+#pragma unroll
+                for (int l = 0; l < NL; ++l) {
+                    size_t idx;
+                    if (done || !lod_index(Ls[l], dx, dy, dz, idx)) continue;
+                    done = true;
+                    sl[j] = l;
+                    svr_linear::lane_lod_take(q, Ls[l], dx * Ls[l].scale[0], dy * Ls[l].scale[1], dz * Ls[l].scale[2]);
+                    base = static_cast<const char*>(Ls[l].density);
+                    if (TINT && Ls[l].labels) laddr[j] = Ls[l].labels + idx;
+                }
+                const svr_linear::Cell cell = svr_linear::cell_of(q);
+                size_t o[8];
+                svr_linear::row_offsets(q, cell, o);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) addr[j][k] = base + (o[k] << ESH);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) frac[j][a] = cell.f[a];
+            }
+            float v8[U][8];
+#pragma unroll
+            for (int j = 0; j < U; ++j)
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v8[j][k] = load_global<ESH>(addr[j][k]);
+#pragma unroll
+            for (int j = 0; j < U; ++j) vals[j] = svr_linear::blend(v8[j], frac[j]);
+            }
+            uint32_t labs[U];
             if (TINT) {
 #pragma unroll
-                for (int j = 0; j < COMP_UNROLL; ++j) labs[j] = laddr[j] ? *laddr[j] : 0u;
+                for (int j = 0; j < U; ++j) labs[j] = laddr[j] ? *laddr[j] : 0u;
             }
 #pragma unroll
-            for (int j = 0; j < COMP_UNROLL; ++j) {
+            for (int j = 0; j < U; ++j) {
                 if (!alive || i0 + j >= R.nsteps) break;
                 ++steps;
                 if (sl[j] == NL) continue;                           // not resident: contributes nothing
@@ -330,18 +376,32 @@ __global__ __launch_bounds__(256) void composite_kernel(const CompParams P) {
     if (P.pick) P.pick[o] = pk;
 }
 
-template <int NL, int ESH>
+template <int NL, int ESH, bool LIN>
 hipError_t launch_esh(const CompParams& P, bool tint, dim3 grid, size_t lds, hipStream_t stream) {
-    if (tint) hipLaunchKernelGGL((composite_kernel<NL, ESH, true>), grid, dim3(256), lds, stream, P);
-    else hipLaunchKernelGGL((composite_kernel<NL, ESH, false>), grid, dim3(256), lds, stream, P);
+    if (tint) hipLaunchKernelGGL((composite_kernel<NL, ESH, true, LIN>), grid, dim3(256), lds, stream, P);
+    else hipLaunchKernelGGL((composite_kernel<NL, ESH, false, LIN>), grid, dim3(256), lds, stream, P);
     return hipGetLastError();
 }
 
-template <int NL>
+template <int NL, bool LIN>
 hipError_t launch_nl(const CompParams& P, int esh, bool tint, dim3 grid, size_t lds, hipStream_t stream) {
-    if (esh == 0) return launch_esh<NL, 0>(P, tint, grid, lds, stream);
-    if (esh == 1) return launch_esh<NL, 1>(P, tint, grid, lds, stream);
-    return launch_esh<NL, 2>(P, tint, grid, lds, stream);
+    if (esh == 0) return launch_esh<NL, 0, LIN>(P, tint, grid, lds, stream);
+    if (esh == 1) return launch_esh<NL, 1, LIN>(P, tint, grid, lds, stream);
+    return launch_esh<NL, 2, LIN>(P, tint, grid, lds, stream);
+}
+
+template <bool LIN>
+hipError_t launch_composite(const CompParams& P, int num_lods, int esh, bool tint, dim3 grid, size_t lds, hipStream_t stream) {
+    switch (num_lods) {
+        case 1: return launch_nl<1, LIN>(P, esh, tint, grid, lds, stream);
+        case 2: return launch_nl<2, LIN>(P, esh, tint, grid, lds, stream);
+        case 3: return launch_nl<3, LIN>(P, esh, tint, grid, lds, stream);
+        case 4: return launch_nl<4, LIN>(P, esh, tint, grid, lds, stream);
+        case 5: return launch_nl<5, LIN>(P, esh, tint, grid, lds, stream);
+        case 6: return launch_nl<6, LIN>(P, esh, tint, grid, lds, stream);
+        case 7: return launch_nl<7, LIN>(P, esh, tint, grid, lds, stream);
+        default: return launch_nl<8, LIN>(P, esh, tint, grid, lds, stream);
+    }
 }
 
 // f32 matrix helpers in the contract's operation order (svr_api.hip's)
@@ -355,10 +415,10 @@ void mat_mul4(const float* a, const float* b, float* out) {
 }  // namespace
 
 // Declared in svr_api.hip, which validates the arguments, orders the launch against the uploads and marks it as a
-// render.  table: the device copy of the transfer function (K entries of RGBA).
+// render.  table: the device copy of the transfer function (K entries of RGBA).  interp: SVR_INTERP_*.
 hipError_t svr_launch_composite(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr,
                                 const svr_composite_params& cp, const svr_outputs& out, const float* table, int K,
-                                hipStream_t stream) {
+                                int interp, hipStream_t stream) {
     CompParams P;
     memset(&P, 0, sizeof(P));
     float tmp[16];
@@ -397,14 +457,6 @@ hipError_t svr_launch_composite(const svr_ctx* c, const svr_camera& cam, const s
     const bool tint = cp.color_by_label != 0;
     const dim3 grid((unsigned)(P.tiles_x * P.tiles_y));
     const size_t lds = (size_t)K * 4 * sizeof(float);
-    switch (c->num_lods) {
-        case 1: return launch_nl<1>(P, esh, tint, grid, lds, stream);
-        case 2: return launch_nl<2>(P, esh, tint, grid, lds, stream);
-        case 3: return launch_nl<3>(P, esh, tint, grid, lds, stream);
-        case 4: return launch_nl<4>(P, esh, tint, grid, lds, stream);
-        case 5: return launch_nl<5>(P, esh, tint, grid, lds, stream);
-        case 6: return launch_nl<6>(P, esh, tint, grid, lds, stream);
-        case 7: return launch_nl<7>(P, esh, tint, grid, lds, stream);
-        default: return launch_nl<8>(P, esh, tint, grid, lds, stream);
-    }
+    return interp == SVR_INTERP_LINEAR ? launch_composite<true>(P, c->num_lods, esh, tint, grid, lds, stream)
+                                       : launch_composite<false>(P, c->num_lods, esh, tint, grid, lds, stream);
 }

@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include "svr_internal.h"
+#include "linear_sample.h"
 
 namespace {
 
@@ -222,12 +223,30 @@ __device__ __forceinline__ bool cascade(const IsoLod* Ls, float dx, float dy, fl
     return false;
 }
 
-template <int NL, int ESH>
+template <int NL, int ESH, bool LIN>
 __device__ __forceinline__ bool value_at(const IsoLod* Ls, float dx, float dy, float dz, float& v, int& lod, size_t& idx) {
     if (!cascade<NL>(Ls, dx, dy, dz, lod, idx)) return false;
+    if constexpr (!LIN) {
 #pragma unroll
     for (int l = 0; l < NL; ++l)
         if (lod == l) v = load_global<ESH>(static_cast<const char*>(Ls[l].density) + (idx << ESH));
+    } else {       // the linear sample inside the LOD the nearest sample picked
+        svr_linear::LaneLod q = svr_linear::lane_lod_zero();
+        const char* base = static_cast<const char*>(Ls[0].density);
+#pragma unroll
+        for (int l = 0; l < NL; ++l)
+            if (lod == l) {
+                svr_linear::lane_lod_take(q, Ls[l], dx * Ls[l].scale[0], dy * Ls[l].scale[1], dz * Ls[l].scale[2]);
+                base = static_cast<const char*>(Ls[l].density);
+            }
+        const svr_linear::Cell cell = svr_linear::cell_of(q);
+        size_t o[8];
+        svr_linear::row_offsets(q, cell, o);
+        float c8[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) c8[k] = load_global<ESH>(base + (o[k] << ESH));
+        v = svr_linear::blend(c8, cell.f);
+    }
     return true;
 }
 
@@ -249,7 +268,15 @@ __device__ __forceinline__ float load_cell(const void* cells, uint32_t i) {
 // holds the whole box (then every sample resolves there or finer).  For a LOD that matters the part of the box inside
 // its ROI is looked up: when it spans at most two cells per axis, the `blk` maximum at the lower cell covers it (on
 // the torus, like the ring: ring extents are whole cells); wider boxes, and LODs without a cell grid, answer "maybe".
-template <int NL, int ESH>
+//
+// LIN (linear sampling): a sample that resolves at a LOD reads the voxels floor(s - 0.5) and that plus one per axis,
+// clamped to the window: at most one voxel outside the box on each side.  Which LODs matter is decided on the box
+// itself (the LOD pick is the nearest sample's); the box that is LOOKED UP is grown by one voxel per side and clamped
+// to the window before the two-cell test.  The blend of eight corners of magnitude <= m is, in exact arithmetic, at
+// most m; each of the three nested f32 lerps a + f * (b - a), 0 <= f < 1, |a|, |b| <= M, returns at most
+// M * (1 + 5u + O(u^2)), u = 2^-24 (two roundings on a term of magnitude <= 2 M, one on the sum), so the computed
+// value stays below m * (1 + 2^-19) plus what underflow can add (far below FLT_MIN).  The test compares that bound.
+template <int NL, int ESH, bool LIN>
 __device__ __forceinline__ bool stretch_may_reach(const IsoLod* Ls, const IsoParams& P, const Ray& R, int i0) {
     const float ia = (float)i0, ib = (float)(i0 + (ISO_UNROLL - 1));
     const float ax = (R.start.x + ia * R.step.x) * P.size[0], bx = (R.start.x + ib * R.step.x) * P.size[0];
@@ -274,7 +301,8 @@ __device__ __forceinline__ bool stretch_may_reach(const IsoLod* Ls, const IsoPar
             inter = inter && clo <= chi;
             whole = whole && lo >= first && hi <= last;
             // ring slots before the wrap: below 2 * ring, so the cell coordinate is below 2 * cdim
-            const uint32_t ulo = (uint32_t)(clo - first) + L.wrap0[k], uhi = (uint32_t)(chi - first) + L.wrap0[k];
+            const int glo = LIN ? max(lo - 1, first) : clo, ghi = LIN ? min(hi + 1, last) : chi;   // (the looked-up box)
+            const uint32_t ulo = (uint32_t)(glo - first) + L.wrap0[k], uhi = (uint32_t)(ghi - first) + L.wrap0[k];
             const uint32_t cl = ulo >> L.cshift, ch = uhi >> L.cshift;
             wide = wide || ch > cl + 1u;
             c[k] = min(cl, cl - L.cdim[k]);
@@ -289,12 +317,17 @@ __device__ __forceinline__ bool stretch_may_reach(const IsoLod* Ls, const IsoPar
     for (int l = 0; l < NL; ++l) {
         if (Ls[l].cells == nullptr) continue;                            // (uniform)
         const float m = load_cell<ESH>(Ls[l].cells, cell[l]);
-        maybe = maybe || (look[l] && m >= P.iso);
+        const float bound = LIN ? (m + m * 0x1p-19f) + 1.17549435e-38f : m;
+        maybe = maybe || (look[l] && bound >= P.iso);
     }
     return maybe;
 }
 
-template <int NL, int ESH>
+constexpr int ISO_LIN_GROUP = 4;   // linear sampling: a stretch's samples go in groups of 4 (32 gathers in flight per lane)
+
+// LIN: S(iter) and D(p) are the linear sample of svr.h (svr_set_interpolation); label and LOD of the hit stay the
+// nearest sample's.
+template <int NL, int ESH, bool LIN>
 __global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
     const int nblocks = P.tiles_x * P.tiles_y;
     const int t = xcd_remap((int)blockIdx.x, nblocks);
@@ -324,11 +357,57 @@ __global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
         asm volatile("" : "+s"(kq));
         const IsoLod* Ls = (const IsoLod*)kq->L;
         if (P.skip) {
-            const bool veto = live && stretch_may_reach<NL, ESH>(Ls, P, R, i0);
+            const bool veto = live && stretch_may_reach<NL, ESH, LIN>(Ls, P, R, i0);
             if (!__any(veto)) { ++skipped; continue; }
         }
         ++marched;
-        if (live) {
+        if constexpr (LIN) {
+            if (live) {
+#pragma unroll
+                for (int g0 = 0; g0 < ISO_UNROLL; g0 += ISO_LIN_GROUP) {
+                    if (cand >= 0 || i0 + g0 >= nsteps) break;       // the first one wins: later groups cannot
+                    const char* addr[ISO_LIN_GROUP][8];
+                    float frac[ISO_LIN_GROUP][3];
+                    bool held[ISO_LIN_GROUP];
+#pragma unroll
+                    for (int j = 0; j < ISO_LIN_GROUP; ++j) {
+                        const float iter = (float)(i0 + g0 + j);
+                        const float cx = R.start.x + iter * R.step.x;
+                        const float cy = R.start.y + iter * R.step.y;
+                        const float cz = R.start.z + iter * R.step.z;
+                        const float dx = cx * P.size[0], dy = cy * P.size[1], dz = cz * P.size[2];
+                        held[j] = false;
+                        svr_linear::LaneLod q = svr_linear::lane_lod_zero();
+                        const char* base = static_cast<const char*>(Ls[0].density);   // a valid address for the unused gathers
+                        bool done = i0 + g0 + j >= nsteps;
+#pragma unroll
+                        for (int l = 0; l < NL; ++l) {
+                            size_t idx;
+                            if (done || !lod_index(Ls[l], dx, dy, dz, idx)) continue;
+                            done = true;
+                            held[j] = true;
+                            svr_linear::lane_lod_take(q, Ls[l], dx * Ls[l].scale[0], dy * Ls[l].scale[1], dz * Ls[l].scale[2]);
+                            base = static_cast<const char*>(Ls[l].density);
+                        }
+                        const svr_linear::Cell cell = svr_linear::cell_of(q);
+                        size_t o[8];
+                        svr_linear::row_offsets(q, cell, o);
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) addr[j][k] = base + (o[k] << ESH);
+#pragma unroll
+                        for (int a = 0; a < 3; ++a) frac[j][a] = cell.f[a];
+                    }
+                    float v8[ISO_LIN_GROUP][8];
+#pragma unroll
+                    for (int j = 0; j < ISO_LIN_GROUP; ++j)
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) v8[j][k] = load_global<ESH>(addr[j][k]);
+#pragma unroll
+                    for (int j = ISO_LIN_GROUP - 1; j >= 0; --j)     // the first one wins
+                        if (held[j] && svr_linear::blend(v8[j], frac[j]) >= iso) cand = i0 + g0 + j;
+                }
+            }
+        } else if (live) {
             const char* addr[ISO_UNROLL];
             bool held[ISO_UNROLL];
 #pragma unroll
@@ -380,7 +459,7 @@ __global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
                 const float it = base + (float)k / rf;
                 const float cx = R.start.x + it * R.step.x, cy = R.start.y + it * R.step.y, cz = R.start.z + it * R.step.z;
                 float v = 0.0f; int lod = 0; size_t idx = 0;
-                if (value_at<NL, ESH>(Ls, cx * P.size[0], cy * P.size[1], cz * P.size[2], v, lod, idx) && v >= iso) {
+                if (value_at<NL, ESH, LIN>(Ls, cx * P.size[0], cy * P.size[1], cz * P.size[2], v, lod, idx) && v >= iso) {
                     iter = it;
                     break;
                 }
@@ -407,7 +486,7 @@ __global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
                 float v = 0.0f; int lod = 0; size_t idx = 0;
-                tap[k] = value_at<NL, ESH>(Ls, px[k], py[k], pz[k], v, lod, idx) ? v : 0.0f;
+                tap[k] = value_at<NL, ESH, LIN>(Ls, px[k], py[k], pz[k], v, lod, idx) ? v : 0.0f;
             }
         }
         const f3 g = { (tap[0] - tap[1]) * sx, (tap[2] - tap[3]) * sy, (tap[4] - tap[5]) * sz };
@@ -461,12 +540,26 @@ __global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
     if (P.normal) { P.normal[3 * o] = n.x; P.normal[3 * o + 1] = n.y; P.normal[3 * o + 2] = n.z; }
 }
 
-template <int NL>
+template <int NL, bool LIN>
 hipError_t launch_nl(const IsoParams& P, int esh, dim3 grid, hipStream_t stream) {
-    if (esh == 0)      hipLaunchKernelGGL((iso_kernel<NL, 0>), grid, dim3(256), 0, stream, P);
-    else if (esh == 1) hipLaunchKernelGGL((iso_kernel<NL, 1>), grid, dim3(256), 0, stream, P);
-    else               hipLaunchKernelGGL((iso_kernel<NL, 2>), grid, dim3(256), 0, stream, P);
+    if (esh == 0)      hipLaunchKernelGGL((iso_kernel<NL, 0, LIN>), grid, dim3(256), 0, stream, P);
+    else if (esh == 1) hipLaunchKernelGGL((iso_kernel<NL, 1, LIN>), grid, dim3(256), 0, stream, P);
+    else               hipLaunchKernelGGL((iso_kernel<NL, 2, LIN>), grid, dim3(256), 0, stream, P);
     return hipGetLastError();
+}
+
+template <bool LIN>
+hipError_t launch_iso(const IsoParams& P, int num_lods, int esh, dim3 grid, hipStream_t stream) {
+    switch (num_lods) {
+        case 1: return launch_nl<1, LIN>(P, esh, grid, stream);
+        case 2: return launch_nl<2, LIN>(P, esh, grid, stream);
+        case 3: return launch_nl<3, LIN>(P, esh, grid, stream);
+        case 4: return launch_nl<4, LIN>(P, esh, grid, stream);
+        case 5: return launch_nl<5, LIN>(P, esh, grid, stream);
+        case 6: return launch_nl<6, LIN>(P, esh, grid, stream);
+        case 7: return launch_nl<7, LIN>(P, esh, grid, stream);
+        default: return launch_nl<8, LIN>(P, esh, grid, stream);
+    }
 }
 
 // f32 matrix helpers in the contract's operation order (svr_api.hip's)
@@ -480,9 +573,9 @@ void mat_mul4(const float* a, const float* b, float* out) {
 }  // namespace
 
 // Declared in svr_api.hip, which validates the arguments, orders the launch against the uploads and marks it as a
-// render.
+// render.  interp: SVR_INTERP_*.
 hipError_t svr_launch_iso(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr, const svr_iso_params& ip,
-                          const svr_outputs& out, hipStream_t stream) {
+                          const svr_outputs& out, int interp, hipStream_t stream) {
     IsoParams P;
     memset(&P, 0, sizeof(P));
     float tmp[16];
@@ -533,14 +626,6 @@ hipError_t svr_launch_iso(const svr_ctx* c, const svr_camera& cam, const svr_fra
     P.skip = any_cells && !ip.no_skip && ip.iso_value > 0.0f;
     const int esh = c->density_storage == SVR_U8 ? 0 : (c->density_storage == SVR_U16 ? 1 : 2);
     const dim3 grid((unsigned)(P.tiles_x * P.tiles_y));
-    switch (c->num_lods) {
-        case 1: return launch_nl<1>(P, esh, grid, stream);
-        case 2: return launch_nl<2>(P, esh, grid, stream);
-        case 3: return launch_nl<3>(P, esh, grid, stream);
-        case 4: return launch_nl<4>(P, esh, grid, stream);
-        case 5: return launch_nl<5>(P, esh, grid, stream);
-        case 6: return launch_nl<6>(P, esh, grid, stream);
-        case 7: return launch_nl<7>(P, esh, grid, stream);
-        default: return launch_nl<8>(P, esh, grid, stream);
-    }
+    return interp == SVR_INTERP_LINEAR ? launch_iso<true>(P, c->num_lods, esh, grid, stream)
+                                       : launch_iso<false>(P, c->num_lods, esh, grid, stream);
 }

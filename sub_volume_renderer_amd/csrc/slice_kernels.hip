@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "svr_internal.h"
+#include "linear_sample.h"
 
 namespace {
 
@@ -98,7 +99,21 @@ __device__ __forceinline__ float load_texel(const void* base, size_t i) {
     return static_cast<const float*>(base)[i];
 }
 
-template <int NL, int ESH>
+// a texel at a byte address known to be in global memory (global_load rather than flat_load: the ring pointers come
+// from the kernel arguments through a pointer the compiler cannot see into)
+template <int ESH>
+__device__ __forceinline__ float load_global(const char* a) {
+    typedef __attribute__((address_space(1))) const uint8_t G8;
+    typedef __attribute__((address_space(1))) const uint16_t G16;
+    typedef __attribute__((address_space(1))) const float G32;
+    if (ESH == 0) return (float)*(G8*)a;
+    if (ESH == 1) return (float)*(G16*)a;
+    return *(G32*)a;
+}
+
+// LIN: the linear sample of svr.h (svr_set_interpolation) in place of the nearest texel; label and lod stay the
+// nearest sample's.  The eight gathers of a pixel are issued together, then blended.
+template <int NL, int ESH, bool LIN>
 __global__ __launch_bounds__(256) void slice_kernel(const SliceParams P) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = blockIdx.x * 16 + (lane & 15);
@@ -128,6 +143,7 @@ __global__ __launch_bounds__(256) void slice_kernel(const SliceParams P) {
         if (dx >= 0.0f && dx < P.size[0] && dy >= 0.0f && dy < P.size[1] && dz >= 0.0f && dz < P.size[2]) {
             cls = SVR_PIX_MISS;
             color.w = 1.0f;
+            if constexpr (!LIN) {
 #pragma unroll
             for (int l = 0; l < NL; ++l) {
                 uint32_t wx, wy, wz;
@@ -140,6 +156,37 @@ __global__ __launch_bounds__(256) void slice_kernel(const SliceParams P) {
                 lod = (uint8_t)l;
                 cls = SVR_PIX_HIT;
                 break;
+            }
+            } else {
+                svr_linear::LaneLod q = svr_linear::lane_lod_zero();
+                const char* base = nullptr;
+                const uint32_t* labels = nullptr;
+                size_t lidx = 0;
+                bool blocked = false;
+#pragma unroll
+                for (int l = 0; l < NL; ++l) {
+                    uint32_t wx, wy, wz;
+                    if (cls == SVR_PIX_HIT || !lod_slot(P.L[l], dx, dy, dz, wx, wy, wz)) continue;
+                    const SliceLod& L = P.L[l];
+                    svr_linear::lane_lod_take(q, L, dx * L.scale[0], dy * L.scale[1], dz * L.scale[2]);
+                    blocked = L.twin != nullptr;
+                    base = static_cast<const char*>(blocked ? L.twin : L.density);
+                    labels = L.labels;
+                    lidx = ((size_t)wz * L.ring[1] + wy) * (size_t)L.ring[0] + wx;
+                    lod = (uint8_t)l;
+                    cls = SVR_PIX_HIT;
+                }
+                if (cls == SVR_PIX_HIT) {
+                    const svr_linear::Cell cell = svr_linear::cell_of(q);
+                    size_t o[8];
+                    if (blocked) svr_linear::blocked_offsets(ESH, q, cell, o);
+                    else svr_linear::row_offsets(q, cell, o);
+                    float v[8];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) v[k] = load_global<ESH>(base + (o[k] << ESH));
+                    value = svr_linear::blend(v, cell.f);
+                    label = labels ? labels[lidx] : 0u;
+                }
             }
             if (cls == SVR_PIX_HIT) {
                 float s = (value - P.clim0) / (P.clim1 - P.clim0);
@@ -159,12 +206,26 @@ __global__ __launch_bounds__(256) void slice_kernel(const SliceParams P) {
     if (P.lod) P.lod[o] = lod;
 }
 
-template <int NL>
+template <int NL, bool LIN>
 hipError_t launch_nl(const SliceParams& P, int esh, dim3 grid, hipStream_t stream) {
-    if (esh == 0) hipLaunchKernelGGL((slice_kernel<NL, 0>), grid, dim3(256), 0, stream, P);
-    else if (esh == 1) hipLaunchKernelGGL((slice_kernel<NL, 1>), grid, dim3(256), 0, stream, P);
-    else hipLaunchKernelGGL((slice_kernel<NL, 2>), grid, dim3(256), 0, stream, P);
+    if (esh == 0) hipLaunchKernelGGL((slice_kernel<NL, 0, LIN>), grid, dim3(256), 0, stream, P);
+    else if (esh == 1) hipLaunchKernelGGL((slice_kernel<NL, 1, LIN>), grid, dim3(256), 0, stream, P);
+    else hipLaunchKernelGGL((slice_kernel<NL, 2, LIN>), grid, dim3(256), 0, stream, P);
     return hipGetLastError();
+}
+
+template <bool LIN>
+hipError_t launch_slice(const SliceParams& P, int num_lods, dim3 grid, hipStream_t stream) {
+    switch (num_lods) {
+        case 1: return launch_nl<1, LIN>(P, P.esh, grid, stream);
+        case 2: return launch_nl<2, LIN>(P, P.esh, grid, stream);
+        case 3: return launch_nl<3, LIN>(P, P.esh, grid, stream);
+        case 4: return launch_nl<4, LIN>(P, P.esh, grid, stream);
+        case 5: return launch_nl<5, LIN>(P, P.esh, grid, stream);
+        case 6: return launch_nl<6, LIN>(P, P.esh, grid, stream);
+        case 7: return launch_nl<7, LIN>(P, P.esh, grid, stream);
+        default: return launch_nl<8, LIN>(P, P.esh, grid, stream);
+    }
 }
 
 // ---- thick slabs (svr_slab, include/svr.h): N samples per pixel along the data-space step dw, reduced to one.
@@ -181,18 +242,6 @@ struct SlabParams {
     int32_t mean;
 };
 
-// a texel at a byte address known to be in global memory (global_load rather than flat_load: the ring pointers come
-// from the kernel arguments through a pointer the compiler cannot see into)
-template <int ESH>
-__device__ __forceinline__ float load_global(const char* a) {
-    typedef __attribute__((address_space(1))) const uint8_t G8;
-    typedef __attribute__((address_space(1))) const uint16_t G16;
-    typedef __attribute__((address_space(1))) const float G32;
-    if (ESH == 0) return (float)*(G8*)a;
-    if (ESH == 1) return (float)*(G16*)a;
-    return *(G32*)a;
-}
-
 using SlabArgs = const SlabParams __attribute__((address_space(4)));     // the kernel arguments' own address space
 
 constexpr int SLAB_UNROLL = 4;     // samples whose gathers are in flight together per lane
@@ -201,7 +250,9 @@ constexpr int SLAB_UNROLL = 4;     // samples whose gathers are in flight togeth
 // x is at least 2^-25 in magnitude (q_k + 0.5f is exact by Sterbenz's lemma where it is small), so x / size stays
 // normal and both steps are exact scalings; 0, inf and NaN pass through unchanged.  The round trip, three IEEE
 // divisions per sample, is skipped.
-template <int NL, int ESH, bool POW2>
+// LIN: every sample's value_k is the linear sample of svr.h; it runs the general coordinate chain (POW2 = false: results
+// are defined by that chain, and the cell needs its s bits).
+template <int NL, int ESH, bool POW2, bool LIN>
 __global__ __launch_bounds__(256) void slab_kernel(const SlabParams Q) {
     const SliceParams& P = Q.S;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -238,10 +289,12 @@ __global__ __launch_bounds__(256) void slab_kernel(const SlabParams Q) {
             asm volatile("" : "+s"(kq));
             const SliceLod* Ls = (const SliceLod*)kq->S.L;
             // addresses of SLAB_UNROLL samples first, then their gathers, then the compares in increasing k
-            const char* addr[SLAB_UNROLL];
             size_t ridx[SLAB_UNROLL];
             int sl[SLAB_UNROLL];
             bool in[SLAB_UNROLL];
+            float vals[SLAB_UNROLL];
+            if constexpr (!LIN) {
+            const char* addr[SLAB_UNROLL];
 #pragma unroll
             for (int j = 0; j < SLAB_UNROLL; ++j) {
                 const float t = (float)(k0 + j) - Q.half;
@@ -267,9 +320,55 @@ __global__ __launch_bounds__(256) void slab_kernel(const SlabParams Q) {
                                      : static_cast<const char*>(L.density) + (ridx[j] << ESH);
                 }
             }
-            float vals[SLAB_UNROLL];
 #pragma unroll
             for (int j = 0; j < SLAB_UNROLL; ++j) vals[j] = load_global<ESH>(addr[j]);
+            } else {
+            const char* addr[SLAB_UNROLL][8];
+            float frac[SLAB_UNROLL][3];
+#pragma unroll
+            for (int j = 0; j < SLAB_UNROLL; ++j) {
+                const float t = (float)(k0 + j) - Q.half;
+                const float ax = qx + t * Q.dw[0], ay = qy + t * Q.dw[1], az = qz + t * Q.dw[2];
+                const float dx = ((ax + 0.5f) / P.size[0]) * P.size[0];
+                const float dy = ((ay + 0.5f) / P.size[1]) * P.size[1];
+                const float dz = ((az + 0.5f) / P.size[2]) * P.size[2];
+                in[j] = k0 + j < Q.samples && dx >= 0.0f && dx < P.size[0] && dy >= 0.0f && dy < P.size[1] &&
+                        dz >= 0.0f && dz < P.size[2];
+                sl[j] = NL;                                        // no LOD holds it
+                ridx[j] = 0;
+                svr_linear::LaneLod q = svr_linear::lane_lod_zero();
+                const char* base = static_cast<const char*>(Ls[0].density);   // a valid address for the unused gathers
+                bool blocked = false;
+                bool done = !in[j];
+#pragma unroll
+                for (int l = 0; l < NL; ++l) {
+                    uint32_t wx, wy, wz;
+                    if (done || !lod_slot(Ls[l], dx, dy, dz, wx, wy, wz)) continue;
+                    const SliceLod& L = Ls[l];
+                    done = true;
+                    sl[j] = l;
+                    ridx[j] = ((size_t)wz * L.ring[1] + wy) * (size_t)L.ring[0] + wx;
+                    svr_linear::lane_lod_take(q, L, dx * L.scale[0], dy * L.scale[1], dz * L.scale[2]);
+                    blocked = L.twin != nullptr;
+                    base = static_cast<const char*>(blocked ? L.twin : L.density);
+                }
+                const svr_linear::Cell cell = svr_linear::cell_of(q);
+                size_t o[8];
+                if (blocked) svr_linear::blocked_offsets(ESH, q, cell, o);
+                else svr_linear::row_offsets(q, cell, o);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) addr[j][k] = base + (o[k] << ESH);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) frac[j][a] = cell.f[a];
+            }
+            float v8[SLAB_UNROLL][8];
+#pragma unroll
+            for (int j = 0; j < SLAB_UNROLL; ++j)
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v8[j][k] = load_global<ESH>(addr[j][k]);
+#pragma unroll
+            for (int j = 0; j < SLAB_UNROLL; ++j) vals[j] = svr_linear::blend(v8[j], frac[j]);
+            }
 #pragma unroll
             for (int j = 0; j < SLAB_UNROLL; ++j) {
                 inside |= in[j];
@@ -307,25 +406,25 @@ __global__ __launch_bounds__(256) void slab_kernel(const SlabParams Q) {
     if (P.lod) P.lod[o] = lod;
 }
 
-template <int NL, bool POW2>
+template <int NL, bool POW2, bool LIN>
 hipError_t launch_slab_nl(const SlabParams& Q, dim3 grid, hipStream_t stream) {
-    if (Q.S.esh == 0) hipLaunchKernelGGL((slab_kernel<NL, 0, POW2>), grid, dim3(256), 0, stream, Q);
-    else if (Q.S.esh == 1) hipLaunchKernelGGL((slab_kernel<NL, 1, POW2>), grid, dim3(256), 0, stream, Q);
-    else hipLaunchKernelGGL((slab_kernel<NL, 2, POW2>), grid, dim3(256), 0, stream, Q);
+    if (Q.S.esh == 0) hipLaunchKernelGGL((slab_kernel<NL, 0, POW2, LIN>), grid, dim3(256), 0, stream, Q);
+    else if (Q.S.esh == 1) hipLaunchKernelGGL((slab_kernel<NL, 1, POW2, LIN>), grid, dim3(256), 0, stream, Q);
+    else hipLaunchKernelGGL((slab_kernel<NL, 2, POW2, LIN>), grid, dim3(256), 0, stream, Q);
     return hipGetLastError();
 }
 
-template <bool POW2>
+template <bool POW2, bool LIN = false>
 hipError_t launch_slab(const SlabParams& Q, int num_lods, dim3 grid, hipStream_t stream) {
     switch (num_lods) {
-        case 1: return launch_slab_nl<1, POW2>(Q, grid, stream);
-        case 2: return launch_slab_nl<2, POW2>(Q, grid, stream);
-        case 3: return launch_slab_nl<3, POW2>(Q, grid, stream);
-        case 4: return launch_slab_nl<4, POW2>(Q, grid, stream);
-        case 5: return launch_slab_nl<5, POW2>(Q, grid, stream);
-        case 6: return launch_slab_nl<6, POW2>(Q, grid, stream);
-        case 7: return launch_slab_nl<7, POW2>(Q, grid, stream);
-        default: return launch_slab_nl<8, POW2>(Q, grid, stream);
+        case 1: return launch_slab_nl<1, POW2, LIN>(Q, grid, stream);
+        case 2: return launch_slab_nl<2, POW2, LIN>(Q, grid, stream);
+        case 3: return launch_slab_nl<3, POW2, LIN>(Q, grid, stream);
+        case 4: return launch_slab_nl<4, POW2, LIN>(Q, grid, stream);
+        case 5: return launch_slab_nl<5, POW2, LIN>(Q, grid, stream);
+        case 6: return launch_slab_nl<6, POW2, LIN>(Q, grid, stream);
+        case 7: return launch_slab_nl<7, POW2, LIN>(Q, grid, stream);
+        default: return launch_slab_nl<8, POW2, LIN>(Q, grid, stream);
     }
 }
 
@@ -387,9 +486,11 @@ float row_lines(int esh, const float e[3], float cap = 64.0f) {
 }  // namespace
 
 // Declared in svr_api.hip (which validates the arguments, orders the launch against the uploads and marks it as a
-// render).  twin_mode: 0 rows only, 2 the micro-block copy wherever there is one, 1 per LOD the fewer lines.
+// render).  twin_mode: 0 rows only, 2 the micro-block copy wherever there is one, 1 per LOD the fewer lines (the
+// estimate is the nearest sample's under either interpolation: a cell adds one voxel per axis to the footprint).
+// interp: SVR_INTERP_*.
 hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const svr_frame& fr, const svr_slice_outputs& out,
-                            int twin_mode, hipStream_t stream) {
+                            int twin_mode, int interp, hipStream_t stream) {
     SliceParams P;
     float du[3], dv[3];
     fill_slice_params(c, pl, fr, out, P, du, dv);
@@ -404,16 +505,8 @@ hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const s
         }
     }
     const dim3 grid((unsigned)((fr.out_w + 15) / 16), (unsigned)((fr.out_h + 15) / 16));
-    switch (c->num_lods) {
-        case 1: return launch_nl<1>(P, P.esh, grid, stream);
-        case 2: return launch_nl<2>(P, P.esh, grid, stream);
-        case 3: return launch_nl<3>(P, P.esh, grid, stream);
-        case 4: return launch_nl<4>(P, P.esh, grid, stream);
-        case 5: return launch_nl<5>(P, P.esh, grid, stream);
-        case 6: return launch_nl<6>(P, P.esh, grid, stream);
-        case 7: return launch_nl<7>(P, P.esh, grid, stream);
-        default: return launch_nl<8>(P, P.esh, grid, stream);
-    }
+    return interp == SVR_INTERP_LINEAR ? launch_slice<true>(P, c->num_lods, grid, stream)
+                                       : launch_slice<false>(P, c->num_lods, grid, stream);
 }
 
 // Declared in svr_api.hip, like svr_launch_slice; svr_slab has validated the arguments and computed dw.
@@ -423,7 +516,7 @@ hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const s
 //   the distinct lines of the bounding box of the 16 x 4 tile x N samples (what has to reach the CU at least once).
 // The copy is read where that total is lower.
 hipError_t svr_launch_slab(const svr_ctx* c, const svr_slab_params& sp, const float dw[3], const svr_frame& fr,
-                           const svr_slice_outputs& out, int twin_mode, hipStream_t stream) {
+                           const svr_slice_outputs& out, int twin_mode, int interp, hipStream_t stream) {
     SlabParams Q;
     memset(&Q, 0, sizeof(Q));
     float du[3], dv[3];
@@ -459,5 +552,6 @@ hipError_t svr_launch_slab(const svr_ctx* c, const svr_slab_params& sp, const fl
         pow2 = pow2 && mant == 0.5f && e2 <= 25;
     }
     const dim3 grid((unsigned)((fr.out_w + 15) / 16), (unsigned)((fr.out_h + 15) / 16));
+    if (interp == SVR_INTERP_LINEAR) return launch_slab<false, true>(Q, c->num_lods, grid, stream);   // the general chain
     return pow2 ? launch_slab<true>(Q, c->num_lods, grid, stream) : launch_slab<false>(Q, c->num_lods, grid, stream);
 }

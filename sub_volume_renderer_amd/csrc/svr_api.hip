@@ -47,28 +47,31 @@ hipError_t svr_launch_outline(const float* rgba, const float* depth, const uint3
                               const uint32_t* sel, uint32_t nsel, float* out, uint8_t* mask, hipStream_t stream);
 // slice_kernels.hip (same reason).  twin_mode: 0 rows only, 1 per LOD the layout with fewer lines per wave, 2 the copy.
 hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const svr_frame& fr, const svr_slice_outputs& out,
-                            int twin_mode, hipStream_t stream);
+                            int twin_mode, int interp, hipStream_t stream);
 // slice_kernels.hip (same reason).  dw: the data-space sample step, computed and checked by svr_slab.
 hipError_t svr_launch_slab(const svr_ctx* c, const svr_slab_params& sp, const float dw[3], const svr_frame& fr,
-                           const svr_slice_outputs& out, int twin_mode, hipStream_t stream);
+                           const svr_slice_outputs& out, int twin_mode, int interp, hipStream_t stream);
 // composite_kernels.hip (same reason).  table: the device copy of the transfer function, K entries of RGBA.
 hipError_t svr_launch_composite(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr,
                                 const svr_composite_params& cp, const svr_outputs& out, const float* table, int K,
-                                hipStream_t stream);
+                                int interp, hipStream_t stream);
 // iso_kernels.hip (same reason).
 hipError_t svr_launch_iso(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr, const svr_iso_params& ip,
-                          const svr_outputs& out, hipStream_t stream);
+                          const svr_outputs& out, int interp, hipStream_t stream);
 
 namespace {
 
 // Transfer functions of svr_set_transfer_function, per context.  Kept here rather than in svr_ctx (svr_internal.h is
 // part of the kernel-source stamp).  Like the colour table of svr_set_material, every new table goes into a fresh
-// device buffer; the replaced ones are freed once the device has drained (or with the context).
+// device buffer; the replaced ones are freed once the device has drained (or with the context).  dev is null until a
+// table has been set.  The entry also carries the context's svr_set_interpolation mode (same reason): no entry means
+// SVR_INTERP_NEAREST.
 struct TransferTable {
     const svr_ctx* ctx;
     float* dev;
     int K;
     std::vector<float*> retired;
+    int interp;
 };
 std::mutex g_tf_mu;
 std::vector<TransferTable> g_tf;
@@ -76,6 +79,12 @@ std::vector<TransferTable> g_tf;
 TransferTable* transfer_table(const svr_ctx* c) {       // (under g_tf_mu)
     for (auto& t : g_tf) if (t.ctx == c) return &t;
     return nullptr;
+}
+
+int interpolation_of(const svr_ctx* c) {
+    std::lock_guard<std::mutex> lock(g_tf_mu);
+    const TransferTable* t = transfer_table(c);
+    return t ? t->interp : SVR_INTERP_NEAREST;
 }
 
 void drop_transfer_table(const svr_ctx* c) {
@@ -1204,7 +1213,7 @@ int svr_slice(svr_ctx* c, const svr_slice_plane* plane, const svr_frame* fr, con
     hipStream_t s = static_cast<hipStream_t>(stream);         // NULL = default stream, as in svr_render
     // ordered like a render: behind the published uploads, and later uploads behind this slice (mark_render)
     if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
-    SVR_HIP_TRY(svr_launch_slice(c, *plane, f, *out, twin_mode, s));
+    SVR_HIP_TRY(svr_launch_slice(c, *plane, f, *out, twin_mode, interpolation_of(c), s));
     return mark_render(c, s);
 }
 
@@ -1240,7 +1249,7 @@ int svr_slab(svr_ctx* c, const svr_slab_params* sp, const svr_frame* fr, const s
     hipStream_t s = static_cast<hipStream_t>(stream);
     // ordered like svr_slice: behind the published uploads, and later uploads behind this slab (mark_render)
     if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
-    SVR_HIP_TRY(svr_launch_slab(c, *sp, dw, f, *out, twin_mode, s));
+    SVR_HIP_TRY(svr_launch_slab(c, *sp, dw, f, *out, twin_mode, interpolation_of(c), s));
     return mark_render(c, s);
 }
 
@@ -1261,7 +1270,7 @@ int svr_set_transfer_function(svr_ctx* c, const float* rgba, int32_t K) {
     std::lock_guard<std::mutex> lock(g_tf_mu);
     TransferTable* t = transfer_table(c);
     if (!t) {
-        g_tf.push_back(TransferTable{ c, nullptr, 0, {} });
+        g_tf.push_back(TransferTable{ c, nullptr, 0, {}, SVR_INTERP_NEAREST });
         t = &g_tf.back();
     }
     if (t->dev) t->retired.push_back(t->dev);        // composites still in flight keep reading the old table
@@ -1275,6 +1284,20 @@ int svr_set_transfer_function(svr_ctx* c, const float* rgba, int32_t K) {
     return SVR_OK;
 }
 
+int svr_set_interpolation(svr_ctx* c, int mode) {
+    SVR_REQUIRE(c, "svr_set_interpolation: null ctx");
+    SVR_REQUIRE(mode == SVR_INTERP_NEAREST || mode == SVR_INTERP_LINEAR,
+                "svr_set_interpolation: mode must be SVR_INTERP_NEAREST or SVR_INTERP_LINEAR");
+    std::lock_guard<std::mutex> lock(g_tf_mu);
+    TransferTable* t = transfer_table(c);
+    if (!t) {
+        g_tf.push_back(TransferTable{ c, nullptr, 0, {}, SVR_INTERP_NEAREST });
+        t = &g_tf.back();
+    }
+    t->interp = mode;
+    return SVR_OK;
+}
+
 int svr_composite(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, const svr_composite_params* cp,
                   const svr_outputs* out, void* stream) {
     SVR_REQUIRE(c && cam && fr && cp && out && out->rgba, "svr_composite: null argument");
@@ -1285,11 +1308,11 @@ int svr_composite(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, const 
         SVR_REQUIRE(cam->volume_dimensions[a] >= 1.0f, "svr_composite: volume_dimensions must be >= 1");
     SVR_REQUIRE(cp->alpha_cutoff > 0.0f && cp->alpha_cutoff <= 1.0f, "svr_composite: alpha_cutoff must be in (0, 1]");
     const float* table = nullptr;
-    int K = 0;
+    int K = 0, interp = SVR_INTERP_NEAREST;
     {
         std::lock_guard<std::mutex> lock(g_tf_mu);
         const TransferTable* t = transfer_table(c);
-        if (t) { table = t->dev; K = t->K; }
+        if (t) { table = t->dev; K = t->K; interp = t->interp; }
     }
     SVR_REQUIRE(table, "svr_composite: svr_set_transfer_function has not been called");
     svr_frame f = *fr;
@@ -1298,7 +1321,7 @@ int svr_composite(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, const 
     hipStream_t s = static_cast<hipStream_t>(stream);         // NULL = default stream, as in svr_render
     // ordered like a render: behind the published uploads, and later uploads behind this composite (mark_render)
     if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
-    SVR_HIP_TRY(svr_launch_composite(c, *cam, f, *cp, *out, table, K, s));
+    SVR_HIP_TRY(svr_launch_composite(c, *cam, f, *cp, *out, table, K, interp, s));
     return mark_render(c, s);
 }
 
@@ -1330,7 +1353,7 @@ int svr_iso(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, const svr_is
     hipStream_t s = static_cast<hipStream_t>(stream);         // NULL = default stream, as in svr_render
     // ordered like a render: behind the published uploads, and later uploads behind this draw (mark_render)
     if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
-    SVR_HIP_TRY(svr_launch_iso(c, *cam, f, *ip, *out, s));
+    SVR_HIP_TRY(svr_launch_iso(c, *cam, f, *ip, *out, interpolation_of(c), s));
     return mark_render(c, s);
 }
 

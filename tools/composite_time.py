@@ -57,6 +57,8 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--boxes", type=int, default=3)
     ap.add_argument("--volume-n", type=int, default=1024)
+    ap.add_argument("--interpolation", default="nearest", choices=("nearest", "linear", "both"),
+                    help="svr_set_interpolation mode of the timed calls; both: nearest and linear alternate, case by case")
     ap.add_argument("--stats", default=None, help="print the composite kernels of a --stats run's CSV instead of timing")
     args = ap.parse_args()
     if args.stats:
@@ -124,19 +126,24 @@ def main():
             for _ in range(k):
                 N.check(lib.svr_composite(*argv), "svr_composite")
 
-        calls(5)
-        call_s = [window(calls) / args.calls for _ in range(args.boxes)]
-        hold = int(max(4.0 * max(call_s) * args.calls, 0.02) / per_cycle)
-        gpu_s = [window(calls, hold) / args.calls for _ in range(args.boxes)]
-        torch.cuda.synchronize()
-        gpu = float(np.median(gpu_s))
-        row = {"case": case, "storage": vol._rings.density_storage, "table_entries": tf.size, "alpha_cutoff": cutoff,
-               "call_ms": round(float(np.median(call_s)) * 1e3, 4), "gpu_ms": round(gpu * 1e3, 4),
-               "calls_per_box": args.calls, "samples": samples, "samples_per_s": float(f"{samples / gpu:.4g}"),
-               "hit_pixels": hits}
-        if case == "a":
-            row["lmip_full_samples"] = lmip_full
-        print(json.dumps(row), flush=True)
+        for interp in (("nearest", "linear") if args.interpolation == "both" else (args.interpolation,)):
+            # (samples and hit_pixels are the nearest render's: the rays are the same, linear values end some earlier or later)
+            N.check(lib.svr_set_interpolation(handle, N.INTERPOLATIONS[interp]), "svr_set_interpolation")
+            calls(5)
+            call_s = [window(calls) / args.calls for _ in range(args.boxes)]
+            hold = int(max(4.0 * max(call_s) * args.calls, 0.02) / per_cycle)
+            gpu_s = [window(calls, hold) / args.calls for _ in range(args.boxes)]
+            torch.cuda.synchronize()
+            gpu = float(np.median(gpu_s))
+            row = {"case": case, "storage": vol._rings.density_storage, "interpolation": interp, "table_entries": tf.size,
+                   "alpha_cutoff": cutoff, "call_ms": round(float(np.median(call_s)) * 1e3, 4), "gpu_ms": round(gpu * 1e3, 4),
+                   "gpu_ms_boxes": [round(t * 1e3, 4) for t in gpu_s],
+                   "calls_per_box": args.calls, "samples": samples, "samples_per_s": float(f"{samples / gpu:.4g}"),
+                   "hit_pixels": hits}
+            if case == "a":
+                row["lmip_full_samples"] = lmip_full
+            print(json.dumps(row), flush=True)
+        N.check(lib.svr_set_interpolation(handle, 0), "svr_set_interpolation")
     vol.close()
 
 

@@ -60,6 +60,8 @@ def main():
     ap.add_argument("--boxes", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--volume-n", type=int, default=1024)
+    ap.add_argument("--interpolation", default="nearest", choices=("nearest", "linear", "both"),
+                    help="svr_set_interpolation mode of the timed calls; both: nearest and linear alternate, case by case")
     ap.add_argument("--stats", default=None, help="print the kernels of a --stats run's CSV instead of timing")
     args = ap.parse_args()
     if args.stats:
@@ -110,25 +112,30 @@ def main():
     print(json.dumps({"storage": vol._rings.density_storage, "frame": [W, H], "volume_n": n_vol, "camera": args.camera,
                       "iso_value": level, "refine": args.refine}), flush=True)
 
+    interps = ("nearest", "linear") if args.interpolation == "both" else (args.interpolation,)
     # one counted render of each (steps planes, skip counters), then the production argument structs
     m.render_mode = "iso"
-    out = vol.iso_outputs(W, H, count_steps=True, normal=False, skip_counters=True)
-    vol.render(cam, W, H, count_steps=True, out=out)
-    torch.cuda.synchronize()
-    marched, skipped = (int(v) for v in out.skip_counters.cpu().numpy().view(np.uint32))
-    info = {"iso": {"hit_pixels": int((out.flags == N.SVR_PIX_HIT).sum()), "coarse_samples": int(out.steps.to(torch.int64).sum()),
-                    "wave_stretches_marched": marched, "wave_stretches_skipped": skipped,
-                    "skipped_share": round(skipped / max(marched + skipped, 1), 4)}}
+    info = {}
+    for interp in [i for i in interps if i != "nearest"] + ["nearest"]:     # (nearest last: what the yardsticks below compare with)
+        m.interpolation = interp
+        out = vol.iso_outputs(W, H, count_steps=True, normal=False, skip_counters=True)
+        vol.render(cam, W, H, count_steps=True, out=out)
+        torch.cuda.synchronize()
+        marched, skipped = (int(v) for v in out.skip_counters.cpu().numpy().view(np.uint32))
+        info[("iso", interp)] = {"hit_pixels": int((out.flags == N.SVR_PIX_HIT).sum()),
+                                 "coarse_samples": int(out.steps.to(torch.int64).sum()),
+                                 "wave_stretches_marched": marched, "wave_stretches_skipped": skipped,
+                                 "skipped_share": round(skipped / max(marched + skipped, 1), 4)}
     iso_steps = out.steps.clone()
     m.render_mode = "composite"
     res = vol.render(cam, W, H, count_steps=True)
     torch.cuda.synchronize()
-    info["A"] = {"hit_pixels": int((res.flags == N.SVR_PIX_HIT).sum()), "samples": int(res.steps.to(torch.int64).sum()),
+    info[("A", "nearest")] = {"hit_pixels": int((res.flags == N.SVR_PIX_HIT).sum()), "samples": int(res.steps.to(torch.int64).sum()),
                  "pixels_with_iso_steps": int((res.steps == iso_steps).sum())}
     m.render_mode = "lmip"
     res = vol.render(cam, W, H)
     torch.cuda.synchronize()
-    info["B"] = {"hit_pixels": int((res.flags == N.SVR_PIX_HIT).sum())}
+    info[("B", "nearest")] = {"hit_pixels": int((res.flags == N.SVR_PIX_HIT).sum())}
 
     handle = vol.prepare()
     vol._push_transfer_function()
@@ -150,7 +157,9 @@ def main():
     if args.only:
         runs = {k: v for k, v in runs.items() if k in args.only.split(",")}
     for rnd in range(args.rounds):
-        for name, one in runs.items():
+        for name, one, interp in ((n, o, i) for n, o in runs.items() for i in (interps if n != "B" else ("nearest",))):
+            N.check(lib.svr_set_interpolation(handle, N.INTERPOLATIONS[interp]), "svr_set_interpolation")
+
             def calls(k=args.calls, one=one):
                 for _ in range(k):
                     one()
@@ -160,11 +169,12 @@ def main():
             hold = int(max(4.0 * max(call_s) * args.calls, 0.02) / per_cycle)
             gpu_s = [window(calls, hold) / args.calls for _ in range(args.boxes)]
             torch.cuda.synchronize()
-            row = {"case": name, "round": rnd, "call_ms": round(float(np.median(call_s)) * 1e3, 4),
+            row = {"case": name, "interpolation": interp, "round": rnd, "call_ms": round(float(np.median(call_s)) * 1e3, 4),
                    "gpu_ms": round(float(np.median(gpu_s)) * 1e3, 4), "gpu_ms_min": round(min(gpu_s) * 1e3, 4),
                    "gpu_ms_max": round(max(gpu_s) * 1e3, 4), "calls_per_box": args.calls}
-            row.update(info.get("iso" if name.startswith("iso") else name, {}))
+            row.update(info.get(("iso" if name.startswith("iso") else name, interp), {}))
             print(json.dumps(row), flush=True)
+    N.check(lib.svr_set_interpolation(handle, 0), "svr_set_interpolation")
     vol.close()
 
 

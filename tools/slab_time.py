@@ -110,6 +110,8 @@ def main():
     ap.add_argument("--volume-n", type=int, default=1024)
     ap.add_argument("--valu-per-sample", type=float, default=None,
                     help="VALU per sample of slab_kernel's loop, from its ISA (DESIGN.md); omit: no VALU floor")
+    ap.add_argument("--interpolation", default="nearest", choices=("nearest", "linear", "both"),
+                    help="svr_set_interpolation mode of the timed calls; both: nearest and linear alternate, case by case")
     ap.add_argument("--trace-db", default=None, help="attribute the kernels of a traced run instead of timing")
     args = ap.parse_args()
     if args.trace_db:
@@ -130,6 +132,7 @@ def main():
     torch.cuda.synchronize()
     stream = torch.cuda.current_stream(dev)
     lib = N.lib()
+    interps = ("nearest", "linear") if args.interpolation == "both" else (args.interpolation,)
 
     def window(calls, hold_cycles=0):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -167,7 +170,7 @@ def main():
 
         ob_slice, ob_slab = outputs(res_slice), outputs(res)
         foot = {}
-        for kind, s, n, mode, routing in cases():
+        for kind, s, n, mode, routing, interp in ((*c, i) for c in cases() for i in interps):
             if s == "oblique":
                 origin, (u, v, w) = focus, OBLIQUE
             else:
@@ -195,6 +198,7 @@ def main():
                     N.check(fn(*argv), name)
 
             N.check(lib.svr_set_variant(handle, {"default": 0, "rows": 0x100, "copy": 0x200}[routing]), "svr_set_variant")
+            N.check(lib.svr_set_interpolation(handle, N.INTERPOLATIONS[interp]), "svr_set_interpolation")
             calls(20)
             call_s = [window(calls) / args.calls for _ in range(args.boxes)]
             hold = int(max(4.0 * max(call_s) * args.calls, 0.02) / per_cycle)
@@ -202,7 +206,7 @@ def main():
             torch.cuda.synchronize()
             read = texels * (es + (4 if vol._rings.labels else 0))
             row = {"storage": vol._rings.density_storage, "kind": kind, "slab": s, "samples": n, "mode": mode,
-                   "routing": routing, "call_us": round(float(np.median(call_s)) * 1e6, 2),
+                   "routing": routing, "interpolation": interp, "call_us": round(float(np.median(call_s)) * 1e6, 2),
                    "gpu_us": round(float(np.median(gpu_s)) * 1e6, 2), "calls_per_box": args.calls,
                    "samples_inside": inside, "bytes_written": written, "bytes_read_floor": read,
                    "bytes_floor_us": round((written + read) / HBM_ACHIEVABLE * 1e6, 2)}
@@ -210,6 +214,7 @@ def main():
                 row["valu_floor_us"] = round(inside / 64 * args.valu_per_sample * VALU_NS_PER_WAVE_INSTR / SIMDS / 1e3, 2)
             print(json.dumps(row), flush=True)
         N.check(lib.svr_set_variant(handle, 0), "svr_set_variant")
+        N.check(lib.svr_set_interpolation(handle, 0), "svr_set_interpolation")
         vol.close()
         del vol, res, res_slice
 

@@ -92,6 +92,8 @@ def main():
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--boxes", type=int, default=5)
     ap.add_argument("--volume-n", type=int, default=1024)
+    ap.add_argument("--interpolation", default="nearest", choices=("nearest", "linear", "both"),
+                    help="svr_set_interpolation mode of the timed calls; both: nearest and linear alternate, case by case")
     ap.add_argument("--trace-db", default=None, help="attribute the kernels of a traced run instead of timing")
     args = ap.parse_args()
     if args.trace_db:
@@ -112,6 +114,7 @@ def main():
     torch.cuda.synchronize()
     stream = torch.cuda.current_stream(dev)
     lib = N.lib()
+    interps = ("nearest", "linear") if args.interpolation == "both" else (args.interpolation,)
 
     def window(calls, hold_cycles=0):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -157,8 +160,9 @@ def main():
                 for _ in range(k):
                     N.check(lib.svr_slice(*argv), "svr_slice")
 
-            for routing, variant in zip(ROUTINGS, (0, 0x100, 0x200)):
+            for routing, variant, interp in ((r, x, i) for r, x in zip(ROUTINGS, (0, 0x100, 0x200)) for i in interps):
                 N.check(lib.svr_set_variant(handle, variant), "svr_set_variant")
+                N.check(lib.svr_set_interpolation(handle, N.INTERPOLATIONS[interp]), "svr_set_interpolation")
                 calls(20)                                             # warm-up
                 call_s = [window(calls) / args.calls for _ in range(args.boxes)]
                 hold = int(max(4.0 * max(call_s) * args.calls, 0.02) / per_cycle)
@@ -166,7 +170,7 @@ def main():
                 torch.cuda.synchronize()
                 call_us, gpu_us = float(np.median(call_s)) * 1e6, float(np.median(gpu_s)) * 1e6
                 written = W * H * (16 + 4 + 4 + 1 + 4 + 1)
-                print(json.dumps({"storage": vol._rings.density_storage, "plane": name, "routing": routing,
+                print(json.dumps({"storage": vol._rings.density_storage, "plane": name, "routing": routing, "interpolation": interp,
                                   "call_us": round(call_us, 2), "gpu_us": round(gpu_us, 2),
                                   "call_us_boxes": [round(t * 1e6, 2) for t in call_s],
                                   "gpu_us_boxes": [round(t * 1e6, 2) for t in gpu_s],
@@ -174,6 +178,7 @@ def main():
                                   "write_share_of_6.3TBps_at_gpu_us": round(written / (gpu_us * 1e-6) / HBM_ACHIEVABLE, 3),
                                   "bytes_read_lower_bound": read, "hits": int((res.flags == 2).sum())}), flush=True)
         N.check(lib.svr_set_variant(handle, 0), "svr_set_variant")
+        N.check(lib.svr_set_interpolation(handle, 0), "svr_set_interpolation")
         vol.close()
         del vol, res
 
