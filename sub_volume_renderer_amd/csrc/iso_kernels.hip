@@ -11,19 +11,14 @@
 // a wave leaves the loop when no lane is live.  Refinement, gradient and shading run once per wave, after the loop.
 //
 // Arithmetic contract: strict IEEE f32 without contraction (-ffp-contract=off), operation order as written in svr.h.
-// The device helpers below are copies of the march's (march_kernel.hip) as composite_kernels.hip restates them; the
-// march sources are the kernel-source stamp bench.py records and stay untouched.  tests/test_gpu_iso.py holds this
-// kernel to tests/iso_twin.py.
-#include <math.h>
-#include <string.h>
-
-#include "svr_internal.h"
+// Ray set-up, LOD test and the small helpers are ray_common.h's; tests/test_gpu_iso.py holds this kernel to
+// tests/iso_twin.py.
+#include "ray_common.h"
 #include "linear_sample.h"
 
 namespace {
 
-struct f3 { float x, y, z; };
-struct f4 { float x, y, z, w; };
+using namespace svr_common;
 
 struct IsoLod {
     const void*     density;   // ring [z][y][x], element type per the kernel's ESH
@@ -72,143 +67,6 @@ struct IsoParams {
     uint32_t* counters;
     IsoLod L[SVR_MAX_LODS];
 };
-
-// march_kernel.hip `mat_vec`
-__device__ __forceinline__ f4 mat_vec(const float* m, float x, float y, float z, float w) {
-    f4 r;
-    r.x = ((m[0] * x + m[4] * y) + m[8]  * z) + m[12] * w;
-    r.y = ((m[1] * x + m[5] * y) + m[9]  * z) + m[13] * w;
-    r.z = ((m[2] * x + m[6] * y) + m[10] * z) + m[14] * w;
-    r.w = ((m[3] * x + m[7] * y) + m[11] * z) + m[15] * w;
-    return r;
-}
-
-__device__ __forceinline__ float dot3(f3 a, f3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-
-// march_kernel.hip `wrap`
-__device__ __forceinline__ uint32_t wrap(uint32_t t, uint32_t wrap0, uint32_t ring) {
-    const uint32_t w = t + wrap0;
-    return min(w, w - ring);
-}
-
-// march_kernel.hip `lod_texel` (sample_vol.wgsl:4-25), with a 64-bit element index (a float ring can exceed 4 GiB)
-__device__ __forceinline__ bool lod_index(const IsoLod& L, float dx, float dy, float dz, size_t& idx) {
-    const float sx = dx * L.scale[0], sy = dy * L.scale[1], sz = dz * L.scale[2];
-    const int ix = (int)sx, iy = (int)sy, iz = (int)sz;
-    const uint32_t tx = (uint32_t)(ix - L.off[0]), ty = (uint32_t)(iy - L.off[1]), tz = (uint32_t)(iz - L.off[2]);
-    if (!(tx < L.shape[0] && ty < L.shape[1] && tz < L.shape[2])) return false;
-    const uint32_t wx = wrap(tx, L.wrap0[0], L.ring[0]);
-    const uint32_t wy = wrap(ty, L.wrap0[1], L.ring[1]);
-    const uint32_t wz = wrap(tz, L.wrap0[2], L.ring[2]);
-    idx = ((size_t)wz * L.ring[1] + wy) * (size_t)L.ring[0] + wx;
-    return true;
-}
-
-// march_kernel.hip `pick_field`
-__device__ __forceinline__ uint32_t pick_field(float c) {
-    const float f = c * 16383.0f;
-    uint32_t u = 0u;
-    if (f > 0.0f) u = f >= 4294967296.0f ? 0xFFFFFFFFu : (uint32_t)f;
-    return min(u, 16383u);
-}
-
-// march_kernel.hip `hsv_to_rgb` (hsv_selection.wgsl:7-41)
-__device__ __forceinline__ f3 hsv_to_rgb(float h, float s, float v) {
-    f3 r;
-    if (s == 0.0f) { r.x = v; r.y = v; r.z = v; return r; }
-    const float h_scaled = h * 6.0f;
-    const float fl = floorf(h_scaled);
-    const int sector = (int)fl;
-    const float fr = h_scaled - fl;
-    const float p = v * (1.0f - s);
-    const float q = v * (1.0f - s * fr);
-    const float t = v * (1.0f - s * (1.0f - fr));
-    if (sector == 0)      { r.x = v; r.y = t; r.z = p; }
-    else if (sector == 1) { r.x = q; r.y = v; r.z = p; }
-    else if (sector == 2) { r.x = p; r.y = v; r.z = t; }
-    else if (sector == 3) { r.x = p; r.y = q; r.z = v; }
-    else if (sector == 4) { r.x = t; r.y = p; r.z = v; }
-    else                  { r.x = v; r.y = p; r.z = q; }
-    return r;
-}
-
-struct Ray {
-    f3 start, step;
-    int nsteps;
-};
-
-// march_kernel.hip `setup_ray` (vs_main.wgsl:36-47 + fs_main.wgsl:20-48) for the pixel (i, j) of the full frame.
-// Returns false when no fragment runs for this pixel (discard).
-__device__ __forceinline__ bool setup_ray(const IsoParams& P, int i, int j, Ray& R) {
-    const float W = (float)P.frame.frame_w, H = (float)P.frame.frame_h;
-    const float px = (2.0f * ((float)i + 0.5f)) / W - 1.0f;
-    const float py = 1.0f - (2.0f * ((float)j + 0.5f)) / H;
-    const f4 n4 = mat_vec(P.ndc_to_data, px, py, -1.0f, 1.0f);
-    const f4 f4_ = mat_vec(P.ndc_to_data, px, py, 1.0f, 1.0f);
-    const f3 far_pos  = { f4_.x / f4_.w, f4_.y / f4_.w, f4_.z / f4_.w };
-    const f3 near_pos = { n4.x / n4.w, n4.y / n4.w, n4.z / n4.w };
-    const f3 dir = { far_pos.x - near_pos.x, far_pos.y - near_pos.y, far_pos.z - near_pos.z };
-    const float len = sqrtf(dot3(dir, dir));
-    const f3 ray = { dir.x / len, dir.y / len, dir.z / len };
-
-    const float lo = -0.5f;
-    const float hx = P.size[0] - 0.5f, hy = P.size[1] - 0.5f, hz = P.size[2] - 0.5f;
-    const float tx1 = (lo - near_pos.x) / ray.x, tx2 = (hx - near_pos.x) / ray.x;
-    const float ty1 = (lo - near_pos.y) / ray.y, ty2 = (hy - near_pos.y) / ray.y;
-    const float tz1 = (lo - near_pos.z) / ray.z, tz2 = (hz - near_pos.z) / ray.z;
-    const float t_exit  = fminf(fminf(fmaxf(tx1, tx2), fmaxf(ty1, ty2)), fmaxf(tz1, tz2));
-    const float t_enter = fmaxf(fmaxf(fminf(tx1, tx2), fminf(ty1, ty2)), fminf(tz1, tz2));
-    if (!(t_enter <= t_exit)) return false;
-    const f3 back = { near_pos.x + ray.x * t_exit, near_pos.y + ray.y * t_exit, near_pos.z + ray.z * t_exit };
-    const f4 bw = mat_vec(P.world, back.x, back.y, back.z, 1.0f);
-    const f4 bc = mat_vec(P.pc, bw.x, bw.y, bw.z, bw.w);
-    if (!(bc.w > 0.0f) || !(bc.z >= 0.0f) || !(bc.z <= bc.w)) return false;
-    if (P.clip_count) {
-        const bool all = P.clip_all != 0;
-        bool clipped = all;
-        for (uint32_t k = 0; k < P.clip_count; ++k) {
-            const bool behind = ((bw.x * P.clip[k][0] + bw.y * P.clip[k][1]) + bw.z * P.clip[k][2]) < P.clip[k][3];
-            clipped = all ? (clipped && behind) : (clipped || behind);
-        }
-        if (clipped) return false;
-    }
-
-    const f3 nb = { near_pos.x - back.x, near_pos.y - back.y, near_pos.z - back.z };
-    float dist = dot3(nb, ray);
-    dist = fmaxf(dist, fminf((-0.5f - back.x) / ray.x, (P.size[0] - 0.5f - back.x) / ray.x));
-    dist = fmaxf(dist, fminf((-0.5f - back.y) / ray.y, (P.size[1] - 0.5f - back.y) / ray.y));
-    dist = fmaxf(dist, fminf((-0.5f - back.z) / ray.z, (P.size[2] - 0.5f - back.z) / ray.z));
-    const f3 front = { back.x + ray.x * dist, back.y + ray.y * dist, back.z + ray.z * dist };
-    float nf = -dist / P.rel_step + 0.5f;
-    if (!(nf >= 1.0f)) return false;
-    if (nf > 16777216.0f) nf = 16777216.0f;
-    R.nsteps = (int)nf;
-    const float nstepsf = (float)R.nsteps;
-    R.start = { (front.x + 0.5f) / P.size[0], (front.y + 0.5f) / P.size[1], (front.z + 0.5f) / P.size[2] };
-    R.step = { ((back.x - front.x) / P.size[0]) / nstepsf,
-               ((back.y - front.y) / P.size[1]) / nstepsf,
-               ((back.z - front.z) / P.size[2]) / nstepsf };
-    return true;
-}
-
-// march_kernel.hip `xcd_remap`: workgroups b and b + 8 share an XCD; each XCD gets one contiguous run of tiles
-__device__ __forceinline__ int xcd_remap(int b, int nblocks) {
-    const int per = nblocks >> 3;
-    const int body = per << 3;
-    if (b >= body) return b;
-    return (b & 7) * per + (b >> 3);
-}
-
-// a texel at a byte address known to be in global memory (slice_kernels.hip `load_global`)
-template <int ESH>
-__device__ __forceinline__ float load_global(const char* a) {
-    typedef __attribute__((address_space(1))) const uint8_t G8;
-    typedef __attribute__((address_space(1))) const uint16_t G16;
-    typedef __attribute__((address_space(1))) const float G32;
-    if (ESH == 0) return (float)*(G8*)a;
-    if (ESH == 1) return (float)*(G16*)a;
-    return *(G32*)a;
-}
 
 using IsoArgs = const IsoParams __attribute__((address_space(4)));     // the kernel arguments' own address space
 
@@ -540,36 +398,6 @@ __global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
     if (P.normal) { P.normal[3 * o] = n.x; P.normal[3 * o + 1] = n.y; P.normal[3 * o + 2] = n.z; }
 }
 
-template <int NL, bool LIN>
-hipError_t launch_nl(const IsoParams& P, int esh, dim3 grid, hipStream_t stream) {
-    if (esh == 0)      hipLaunchKernelGGL((iso_kernel<NL, 0, LIN>), grid, dim3(256), 0, stream, P);
-    else if (esh == 1) hipLaunchKernelGGL((iso_kernel<NL, 1, LIN>), grid, dim3(256), 0, stream, P);
-    else               hipLaunchKernelGGL((iso_kernel<NL, 2, LIN>), grid, dim3(256), 0, stream, P);
-    return hipGetLastError();
-}
-
-template <bool LIN>
-hipError_t launch_iso(const IsoParams& P, int num_lods, int esh, dim3 grid, hipStream_t stream) {
-    switch (num_lods) {
-        case 1: return launch_nl<1, LIN>(P, esh, grid, stream);
-        case 2: return launch_nl<2, LIN>(P, esh, grid, stream);
-        case 3: return launch_nl<3, LIN>(P, esh, grid, stream);
-        case 4: return launch_nl<4, LIN>(P, esh, grid, stream);
-        case 5: return launch_nl<5, LIN>(P, esh, grid, stream);
-        case 6: return launch_nl<6, LIN>(P, esh, grid, stream);
-        case 7: return launch_nl<7, LIN>(P, esh, grid, stream);
-        default: return launch_nl<8, LIN>(P, esh, grid, stream);
-    }
-}
-
-// f32 matrix helpers in the contract's operation order (svr_api.hip's)
-void mat_vec4(const float* m, const float* v, float* r) {
-    for (int i = 0; i < 4; ++i) r[i] = ((m[0 + i] * v[0] + m[4 + i] * v[1]) + m[8 + i] * v[2]) + m[12 + i] * v[3];
-}
-void mat_mul4(const float* a, const float* b, float* out) {
-    for (int c = 0; c < 4; ++c) mat_vec4(a, b + 4 * c, out + 4 * c);
-}
-
 }  // namespace
 
 // Declared in svr_api.hip, which validates the arguments, orders the launch against the uploads and marks it as a
@@ -578,30 +406,13 @@ hipError_t svr_launch_iso(const svr_ctx* c, const svr_camera& cam, const svr_fra
                           const svr_outputs& out, int interp, hipStream_t stream) {
     IsoParams P;
     memset(&P, 0, sizeof(P));
-    float tmp[16];
-    mat_mul4(cam.world_inv, cam.cam_inv, tmp);               // as svr_render (vs_main.wgsl:22, left-assoc)
-    mat_mul4(tmp, cam.proj_inv, P.ndc_to_data);
-    mat_mul4(cam.proj, cam.cam, P.pc);
-    memcpy(P.world, cam.world, sizeof(P.world));
+    fill_ray_params(c, cam, fr, out, P);
     memcpy(P.world_inv, cam.world_inv, sizeof(P.world_inv));
-    for (int a = 0; a < 3; ++a) P.size[a] = cam.volume_dimensions[a];
-    const float mx = fmaxf(P.size[0], fmaxf(P.size[1], P.size[2]));
-    P.rel_step = fminf(fmaxf(sqrtf(mx) / 20.0f, 0.1f), 0.8f);   // fs_main.wgsl:20
-    P.frame = fr;
-    const svr_material& m = c->material;
-    P.opacity = m.opacity;
-    P.clip_count = m.clipping_plane_count; P.clip_all = m.clipping_mode_all;
-    for (uint32_t k = 0; k < m.clipping_plane_count; ++k)
-        for (int a = 0; a < 4; ++a) P.clip[k][a] = c->clip_host[4 * k + a];
-    P.color_count = m.color_count; P.colors = c->colors_dev;
     P.iso = ip.iso_value; P.refine = ip.refine;
     for (int a = 0; a < 3; ++a) { P.base[a] = ip.iso_color[a]; P.light[a] = ip.light_direction[a]; }
-    P.tint = ip.color_by_label != 0 && m.color_count > 0;
+    P.tint = ip.color_by_label != 0 && c->material.color_count > 0;
     P.ambient = ip.ambient; P.diffuse = ip.diffuse; P.specular = ip.specular;
     P.shininess_log2 = ip.shininess_log2; P.headlight = ip.headlight != 0;
-    P.tiles_x = (fr.out_w + 15) / 16; P.tiles_y = (fr.out_h + 15) / 16;
-    P.rgba = out.rgba; P.depth = out.depth; P.label = out.label; P.flags = out.flags; P.steps = out.steps;
-    P.pick = reinterpret_cast<unsigned long long*>(out.pick); P.pick_id = out.pick_id;
     P.normal = ip.normal; P.counters = ip.skip_counters;
     // The cell test compares a maximum converted like a sample ((float) of u8 / u16 is exact) with iso_value itself, so
     // it is exact for integer rings.  Float rings keep max |v|: an upper bound of v, a proof only while iso_value > 0.
@@ -610,22 +421,17 @@ hipError_t svr_launch_iso(const svr_ctx* c, const svr_camera& cam, const svr_fra
     for (int l = 0; l < c->num_lods; ++l) {
         const LodStorage& S = c->lod[l];
         IsoLod& Q = P.L[l];
-        Q.density = S.density; Q.labels = S.labels;
+        fill_lod_common(S, Q);
         Q.cells = c->cells_dil_all ? S.cells_dil : nullptr;
         any_cells = any_cells || Q.cells;
         Q.cshift = S.cshift;
-        for (int a = 0; a < 3; ++a) {
-            Q.off[a] = S.state.offset[a];
-            Q.shape[a] = (uint32_t)S.state.shape[a];
-            Q.ring[a] = (uint32_t)S.ring[a];
-            Q.wrap0[a] = (uint32_t)(S.state.offset[a] % S.ring[a]);     // (svr_set_lod_state: offsets are >= 0)
-            Q.scale[a] = S.state.scale[a];
-            Q.cdim[a] = (uint32_t)S.cdim[a];
-        }
+        for (int a = 0; a < 3; ++a) Q.cdim[a] = (uint32_t)S.cdim[a];
     }
     P.skip = any_cells && !ip.no_skip && ip.iso_value > 0.0f;
-    const int esh = c->density_storage == SVR_U8 ? 0 : (c->density_storage == SVR_U16 ? 1 : 2);
     const dim3 grid((unsigned)(P.tiles_x * P.tiles_y));
-    return interp == SVR_INTERP_LINEAR ? launch_iso<true>(P, c->num_lods, esh, grid, stream)
-                                       : launch_iso<false>(P, c->num_lods, esh, grid, stream);
+    return with_bool(interp == SVR_INTERP_LINEAR, [&](auto lin) {
+        return with_lods_esh(c->num_lods, esh_of(c), [&](auto nl, auto esh) {
+            return launch_tiles(iso_kernel<nl(), esh(), lin()>, grid, 0, stream, P);
+        });
+    });
 }

@@ -10,9 +10,11 @@
 // are not repeated per LOD of the cascade.
 #pragma once
 
-#include "svr_internal.h"
+#include "ray_common.h"
 
 namespace svr_linear {
+
+using svr_common::wrap;
 
 // What a cell needs from the LOD that holds the sample, per lane.  The zero state (no LOD holds the sample) gives the
 // eight corners the element offset 0: a gather nobody reads, from a valid address.
@@ -45,12 +47,6 @@ struct Cell {
     uint32_t w0[3], w1[3];     // ring slots of the lower / upper corner per axis (clamped to the window, then wrapped)
     float    f[3];
 };
-
-// march_kernel.hip `wrap`: t in [0, shape), wrap0 in [0, ring) -> (t + wrap0) mod ring
-__device__ __forceinline__ uint32_t wrap(uint32_t t, uint32_t wrap0, uint32_t ring) {
-    const uint32_t w = t + wrap0;
-    return min(w, w - ring);
-}
 
 __device__ __forceinline__ Cell cell_of(const LaneLod& q) {
     Cell c;

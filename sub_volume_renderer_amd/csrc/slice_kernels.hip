@@ -3,15 +3,14 @@
 // so that planes that are not x-normal still share L2 lines between neighbouring lanes.  No LDS.
 //
 // Arithmetic contract: strict IEEE f32 without contraction (-ffp-contract=off), operation order as written in svr.h.
-// The device helpers below are copies of the march's (march_kernel.hip), whose bytes are the kernel-source stamp
-// bench.py records and stay untouched; tests/test_gpu_slice.py holds both to the same numpy restatement.
-#include <math.h>
-#include <string.h>
-
-#include "svr_internal.h"
+// LOD test and the small helpers are ray_common.h's; tests/test_gpu_slice.py holds this kernel and the march to the same
+// numpy restatement.
+#include "ray_common.h"
 #include "linear_sample.h"
 
 namespace {
+
+using namespace svr_common;
 
 struct SliceLod {
     const void*     density;   // ring [z][y][x], element type per SliceParams::esh
@@ -43,48 +42,6 @@ struct SliceParams {
     SliceLod L[SVR_MAX_LODS];
 };
 
-struct f3 { float x, y, z; };
-
-// march_kernel.hip `wrap`: t in [0, shape), wrap0 in [0, ring) -> (t + wrap0) mod ring
-__device__ __forceinline__ uint32_t wrap(uint32_t t, uint32_t wrap0, uint32_t ring) {
-    const uint32_t w = t + wrap0;
-    return min(w, w - ring);
-}
-
-// march_kernel.hip `lod_texel` (sample_vol.wgsl:4-25), with the ring slot returned instead of a 32-bit-row index: the
-// caller forms a 64-bit element index (a float ring can exceed 4 GiB)
-__device__ __forceinline__ bool lod_slot(const SliceLod& L, float dx, float dy, float dz, uint32_t& wx, uint32_t& wy,
-                                         uint32_t& wz) {
-    const float sx = dx * L.scale[0], sy = dy * L.scale[1], sz = dz * L.scale[2];
-    const int ix = (int)sx, iy = (int)sy, iz = (int)sz;
-    const uint32_t tx = (uint32_t)(ix - L.off[0]), ty = (uint32_t)(iy - L.off[1]), tz = (uint32_t)(iz - L.off[2]);
-    if (!(tx < L.shape[0] && ty < L.shape[1] && tz < L.shape[2])) return false;
-    wx = wrap(tx, L.wrap0[0], L.ring[0]);
-    wy = wrap(ty, L.wrap0[1], L.ring[1]);
-    wz = wrap(tz, L.wrap0[2], L.ring[2]);
-    return true;
-}
-
-// march_kernel.hip `hsv_to_rgb` (hsv_selection.wgsl:7-41)
-__device__ __forceinline__ f3 hsv_to_rgb(float h, float s, float v) {
-    f3 r;
-    if (s == 0.0f) { r.x = v; r.y = v; r.z = v; return r; }
-    const float h_scaled = h * 6.0f;
-    const float fl = floorf(h_scaled);
-    const int sector = (int)fl;
-    const float fr = h_scaled - fl;
-    const float p = v * (1.0f - s);
-    const float q = v * (1.0f - s * fr);
-    const float t = v * (1.0f - s * (1.0f - fr));
-    if (sector == 0)      { r.x = v; r.y = t; r.z = p; }
-    else if (sector == 1) { r.x = q; r.y = v; r.z = p; }
-    else if (sector == 2) { r.x = p; r.y = v; r.z = t; }
-    else if (sector == 3) { r.x = p; r.y = q; r.z = v; }
-    else if (sector == 4) { r.x = t; r.y = p; r.z = v; }
-    else                  { r.x = v; r.y = p; r.z = q; }
-    return r;
-}
-
 // march_kernel.hip `srgb2physical` (pygfx std.wgsl, restated)
 __device__ __forceinline__ float srgb2physical(float c) {
     const float f = powf((c + 0.055f) / 1.055f, 2.4f);
@@ -97,18 +54,6 @@ __device__ __forceinline__ float load_texel(const void* base, size_t i) {
     if (ESH == 0) return (float)static_cast<const uint8_t*>(base)[i];
     if (ESH == 1) return (float)static_cast<const uint16_t*>(base)[i];
     return static_cast<const float*>(base)[i];
-}
-
-// a texel at a byte address known to be in global memory (global_load rather than flat_load: the ring pointers come
-// from the kernel arguments through a pointer the compiler cannot see into)
-template <int ESH>
-__device__ __forceinline__ float load_global(const char* a) {
-    typedef __attribute__((address_space(1))) const uint8_t G8;
-    typedef __attribute__((address_space(1))) const uint16_t G16;
-    typedef __attribute__((address_space(1))) const float G32;
-    if (ESH == 0) return (float)*(G8*)a;
-    if (ESH == 1) return (float)*(G16*)a;
-    return *(G32*)a;
 }
 
 // LIN: the linear sample of svr.h (svr_set_interpolation) in place of the nearest texel; label and lod stay the
@@ -204,28 +149,6 @@ __global__ __launch_bounds__(256) void slice_kernel(const SliceParams P) {
     if (P.flags) P.flags[o] = cls;
     if (P.value) P.value[o] = value;
     if (P.lod) P.lod[o] = lod;
-}
-
-template <int NL, bool LIN>
-hipError_t launch_nl(const SliceParams& P, int esh, dim3 grid, hipStream_t stream) {
-    if (esh == 0) hipLaunchKernelGGL((slice_kernel<NL, 0, LIN>), grid, dim3(256), 0, stream, P);
-    else if (esh == 1) hipLaunchKernelGGL((slice_kernel<NL, 1, LIN>), grid, dim3(256), 0, stream, P);
-    else hipLaunchKernelGGL((slice_kernel<NL, 2, LIN>), grid, dim3(256), 0, stream, P);
-    return hipGetLastError();
-}
-
-template <bool LIN>
-hipError_t launch_slice(const SliceParams& P, int num_lods, dim3 grid, hipStream_t stream) {
-    switch (num_lods) {
-        case 1: return launch_nl<1, LIN>(P, P.esh, grid, stream);
-        case 2: return launch_nl<2, LIN>(P, P.esh, grid, stream);
-        case 3: return launch_nl<3, LIN>(P, P.esh, grid, stream);
-        case 4: return launch_nl<4, LIN>(P, P.esh, grid, stream);
-        case 5: return launch_nl<5, LIN>(P, P.esh, grid, stream);
-        case 6: return launch_nl<6, LIN>(P, P.esh, grid, stream);
-        case 7: return launch_nl<7, LIN>(P, P.esh, grid, stream);
-        default: return launch_nl<8, LIN>(P, P.esh, grid, stream);
-    }
 }
 
 // ---- thick slabs (svr_slab, include/svr.h): N samples per pixel along the data-space step dw, reduced to one.
@@ -406,28 +329,6 @@ __global__ __launch_bounds__(256) void slab_kernel(const SlabParams Q) {
     if (P.lod) P.lod[o] = lod;
 }
 
-template <int NL, bool POW2, bool LIN>
-hipError_t launch_slab_nl(const SlabParams& Q, dim3 grid, hipStream_t stream) {
-    if (Q.S.esh == 0) hipLaunchKernelGGL((slab_kernel<NL, 0, POW2, LIN>), grid, dim3(256), 0, stream, Q);
-    else if (Q.S.esh == 1) hipLaunchKernelGGL((slab_kernel<NL, 1, POW2, LIN>), grid, dim3(256), 0, stream, Q);
-    else hipLaunchKernelGGL((slab_kernel<NL, 2, POW2, LIN>), grid, dim3(256), 0, stream, Q);
-    return hipGetLastError();
-}
-
-template <bool POW2, bool LIN = false>
-hipError_t launch_slab(const SlabParams& Q, int num_lods, dim3 grid, hipStream_t stream) {
-    switch (num_lods) {
-        case 1: return launch_slab_nl<1, POW2, LIN>(Q, grid, stream);
-        case 2: return launch_slab_nl<2, POW2, LIN>(Q, grid, stream);
-        case 3: return launch_slab_nl<3, POW2, LIN>(Q, grid, stream);
-        case 4: return launch_slab_nl<4, POW2, LIN>(Q, grid, stream);
-        case 5: return launch_slab_nl<5, POW2, LIN>(Q, grid, stream);
-        case 6: return launch_slab_nl<6, POW2, LIN>(Q, grid, stream);
-        case 7: return launch_slab_nl<7, POW2, LIN>(Q, grid, stream);
-        default: return launch_slab_nl<8, POW2, LIN>(Q, grid, stream);
-    }
-}
-
 // 128-byte lines a 16 x 4 wave tile touches, estimated from the bounding box of its footprint in ring voxels (extent
 // e per axis) for a layout of b-voxel lines: prod(e_k / b_k + 1), at most one per lane (cap 64; a slab's N gathers: 64 N)
 float lines_per_tile(const float e[3], float bx, float by, float bz, float cap = 64.0f) {
@@ -453,25 +354,13 @@ void fill_slice_params(const svr_ctx* c, const svr_slice_plane& pl, const svr_fr
     P.clim0 = m.clim[0]; P.clim1 = m.clim[1]; P.gamma = m.gamma; P.opacity = m.opacity;
     P.colorspace_srgb = m.colorspace_srgb;
     P.color_count = m.color_count; P.colors = c->colors_dev;
-    P.esh = c->density_storage == SVR_U8 ? 0 : (c->density_storage == SVR_U16 ? 1 : 2);
+    P.esh = esh_of(c);
     P.rgba = out.rgba; P.depth = out.depth; P.label = out.label; P.flags = out.flags; P.value = out.value; P.lod = out.lod;
     for (int k = 0; k < 3; ++k) {
         du[k] = (pl.world_inv[k] * pl.u[0] + pl.world_inv[4 + k] * pl.u[1]) + pl.world_inv[8 + k] * pl.u[2];
         dv[k] = (pl.world_inv[k] * pl.v[0] + pl.world_inv[4 + k] * pl.v[1]) + pl.world_inv[8 + k] * pl.v[2];
     }
-    for (int l = 0; l < c->num_lods; ++l) {
-        const LodStorage& S = c->lod[l];
-        SliceLod& Q = P.L[l];
-        Q.density = S.density; Q.labels = S.labels;
-        for (int a = 0; a < 3; ++a) {
-            Q.off[a] = S.state.offset[a];
-            Q.shape[a] = (uint32_t)S.state.shape[a];
-            Q.ring[a] = (uint32_t)S.ring[a];
-            Q.wrap0[a] = (uint32_t)(S.state.offset[a] % S.ring[a]);     // (svr_set_lod_state: offsets are >= 0)
-            Q.scale[a] = S.state.scale[a];
-        }
-        Q.twin = nullptr;
-    }
+    for (int l = 0; l < c->num_lods; ++l) fill_lod_common(c->lod[l], P.L[l]);     // (twin stays null: the launchers route)
 }
 
 // 128-byte lines of the micro-block copy / of the rows that a footprint of extent e (ring voxels) touches
@@ -505,8 +394,11 @@ hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const s
         }
     }
     const dim3 grid((unsigned)((fr.out_w + 15) / 16), (unsigned)((fr.out_h + 15) / 16));
-    return interp == SVR_INTERP_LINEAR ? launch_slice<true>(P, c->num_lods, grid, stream)
-                                       : launch_slice<false>(P, c->num_lods, grid, stream);
+    return with_bool(interp == SVR_INTERP_LINEAR, [&](auto lin) {
+        return with_lods_esh(c->num_lods, P.esh, [&](auto nl, auto esh) {
+            return launch_tiles(slice_kernel<nl(), esh(), lin()>, grid, 0, stream, P);
+        });
+    });
 }
 
 // Declared in svr_api.hip, like svr_launch_slice; svr_slab has validated the arguments and computed dw.
@@ -552,6 +444,13 @@ hipError_t svr_launch_slab(const svr_ctx* c, const svr_slab_params& sp, const fl
         pow2 = pow2 && mant == 0.5f && e2 <= 25;
     }
     const dim3 grid((unsigned)((fr.out_w + 15) / 16), (unsigned)((fr.out_h + 15) / 16));
-    if (interp == SVR_INTERP_LINEAR) return launch_slab<false, true>(Q, c->num_lods, grid, stream);   // the general chain
-    return pow2 ? launch_slab<true>(Q, c->num_lods, grid, stream) : launch_slab<false>(Q, c->num_lods, grid, stream);
+    if (interp == SVR_INTERP_LINEAR)                                                          // the general chain
+        return with_lods_esh(c->num_lods, Q.S.esh, [&](auto nl, auto esh) {
+            return launch_tiles(slab_kernel<nl(), esh(), false, true>, grid, 0, stream, Q);
+        });
+    return with_bool(pow2, [&](auto p2) {
+        return with_lods_esh(c->num_lods, Q.S.esh, [&](auto nl, auto esh) {
+            return launch_tiles(slab_kernel<nl(), esh(), p2(), false>, grid, 0, stream, Q);
+        });
+    });
 }

@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "svr_internal.h"
+#include "ray_common.h"
 #include "ring_parts.h"
 #include "march_pow2.h"
 
@@ -28,13 +29,8 @@ void svr_set_error(const std::string& msg) { g_err = msg; }
 
 namespace {
 
-// f32 matrix helpers in the contract's operation order (see oracle/lmip_oracle.c header)
-void mat_vec4(const float* m, const float* v, float* r) {
-    for (int i = 0; i < 4; ++i) r[i] = ((m[0 + i] * v[0] + m[4 + i] * v[1]) + m[8 + i] * v[2]) + m[12 + i] * v[3];
-}
-void mat_mul4(const float* a, const float* b, float* out) {
-    for (int c = 0; c < 4; ++c) mat_vec4(a, b + 4 * c, out + 4 * c);
-}
+using svr_common::mat_mul4;
+using svr_common::mat_vec4;
 
 int floor_div(int a, int b) { int q = a / b, r = a % b; return (r != 0 && ((r < 0) != (b < 0))) ? q - 1 : q; }
 
@@ -1195,33 +1191,53 @@ int svr_time_render(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, cons
     return SVR_OK;
 }
 
+// What svr_slice, svr_slab, svr_composite and svr_iso check first, in this order (who: the entry point's name, the
+// prefix of its error texts; args_ok: its own null test), and the frame with band_h defaulted to one band.
+static int draw_prologue(const char* who, bool args_ok, const svr_ctx* c, const svr_frame* fr, svr_frame& f) {
+    const std::string w(who);
+    SVR_REQUIRE(args_ok, w + ": null argument");
+    SVR_REQUIRE(c->material_set, w + ": svr_set_material has not been called");
+    SVR_REQUIRE(fr->frame_w > 0 && fr->frame_h > 0 && fr->out_w > 0 && fr->out_h > 0, w + ": empty frame");
+    SVR_REQUIRE(fr->x0 >= 0 && fr->y0 >= 0, w + ": negative tile origin");
+    f = *fr;
+    if (f.band_h <= 0) { f.band_h = fr->out_h; f.band_pitch = fr->out_h; }
+    return SVR_OK;
+}
+
+// ... and what they end with: launch(s) on the caller's stream (NULL = default stream, as in svr_render), ordered like
+// a render: behind the published uploads, and later uploads behind this draw (mark_render).  what: the launch as the
+// error text of a failed one names it.
+extern "C++" template <class Launch>
+static int draw_ordered(svr_ctx* c, void* stream, const char* what, Launch&& launch) {
+    DeviceGuard guard(c->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
+    const hipError_t e = launch(s);
+    if (e != hipSuccess) {
+        svr_set_error(std::string(what) + ": " + hipGetErrorString(e));
+        return SVR_ERR_HIP;
+    }
+    return mark_render(c, s);
+}
+// (the launch is named `s` in `call`; its text is the prefix of a failed launch's error, as SVR_HIP_TRY would form it)
+#define SVR_DRAW_ORDERED(c, stream, call) draw_ordered(c, stream, #call, [&](hipStream_t s) { return call; })
+
 int svr_slice(svr_ctx* c, const svr_slice_plane* plane, const svr_frame* fr, const svr_slice_outputs* out, void* stream) {
-    SVR_REQUIRE(c && plane && fr && out && out->rgba, "svr_slice: null argument");
-    SVR_REQUIRE(c->material_set, "svr_slice: svr_set_material has not been called");
-    SVR_REQUIRE(fr->frame_w > 0 && fr->frame_h > 0 && fr->out_w > 0 && fr->out_h > 0, "svr_slice: empty frame");
-    SVR_REQUIRE(fr->x0 >= 0 && fr->y0 >= 0, "svr_slice: negative tile origin");
+    svr_frame f;
+    { const int rc = draw_prologue("svr_slice", c && plane && fr && out && out->rgba, c, fr, f); if (rc) return rc; }
     for (int a = 0; a < 3; ++a) {
         SVR_REQUIRE(plane->volume_dimensions[a] >= 1.0f, "svr_slice: volume_dimensions must be >= 1");
         SVR_REQUIRE(isfinite(plane->origin[a]) && isfinite(plane->u[a]) && isfinite(plane->v[a]),
                     "svr_slice: origin, u and v must be finite");
     }
     SVR_REQUIRE((uintptr_t)out->rgba % 16 == 0, "svr_slice: rgba must be 16-byte aligned");
-    svr_frame f = *fr;
-    if (f.band_h <= 0) { f.band_h = fr->out_h; f.band_pitch = fr->out_h; }
     const int twin_mode = (c->variant & 256) ? 0 : ((c->variant & 512) ? 2 : 1);
-    DeviceGuard guard(c->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);         // NULL = default stream, as in svr_render
-    // ordered like a render: behind the published uploads, and later uploads behind this slice (mark_render)
-    if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
-    SVR_HIP_TRY(svr_launch_slice(c, *plane, f, *out, twin_mode, interpolation_of(c), s));
-    return mark_render(c, s);
+    return SVR_DRAW_ORDERED(c, stream, svr_launch_slice(c, *plane, f, *out, twin_mode, interpolation_of(c), s));
 }
 
 int svr_slab(svr_ctx* c, const svr_slab_params* sp, const svr_frame* fr, const svr_slice_outputs* out, void* stream) {
-    SVR_REQUIRE(c && sp && fr && out && out->rgba, "svr_slab: null argument");
-    SVR_REQUIRE(c->material_set, "svr_slab: svr_set_material has not been called");
-    SVR_REQUIRE(fr->frame_w > 0 && fr->frame_h > 0 && fr->out_w > 0 && fr->out_h > 0, "svr_slab: empty frame");
-    SVR_REQUIRE(fr->x0 >= 0 && fr->y0 >= 0, "svr_slab: negative tile origin");
+    svr_frame f;
+    { const int rc = draw_prologue("svr_slab", c && sp && fr && out && out->rgba, c, fr, f); if (rc) return rc; }
     const svr_slice_plane& plane = sp->plane;
     for (int a = 0; a < 3; ++a) {
         SVR_REQUIRE(plane.volume_dimensions[a] >= 1.0f, "svr_slab: volume_dimensions must be >= 1");
@@ -1242,15 +1258,8 @@ int svr_slab(svr_ctx* c, const svr_slab_params* sp, const svr_frame* fr, const s
         SVR_REQUIRE(isfinite(dw[k]), "svr_slab: the data-space step of w must be finite");
     }
     SVR_REQUIRE((uintptr_t)out->rgba % 16 == 0, "svr_slab: rgba must be 16-byte aligned");
-    svr_frame f = *fr;
-    if (f.band_h <= 0) { f.band_h = fr->out_h; f.band_pitch = fr->out_h; }
     const int twin_mode = (c->variant & 256) ? 0 : ((c->variant & 512) ? 2 : 1);
-    DeviceGuard guard(c->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // ordered like svr_slice: behind the published uploads, and later uploads behind this slab (mark_render)
-    if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
-    SVR_HIP_TRY(svr_launch_slab(c, *sp, dw, f, *out, twin_mode, interpolation_of(c), s));
-    return mark_render(c, s);
+    return SVR_DRAW_ORDERED(c, stream, svr_launch_slab(c, *sp, dw, f, *out, twin_mode, interpolation_of(c), s));
 }
 
 int svr_set_transfer_function(svr_ctx* c, const float* rgba, int32_t K) {
@@ -1300,10 +1309,8 @@ int svr_set_interpolation(svr_ctx* c, int mode) {
 
 int svr_composite(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, const svr_composite_params* cp,
                   const svr_outputs* out, void* stream) {
-    SVR_REQUIRE(c && cam && fr && cp && out && out->rgba, "svr_composite: null argument");
-    SVR_REQUIRE(c->material_set, "svr_composite: svr_set_material has not been called");
-    SVR_REQUIRE(fr->frame_w > 0 && fr->frame_h > 0 && fr->out_w > 0 && fr->out_h > 0, "svr_composite: empty frame");
-    SVR_REQUIRE(fr->x0 >= 0 && fr->y0 >= 0, "svr_composite: negative tile origin");
+    svr_frame f;
+    { const int rc = draw_prologue("svr_composite", c && cam && fr && cp && out && out->rgba, c, fr, f); if (rc) return rc; }
     for (int a = 0; a < 3; ++a)
         SVR_REQUIRE(cam->volume_dimensions[a] >= 1.0f, "svr_composite: volume_dimensions must be >= 1");
     SVR_REQUIRE(cp->alpha_cutoff > 0.0f && cp->alpha_cutoff <= 1.0f, "svr_composite: alpha_cutoff must be in (0, 1]");
@@ -1315,22 +1322,13 @@ int svr_composite(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, const 
         if (t) { table = t->dev; K = t->K; interp = t->interp; }
     }
     SVR_REQUIRE(table, "svr_composite: svr_set_transfer_function has not been called");
-    svr_frame f = *fr;
-    if (f.band_h <= 0) { f.band_h = fr->out_h; f.band_pitch = fr->out_h; }
-    DeviceGuard guard(c->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);         // NULL = default stream, as in svr_render
-    // ordered like a render: behind the published uploads, and later uploads behind this composite (mark_render)
-    if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
-    SVR_HIP_TRY(svr_launch_composite(c, *cam, f, *cp, *out, table, K, interp, s));
-    return mark_render(c, s);
+    return SVR_DRAW_ORDERED(c, stream, svr_launch_composite(c, *cam, f, *cp, *out, table, K, interp, s));
 }
 
 int svr_iso(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, const svr_iso_params* ip, const svr_outputs* out,
             void* stream) {
-    SVR_REQUIRE(c && cam && fr && ip && out && out->rgba, "svr_iso: null argument");
-    SVR_REQUIRE(c->material_set, "svr_iso: svr_set_material has not been called");
-    SVR_REQUIRE(fr->frame_w > 0 && fr->frame_h > 0 && fr->out_w > 0 && fr->out_h > 0, "svr_iso: empty frame");
-    SVR_REQUIRE(fr->x0 >= 0 && fr->y0 >= 0, "svr_iso: negative tile origin");
+    svr_frame f;
+    { const int rc = draw_prologue("svr_iso", c && cam && fr && ip && out && out->rgba, c, fr, f); if (rc) return rc; }
     for (int a = 0; a < 3; ++a)
         SVR_REQUIRE(cam->volume_dimensions[a] >= 1.0f, "svr_iso: volume_dimensions must be >= 1");
     SVR_REQUIRE(ip->iso_value == ip->iso_value, "svr_iso: iso_value must not be NaN");
@@ -1347,14 +1345,7 @@ int svr_iso(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, const svr_is
         const float len2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
         SVR_REQUIRE(fabsf(sqrtf(len2) - 1.0f) <= 1e-3f, "svr_iso: light_direction must be finite and of unit length");
     }
-    svr_frame f = *fr;
-    if (f.band_h <= 0) { f.band_h = fr->out_h; f.band_pitch = fr->out_h; }
-    DeviceGuard guard(c->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);         // NULL = default stream, as in svr_render
-    // ordered like a render: behind the published uploads, and later uploads behind this draw (mark_render)
-    if (c->have_published) SVR_HIP_TRY(hipStreamWaitEvent(s, c->uploads_published, 0));
-    SVR_HIP_TRY(svr_launch_iso(c, *cam, f, *ip, *out, interpolation_of(c), s));
-    return mark_render(c, s);
+    return SVR_DRAW_ORDERED(c, stream, svr_launch_iso(c, *cam, f, *ip, *out, interpolation_of(c), s));
 }
 
 int svr_untile_stripes(svr_ctx* c, const void* gathered, void* frame_out, int frame_w, int frame_h,
