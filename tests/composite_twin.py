@@ -56,17 +56,32 @@ def lookup(rings, size, coord):
     return value, label, done
 
 
+def resolving_lod(rings, size, coord=None, data=None):
+    """The LOD whose ROI is the first to hold each point (-1: none): the window tests of ``lookup`` alone, which both
+    samplings share (the linear sample is taken inside the LOD the nearest sample picks)."""
+    dd = [coord[k] * size[k] for k in range(3)] if data is None else data
+    lod = np.full(dd[0].shape, -1, np.int32)
+    for n, r in enumerate(rings):
+        ic = [(dd[k] * f32(r["scale"][k])).astype(np.int32) for k in range(3)]
+        inb = lod < 0
+        for k in range(3):
+            inb &= (r["offset"][k] <= ic[k]) & (ic[k] < r["offset"][k] + r["shape"][k])
+        lod[inb] = n
+    return lod
+
+
 def composite_twin(rings, matrices, size, material, table, width, height, alpha_cutoff, color_by_label=False,
-                   region=None, pick_id=0):
+                   region=None, pick_id=0, census=False):
     """``rings``: oracle.lmip.rings_of(...); ``matrices``: the six row-major mat4 of svr_camera; ``size``:
     volume_dimensions in shader order; ``table``: the K x 4 f32 device table.  Returns dict(rgba, depth, label, flags,
-    steps, pick) for the output pixels of ``region`` (default: the frame)."""
+    steps, pick) for the output pixels of ``region`` (default: the frame).  ``census``: also "census", the number of
+    samples each LOD resolved (int64 [len(rings)]); nothing else changes."""
     with np.errstate(all="ignore"):
         return _composite(rings, matrices, size, material, np.asarray(table, f32), width, height, f32(alpha_cutoff),
-                          bool(color_by_label), region, pick_id)
+                          bool(color_by_label), region, pick_id, census)
 
 
-def _composite(rings, M, size, mat, T, W, H, cutoff, tint, region, pick_id):
+def _composite(rings, M, size, mat, T, W, H, cutoff, tint, region, pick_id, census=False):
     world = np.asarray(M["world"], f32)
     ndc_to_data = _mm(_mm(np.asarray(M["world_inv"], f32), np.asarray(M["cam_inv"], f32)), np.asarray(M["proj_inv"], f32))
     pc = _mm(np.asarray(M["proj"], f32), np.asarray(M["cam"], f32))
@@ -128,6 +143,7 @@ def _composite(rings, M, size, mat, T, W, H, cutoff, tint, region, pick_id):
     first = np.full(shape, -1, np.int64)
     steps = np.zeros(shape, np.uint32)
     alive = frag.copy()
+    counts = np.zeros(len(rings), np.int64)
     it = 0
     while True:
         act = alive & (it < nsteps)
@@ -137,6 +153,9 @@ def _composite(rings, M, size, mat, T, W, H, cutoff, tint, region, pick_id):
         iterf = f32(it)
         coord = [start[k][idx] + iterf * step[k][idx] for k in range(3)]
         s, lab, res = lookup(rings, size, coord)
+        if census:
+            held = resolving_lod(rings, size, coord)
+            counts += np.bincount(held[held >= 0], minlength=len(rings))
         steps[idx] += 1
         idx = tuple(i[res] for i in idx)                    # samples that no LOD holds contribute nothing
         s, lab = s[res], lab[res]
@@ -187,7 +206,10 @@ def _composite(rings, M, size, mat, T, W, H, cutoff, tint, region, pick_id):
             u = np.where(fk > 0, np.minimum(np.floor(np.nan_to_num(fk, nan=0.0)), 16383.0), 0.0).astype(np.uint64)
             word |= u << np.uint64(shift)
         pick[h] = word
-    return dict(rgba=rgba, depth=depth, label=label, flags=flags, steps=steps, pick=pick)
+    out = dict(rgba=rgba, depth=depth, label=label, flags=flags, steps=steps, pick=pick)
+    if census:
+        out["census"] = counts
+    return out
 
 
 def matrices_of(volume, camera):

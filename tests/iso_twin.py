@@ -5,7 +5,7 @@ change a plane.  The ray set-up is the march's, the LOD cascade ``composite_twin
 Vectorised over pixels: every step advances the pixels whose rays are still searching."""
 import numpy as np
 
-from composite_twin import _mm, _mv, material_of as _composite_material, matrices_of  # noqa: F401  (re-exported)
+from composite_twin import _mm, _mv, material_of as _composite_material, matrices_of, resolving_lod  # noqa: F401  (re-exported)
 from oracle import lmip
 from slice_twin import DISCARD, HIT, MISS, frame_pixels, hsv_to_rgb
 
@@ -110,18 +110,23 @@ def _unit(v, fallback):
     return [np.where(ok, v[k] / safe, fallback[k]) for k in range(3)]
 
 
-def iso_twin(rings, matrices, size, material, width, height, params=None, region=None, pick_id=0):
+def iso_twin(rings, matrices, size, material, width, height, params=None, region=None, pick_id=0, census=False):
     """``rings``: oracle.lmip.rings_of(...); ``matrices``: the six row-major mat4 of svr_camera; ``size``:
     volume_dimensions in shader order; ``params``: the svr_iso_params fields that differ from ``DEFAULTS``.  Returns
     dict(rgba, depth, label, flags, steps, pick, normal, iter) for the output pixels of ``region`` (default: the frame);
-    ``iter`` is the refined float counter of the hit (diagnostics)."""
+    ``iter`` is the refined float counter of the hit (diagnostics).  ``census``: also "census", the number of samples
+    of the coarse search each LOD resolved (int64 [len(rings)]), and "hit_lod", the LOD that holds each hit (int32,
+    -1 on non-hits); nothing else changes."""
     p = dict(DEFAULTS)
     p.update(params or {})
     with np.errstate(all="ignore"):
-        return _iso(rings, matrices, size, material, width, height, p, region, pick_id)
+        out = _iso(rings, matrices, size, material, width, height, p, region, pick_id, census)
+    if not census:
+        out.pop("census"), out.pop("hit_lod")
+    return out
 
 
-def _iso(rings, M, size, mat, W, H, p, region, pick_id):
+def _iso(rings, M, size, mat, W, H, p, region, pick_id, census=False):
     S = setup_rays(M, size, mat, W, H, region)
     frag, nsteps, start, step, world, pc, size, shape = (S[k] for k in ("frag", "nsteps", "start", "step", "world", "pc", "size", "shape"))
     world_inv = np.asarray(M["world_inv"], f32)
@@ -131,6 +136,8 @@ def _iso(rings, M, size, mat, W, H, p, region, pick_id):
     # ---- coarse search: the first sample at or above the level
     cand = np.full(shape, -1, np.int64)
     searching = frag.copy()
+    counts = np.zeros(len(rings), np.int64)
+    hit_lod = np.full(shape, -1, np.int32)
     it = 0
     while True:
         act = searching & (it < nsteps)
@@ -139,6 +146,8 @@ def _iso(rings, M, size, mat, W, H, p, region, pick_id):
         idx = np.nonzero(act)
         coord = [start[k][idx] + f32(it) * step[k][idx] for k in range(3)]
         s, _, lod = lookup(rings, size, coord)
+        if census:
+            counts += np.bincount(lod[lod >= 0], minlength=len(rings))
         got = (lod >= 0) & (s >= iso)
         at = tuple(i[got] for i in idx)
         cand[at] = it
@@ -154,7 +163,8 @@ def _iso(rings, M, size, mat, W, H, p, region, pick_id):
     normal = np.zeros(shape + (3,), f32)
     iters = np.full(shape, np.nan, f32)
     if not hit.any():
-        return dict(rgba=rgba, depth=depth, label=label, flags=flags, steps=steps, pick=pick, normal=normal, iter=iters)
+        return dict(rgba=rgba, depth=depth, label=label, flags=flags, steps=steps, pick=pick, normal=normal, iter=iters,
+                    census=counts, hit_lod=hit_lod)
     h = np.nonzero(hit)
     st = [start[k][h] for k in range(3)]
     sp = [step[k][h] for k in range(3)]
@@ -177,6 +187,7 @@ def _iso(rings, M, size, mat, W, H, p, region, pick_id):
     d = [c[a] * size[a] for a in range(3)]
     _, lab, hl = lookup(rings, size, c)
     assert (hl >= 0).all()
+    hit_lod[h] = hl
 
     # ---- gradient: central differences of one voxel of the hit's LOD per axis, then the inverse-transpose
     scales = np.array([r["scale"] for r in rings], f32)[hl]              # [n, 3]
@@ -229,7 +240,8 @@ def _iso(rings, M, size, mat, W, H, p, region, pick_id):
         u = np.where(fk > 0, np.minimum(np.floor(np.nan_to_num(fk, nan=0.0)), 16383.0), 0.0).astype(np.uint64)
         word |= u << np.uint64(shift)
     pick[h] = word
-    return dict(rgba=rgba, depth=depth, label=label, flags=flags, steps=steps, pick=pick, normal=normal, iter=iters)
+    return dict(rgba=rgba, depth=depth, label=label, flags=flags, steps=steps, pick=pick, normal=normal, iter=iters,
+                census=counts, hit_lod=hit_lod)
 
 
 def params_of(material):

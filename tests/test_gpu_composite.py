@@ -1,6 +1,6 @@
 """GPU: svr_composite (include/svr.h, composite render mode) == the numpy restatement of tests/composite_twin.py: flags,
 steps, label and pick bit for bit, rgba and depth within 1e-4 — u8 / u16 / float32 rings, with and without labels, 1
-and 3 LODs, no / "auto" / "all" micro-block copies, perspective and orthographic cameras, a rotated and scaled world,
+and 3 LODs (every count 1 .. 8: tests/test_gpu_lod_counts.py), no / "auto" / "all" micro-block copies, perspective and orthographic cameras, a rotated and scaled world,
 clipping planes ANY and ALL, cutoffs 1.0 / 0.99 / 0.5 with and without the label tint, and a fly-through that wraps
 the rings.  Also: tiles and stripes, out= in place, outline / compose on a composite, a float ring beyond 4 GiB, the
 table sent only when it changes, every refusal with nothing launched, and LMIP / MIP / weighted-average frames that a

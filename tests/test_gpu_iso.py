@@ -1,6 +1,6 @@
 """GPU: svr_iso (include/svr.h, iso-surface render mode) == the numpy restatement of tests/iso_twin.py: flags, steps,
 label and pick bit for bit, rgba, depth and normal within 1e-4, no pixel left out — u8 / u16 / float32 rings, with and
-without labels, 1 and 3 LODs, no / "auto" / "all" micro-block copies, perspective and orthographic cameras, a rotated
+without labels, 1 and 3 LODs (every count 1 .. 8: tests/test_gpu_lod_counts.py), no / "auto" / "all" micro-block copies, perspective and orthographic cameras, a rotated
 and anisotropically scaled world, clipping planes ANY and ALL, several levels / refinements / lights, and a fly-through
 that wraps the rings.  Empty-space skipping: skip on == skip off on every plane bit for bit on the scenes
 tests/test_gpu_skip.py builds for LMIP (2^3 blobs on cell corners and faces, levels at / just above / just below the

@@ -1,7 +1,7 @@
 """GPU: interpolation="linear" (svr_set_interpolation, include/svr.h) on svr_slice, svr_slab, svr_composite and svr_iso
 == the numpy restatement of tests/linear_twin.py.  Every pixel is compared: flags, label, lod, steps, pick and the
 slice / slab value plane bit for bit; rgba, depth and normal within 1e-4.  Axes: u8 / u16 / float32 rings, with and
-without labels, 1 and 3 LODs, no / "auto" / "all" micro-block copies and slice variant bits 8 / 9, perspective and
+without labels, 1 and 3 LODs (every count 1 .. 8: tests/test_gpu_lod_counts.py), no / "auto" / "all" micro-block copies and slice variant bits 8 / 9, perspective and
 orthographic cameras, a rotated and anisotropically scaled world, a fly-through that wraps the rings on every axis,
 tiles and stripes, a slice at pixel size 0.25 and oblique ones, slab max / min / mean and N = 1, a float ring beyond
 4 GiB.  Iso skipping under linear: skip on == no_skip on every plane on the scenes of tests/test_gpu_skip.py, and

@@ -1,5 +1,6 @@
 """GPU: svr_slab (include/svr.h, thick-slab projections) == the numpy restatement of tests/slab_twin.py: value, label,
-flags, lod and depth bit for bit, rgba within 1e-4 — u8 / u16 / float32 rings, with and without labels, 1 and 3 LODs,
+flags, lod and depth bit for bit, rgba within 1e-4 — u8 / u16 / float32 rings, with and without labels, 1 and 3 LODs (every
+count 1 .. 8: tests/test_gpu_lod_counts.py),
 no / "auto" / "all" micro-block copies and variant bits 0 / 8 / 9, N in {1, 2, 7, 64}, max / min / mean, three axis
 slabs and an oblique one with an oblique w, a rotated, scaled and translated world, a volume whose sizes are not
 powers of two.  Also: N = 1 max == svr_slice bit for bit, tiles and stripes, out= in place, outline / compose on a slab,

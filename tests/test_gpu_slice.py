@@ -2,7 +2,7 @@
 flags and lod bit for bit, rgba within 1e-4, depth 0 — over synthetic scenes seen from outside and inside and the
 multi-scale demo scene, u8 / u16 / float32 rings, a label-less volume, no / "auto" / "all" micro-block copies, three
 axis-aligned and two oblique planes (one with non-orthogonal u and v), pixel sizes 0.37 / 1 / 2.5, a rotated, scaled
-and translated world, gamma != 1, sRGB on and off, 1 and 3 LODs.  Also: a fly-through against the source arrays,
+and translated world, gamma != 1, sRGB on and off, 1 and 3 LODs (every count 1 .. 8: tests/test_gpu_lod_counts.py).  Also: a fly-through against the source arrays,
 tiles and stripes against the full frame, ordering against asynchronous uploads, a float ring beyond 4 GiB, outline /
 compose on a slice, and every refusal with nothing launched."""
 import ctypes as C
