@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "svr_internal.h"
+#include "twin_address.h"
 
 namespace {
 
@@ -508,19 +509,17 @@ __device__ __forceinline__ uint32_t shl_add_c(uint32_t a, uint32_t c) {         
     return r;
 }
 
-// Micro-block copy of a ring (svr_lod_desc::blocked_twin; host: svr_blocked_index): 128-byte blocks of
-// 2^XB x 2^YB x 2^ZB slots in [bz][by][bx] order, the slots of a block in [z][y][x] order.
-template <int ESH> struct TwinBlock { static constexpr int XB = ESH == 0 ? 3 : 2, YB = 2, ZB = ESH == 2 ? 1 : 2; };
-// Byte offset of the texel of voxel (x, y, z) in that copy, for a lane whose ring slot is voxel + (kx, ky, kz) with
-// constants that are multiples of the ring extents — and therefore of the block extents: the block coordinates of the
-// slot are those of the voxel plus constants, the position inside the block is the voxel's own low bits:
-//   offset = ((z >> ZB) * NBy + (y >> YB)) * NBx + (x >> XB) + Kb) * 128 + in-block part,   Kb = the constants' block number
-// (all mod 2^32).  Computed from the packed form of the voxel (x, yz = y | z << 16, both below 2^16: LodParams::twin says
-// so) in 9 VALU operations, where the form above takes 12 and a quarter-rate v_mad_u64_u32 (the compiler's choice for the
-// inner multiply-add; the asm mad24 of the row-major form costs this loop 9 more VGPRs — one wave per SIMD less):
+// Micro-block copy of a ring (svr_lod_desc::blocked_twin; host: svr_blocked_index): TwinBlock, the layout's separable
+// form and the 6-operation (bytes; 7 for u16) offset svr_twin_offset that the gather loop uses are in twin_address.h.
+// That form needs 16-bit weights (LodParams::twin_w != 0: byte rings of up to 1024 x 512 slots per plane); the copies of
+// larger rings, and those of float32 rings (see where direct_batches is called), are addressed by the form below, from
+// the same packed voxel (x, yz = y | z << 16, both below 2^16: LodParams::twin says so) and the same per-lane constant
+// K' = Kb * (128 >> SZ), Kb = the block number of the lane's wrap constants, in 9 VALU operations:
 //   offset = 4row * (NBx * 32) + (x & ~xm) << (7 - XB)  +  [ (y & 3) * wy + (z & zm) * wz + ((x & xm) << ESH | KbS) ]
 // with 4row = (y & ~3) + (z & ~zm) * (NBy * 4 >> ZB) from one v_dot2_u32_u16, the bracket from another (wy, wz: the byte
-// strides of y and z inside a block) and KbS = Kb << 7 (its low 7 bits are free for the in-block part).
+// strides of y and z inside a block) and KbS = Kb << 7 = K' << SZ (its low 7 bits are free for the in-block part).
+// (The row-major form ((bz * NBy + by) * NBx + bx + Kb) * 128 + in-block part takes 12 and a quarter-rate v_mad_u64_u32,
+// the compiler's choice for the inner multiply-add; the asm mad24 of the rows costs this loop 9 more VGPRs.)
 struct TwinConsts { uint32_t row_w, inb_w, nbx32; };           // wave-uniform: (1 | NBy * 4 >> ZB << 16), (wy | wz << 16), NBx * 32
 template <int ESH>
 __device__ __forceinline__ TwinConsts twin_consts(uint32_t Rx, uint32_t Ry) {
@@ -900,7 +899,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
     // span state: iterations [.., E) use LOD `code` (NL = none) with address constant Kc
     int code = NL, E = 0;
     uint32_t Kc = 0xFFFFFFFFu;
-    uint32_t Kb = 0u;            // the same for the micro-block copy of the span's LOD (twin_offset), kept by waves that gather from it
+    uint32_t Kb = 0u;            // the same for the micro-block copy of the span's LOD (K' of twin_address.h), kept by waves that gather from it
     int zth = 0;                 // BIG builds: first voxel index ic_z whose ring plane lies in the LOD's upper resource
 
     // Wave-static routing of fast runs (u8 rings).  LDS bricks pay when the samples a wave fetches
@@ -963,8 +962,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
                         Kc = (kz * L.ring[1] + ky) * L.rx4 + (kx << ESH) + L.base_bytes;  // mod 2^32
                         if (many_lines && L.twin) {                           // (wave-uniform)
                             typedef TwinBlock<ESH> B;
-                            Kb = (uint32_t)(((int)kz >> B::ZB) * (int)(L.ring[1] >> B::YB) + ((int)ky >> B::YB)) * (L.ring[0] >> B::XB) +
-                                 (uint32_t)((int)kx >> B::XB);
+                            Kb = svr_twin_lane_const<ESH>((uint32_t)(((int)kz >> B::ZB) * (int)(L.ring[1] >> B::YB) + ((int)ky >> B::YB)) * (L.ring[0] >> B::XB) +
+                                                          (uint32_t)((int)kx >> B::XB));
                         }
                         if constexpr (BIG) zth = (int)L.zsplit - (int)kz;                 // slot plane ic_z + kz >= k * zsplit <=> ic_z >= zth + (k - 1) * zsplit
                         if (ev[l].cx > n) E = min(E, ev[l].cx);
@@ -1316,11 +1315,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
             }
 
             // ---- direct fast batches: texel offset = ((iz*Ry + iy)*Rx + ix)*es + Kc, U loads in flight
-            // (two copies of the loop, one per layout the wave gathers from: each keeps only its own constants live)
+            // (a copy of the loop per layout the wave gathers from and per address form of the micro-block copy — 0: rows,
+            //  1: the copy by twin_offset_packed, 2: the copy by svr_twin_offset —: each keeps only its own constants live)
             __amdgpu_buffer_rsrc_t rsrc_twin = rsrc;              // (the copy's own resource and base: set where the wave turns to it)
             const void* twin_base = nullptr;
+            uint32_t twin_w = 0u;                                 // (LodParams::twin_w of the copy, likewise)
             auto direct_batches = [&](auto from_twin) {
-            constexpr bool TW = decltype(from_twin)::value;
+            constexpr int TWF = decltype(from_twin)::value;
+            constexpr bool TW = TWF != 0;
             for (; run > 0; --run) {
                 const bool live = alive && !finished && n < nsteps;
                 if (__builtin_amdgcn_ballot_w64(live) == 0) break;
@@ -1328,9 +1330,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
                 texel_t s[U];
                 uint32_t off[U];
                 float2_t iter = { (float)n, (float)n + 1.0f };
-                if constexpr (TW) {
+                if constexpr (TWF == 2) {
+#pragma unroll
+                    for (int u = 0; u < U; u += 2) {
+                        const Idx2p v = voxel_pair_packed<SCALED>(Rsx, Rsy, Rsz, Rtx, Rty, Rtz, iter, ssx, ssy, ssz);
+                        iter += 2.0f;
+                        off[u] = svr_twin_offset<ESH>(v.x0, v.yz0, twin_w, Kb);
+                        off[u + 1] = svr_twin_offset<ESH>(v.x1, v.yz1, twin_w, Kb);
+                    }
+                } else if constexpr (TWF == 1) {
                     const TwinConsts tc = twin_consts<ESH>(L.ring[0], L.ring[1]);
-                    const uint32_t KbS = Kb << 7;
+                    const uint32_t KbS = Kb << TwinBlock<ESH>::SZ;
 #pragma unroll
                     for (int u = 0; u < U; u += 2) {
                         const Idx2p v = voxel_pair_packed<SCALED>(Rsx, Rsy, Rsz, Rtx, Rty, Rtz, iter, ssx, ssy, ssz);
@@ -1407,9 +1417,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
                 const kparams_t Pt = fresh_params(P);
                 twin_base = Pt->lod[first].twin_rbase;
                 rsrc_twin = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(twin_base), 0, (int)Pt->lod[first].twin_rbytes, 0x00020000);
-                direct_batches(std::true_type{});
+                // (float32 rings stay on form 1: with the third copy of the loop their scaled-ray kernel needs 4 more VGPRs and
+                //  spills, and their LMIP frames ran 1 - 3 % slower on every view — profiles/twin_address/README.md)
+                if constexpr (ESH != 2) twin_w = Pt->lod[first].twin_w;
+                if (ESH != 2 && twin_w != 0u) direct_batches(std::integral_constant<int, 2>{});
+                else direct_batches(std::integral_constant<int, 1>{});
             } else {
-                direct_batches(std::false_type{});
+                direct_batches(std::integral_constant<int, 0>{});
             }
             } while (held > 0 && __builtin_amdgcn_ballot_w64(alive && !finished && n < nsteps) != 0);
             if constexpr (SCALED) {

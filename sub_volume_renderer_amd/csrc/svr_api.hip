@@ -15,6 +15,7 @@
 #include "ray_common.h"
 #include "ring_parts.h"
 #include "march_pow2.h"
+#include "twin_address.h"
 
 static thread_local std::string g_err;
 void svr_set_error(const std::string& msg) { g_err = msg; }
@@ -1151,6 +1152,7 @@ static int fill_params(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, c
         } else {
             Q.rbase = c->density_all; Q.rbytes = P.density_all_bytes;
         }
+        Q.twin_w = Q.twin ? svr_twin_weights(c->density_storage == SVR_U8 ? 0 : (c->density_storage == SVR_U16 ? 1 : 2), Q.ring[0], Q.ring[1]) : 0u;
     }
     P.density_esh = c->density_storage == SVR_U8 ? 0 : (c->density_storage == SVR_U16 ? 1 : 2);
     return SVR_OK;

@@ -64,6 +64,7 @@ struct LodParams {
     uint32_t twin;             // 0: no copy; 1: waves with many rows per gather take it instead of staging bricks; 2: only when they stage none
     uint32_t twin_rbytes;      // size of the copy's own buffer resource (of a full part of it where the ring is cut into parts)
     const void* twin_rbase;    // ... which starts here
+    uint32_t twin_w;           // svr_twin_weights (twin_address.h) of the copy: the march addresses it by the separable form; 0: by the general one
     uint32_t cell_base;        // byte offset of the LOD's cell grid
     uint32_t cdim[3];          // cells per axis
     int32_t  cshift;           // log2 of the cell size (3 or 2)
