@@ -613,6 +613,55 @@ int  svr_iso(svr_ctx* ctx, const svr_camera* cam, const svr_frame* frame, const 
 #define SVR_INTERP_LINEAR  1
 int  svr_set_interpolation(svr_ctx* ctx, int mode);
 
+/* ---- cut planes: trimmed rays and flat lit caps for svr_composite and svr_iso (the cut-away view of a volume viewer;
+ * the material's clipping planes, pygfx's rule, discard whole pixels by where the ray LEAVES the box and never shorten
+ * a ray).  An addition within ABI version 9: one new symbol, no struct changes.  svr_render, svr_slice and svr_slab
+ * are not affected: the march keeps the contract with the reference.
+ *   planes   HOST pointer to count x (a, b, c, d) in world space, copied.  count == 0 clears the planes (planes may
+ *            then be NULL).  A world point w is BEHIND plane k when dot(w, abc_k) < d_k: the sense of clipping_planes.
+ *   mode     a point is CUT AWAY when it is behind ANY plane (SVR_CUT_ANY: what stays is the intersection of the
+ *            half-spaces) or behind ALL of them (SVR_CUT_ALL: a convex wedge is removed).
+ * THE CUT PREDICATE, defined HERE (numpy restatement: tests/cut_twin.py), in f32, in this order, with no fused
+ * operations; m = cam->world, column-major as the iso view vector reads it.  Per call, on the host:
+ *     g_k.x = (m[0]*a + m[1]*b) + m[2]*c;   g_k.y = (m[4]*a + m[5]*b) + m[6]*c;   g_k.z = (m[8]*a + m[9]*b) + m[10]*c
+ *     h_k   = ((m[12]*a + m[13]*b) + m[14]*c) - d
+ *     len_k = sqrtf(dot(abc_k, abc_k));  nhat_k = (a/len_k, b/len_k, c/len_k)
+ * per ray, from the start, step and size of the ray set-up:
+ *     p0_a = start_a*size_a - 0.5f;  sd_a = step_a*size_a  (the iso definition's sd)
+ *     A_k  = dot(g_k, p0) + h_k;     B_k  = dot(g_k, sd)
+ * per float counter iter:
+ *     E_k(iter) = A_k + iter*B_k;  behind_k(iter) = E_k(iter) < 0.0f;  cut(iter) = OR (ANY) or AND (ALL) over k
+ * Along one ray E_k is monotone in iter, under f32 rounding too (iter*B_k is a monotone rounded product, adding A_k is
+ * monotone).  So each plane's behind-set over i = 0 .. nsteps-1 is a prefix or a suffix; under ANY the kept samples
+ * form one index interval, under ALL the cut samples do.  The kernels use that: they find the interval once per ray
+ * (a binary search on the predicate itself, so it agrees with it exactly) and mask samples by integer compares.
+ *   svr_composite  a sample i with cut((float)i) is treated exactly like a sample no LOD holds: it contributes nothing
+ *                  and is counted in steps.  Nothing else in the definition changes.
+ *   svr_iso        S(iter) has no value where cut(iter), in the coarse search and in the refine search.  D(p) of the
+ *                  gradient reads the uncut field.  steps keeps its definition: i + 1 on a hit, nsteps on a MISS.
+ *                  Label, depth, pick and colour rules are unchanged.
+ *   caps (svr_iso) pred = the point examined immediately before the hit in search order:
+ *                    hit at refine sub-sample k >= 2:                  pred = (float)(i-1) + (float)(k-1)/(float)refine
+ *                    hit at k == 1:                                    pred = (float)(i-1)
+ *                    hit at (float)i after a refine search found none: pred = (float)(i-1) + (float)(refine-1)/(float)refine
+ *                    hit at (float)i with refine <= 1 and i > 0:       pred = (float)(i-1)
+ *                    i == 0:                                           there is no pred
+ *                  The hit is a CAP when pred exists and cut(pred).  On a cap the normal is the cutting plane's: under
+ *                  ANY k is the lowest index with behind_k(pred), under ALL the lowest with !behind_k(hit);
+ *                  n = nhat_k, negated when dot(n, v) < 0.0f (v the view vector; a zero v leaves n as it is).  Shading
+ *                  proceeds with that n and the normal plane receives it.  A ray that enters at the box face (i == 0)
+ *                  keeps the gradient normal.
+ *   skipping       a wave-stretch in which every live lane's eight coarse samples are cut is passed without fetching
+ *                  texels or cell maxima and counted under skip_counters[1] (with no_skip too: it is exact).  Skipping
+ *                  stays invisible in every output plane.
+ * Read by the svr_composite and svr_iso calls enqueued after it; a render-thread call like svr_set_interpolation.  A
+ * fresh context has no planes.  SVR_ERR_INVALID, with the state unchanged, for: count > SVR_MAX_CUT_PLANES, NULL planes
+ * with count > 0, an unknown mode, any component not finite, a len_k that is 0 or not finite. */
+#define SVR_MAX_CUT_PLANES 8
+#define SVR_CUT_ANY 0
+#define SVR_CUT_ALL 1
+int  svr_set_cut_planes(svr_ctx* ctx, const float* planes, uint32_t count, int mode);
+
 /* ---- sync */
 int  svr_sync(svr_ctx* ctx);                 /* both streams idle */
 int  svr_sync_uploads(svr_ctx* ctx);         /* upload stream idle */

@@ -73,6 +73,8 @@ class SubVolumeMaterial:
         # inherited from pygfx's Material: no clipping planes unless the caller sets some
         self.clipping_planes = ()
         self.clipping_mode = "ANY"
+        self.cut_planes = ()
+        self.cut_mode = "ANY"
         self.render_mode = "lmip"
         self.interpolation = "nearest"
         self.weight_falloff = 0.5
@@ -161,6 +163,49 @@ class SubVolumeMaterial:
         if mode not in ("ANY", "ALL"):
             raise ValueError(f"Unexpected clipping_mode: {mode}")
         self._store("clipping_mode", mode)
+
+    # -- cut planes (svr_set_cut_planes): the cut-away view of the "composite" and "iso" modes ---------------------
+    MAX_CUT_PLANES = 8
+
+    @property
+    def cut_planes(self) -> list[tuple[float, float, float, float]]:
+        """World-space planes (a, b, c, d) that open the volume up in the "composite" and "iso" render modes: a point
+        p with ``dot(p, abc) < d`` is behind a plane, and the part of the volume behind ANY plane (``cut_mode ==
+        "ANY"``: what stays is the intersection of the half-spaces) or behind ALL of them ("ALL": a convex wedge is
+        removed) is not sampled.  Unlike ``clipping_planes``, which drop whole pixels, these shorten rays; in "iso"
+        mode the cut faces are flat, lit caps (``svr_set_cut_planes`` in ``include/svr.h``).  The march ("lmip",
+        "mip", "weighted_average") knows no cuts: ``SubVolume.render`` refuses those modes while planes are set."""
+        return [tuple(map(float, row)) for row in self._u["cut_planes"]]
+
+    @cut_planes.setter
+    def cut_planes(self, planes) -> None:
+        rows = []
+        for plane in planes:
+            if isinstance(plane, (str, bytes)) or len(plane) != 4:
+                raise TypeError(f"Each cut plane must be an abcd tuple, not {plane}")
+            rows.append([float(v) for v in plane])
+        if len(rows) > self.MAX_CUT_PLANES:
+            raise ValueError(f"at most {self.MAX_CUT_PLANES} cut planes are supported")
+        with np.errstate(over="ignore"):
+            table = np.asarray(rows, np.float32).reshape(-1, 4)
+            if not np.all(np.isfinite(table)):
+                raise ValueError("every component of a cut plane must be finite (as float32)")
+            length = np.sqrt((table[:, 0] * table[:, 0] + table[:, 1] * table[:, 1]) + table[:, 2] * table[:, 2])
+        if not np.all((length > 0) & np.isfinite(length)):
+            raise ValueError("a cut plane's normal (a, b, c) must have a finite, non-zero length (as float32)")
+        self._store("cut_planes", table)
+
+    @property
+    def cut_mode(self) -> str:
+        """"ANY": a point is cut away if it is behind any cut plane; "ALL": only if it is behind all of them."""
+        return self._u["cut_mode"]
+
+    @cut_mode.setter
+    def cut_mode(self, mode) -> None:
+        mode = str(mode).upper()
+        if mode not in ("ANY", "ALL"):
+            raise ValueError(f"Unexpected cut_mode: {mode}")
+        self._store("cut_mode", mode)
 
     # -- render mode: the swappable raycast the reference wishes for (FUTURE.md:97-120) -------------------------
     RENDER_MODES = ("lmip", "mip", "weighted_average", "composite", "iso")

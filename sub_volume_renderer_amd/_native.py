@@ -173,6 +173,8 @@ class IsoParams(C.Structure):
 
 
 INTERPOLATIONS = {"nearest": 0, "linear": 1}      # SVR_INTERP_*
+CUT_MODES = {"ANY": 0, "ALL": 1}                  # SVR_CUT_*
+MAX_CUT_PLANES = 8                                # SVR_MAX_CUT_PLANES
 
 ISO_MAX_REFINE = 16                                 # SVR_ISO_MAX_REFINE
 ISO_MAX_SHININESS_LOG2 = 10                         # SVR_ISO_MAX_SHININESS_LOG2
@@ -228,6 +230,7 @@ SIGNATURES = {
     "svr_iso": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Frame), C.POINTER(IsoParams), C.POINTER(Outputs),
                           C.c_void_p]),
     "svr_set_interpolation": (C.c_int, [C.c_void_p, C.c_int]),
+    "svr_set_cut_planes": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int]),
     "svr_sync": (C.c_int, [C.c_void_p]),
     "svr_sync_uploads": (C.c_int, [C.c_void_p]),
     "svr_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),

@@ -434,6 +434,35 @@ class SubVolume(_HasWorld):
             raise ValueError(f"interpolation must be one of {tuple(N.INTERPOLATIONS)} or None, not {interpolation!r}")
         N.check(N.lib().svr_set_interpolation(self._rings.handle, N.INTERPOLATIONS[mode]), "svr_set_interpolation")
 
+    def _push_cut_planes(self):
+        """Set the context's cut planes for the next composite / iso call from the material (an empty list too, so
+        that a material change clears the context)."""
+        planes = np.ascontiguousarray(self.material._u["cut_planes"], np.float32).reshape(-1, 4)
+        mode = N.CUT_MODES[self.material.cut_mode]
+        ptr = planes.ctypes.data_as(C.POINTER(C.c_float)) if len(planes) else None
+        N.check(N.lib().svr_set_cut_planes(self._rings.handle, ptr, len(planes), mode), "svr_set_cut_planes")
+
+    def crop_planes(self, begin, end):
+        """The six world-space planes (a, b, c, d) of the voxel box ``[begin, end)`` (numpy order, like the array's
+        indices) under the volume's current world transform, computed in float64: with ``material.cut_mode = "ANY"``
+        and ``material.cut_planes = volume.crop_planes(begin, end)`` the "composite" and "iso" renders are cropped to
+        the box.  Voxel i of an axis covers [i - 0.5, i + 0.5) in data space, so the box is [begin - 0.5, end - 0.5)."""
+        begin = np.asarray(begin, np.float64).reshape(-1)
+        end = np.asarray(end, np.float64).reshape(-1)
+        if begin.shape != (3,) or end.shape != (3,) or not (np.all(np.isfinite(begin)) and np.all(np.isfinite(end))):
+            raise ValueError("begin and end must be three finite numbers each")
+        if not np.all(end > begin):
+            raise ValueError("end must exceed begin on every axis")
+        inv = np.asarray(self.world.inverse_matrix, np.float64)        # world -> data (x, y, z)
+        planes = []
+        for axis in range(3):                                           # numpy axis; the data-space axis is 2 - axis
+            row = inv[2 - axis]
+            lo, hi = begin[axis] - 0.5, end[axis] - 0.5
+            # kept: lo <= dot(row[:3], w) + row[3] < hi
+            planes.append((row[0], row[1], row[2], lo - row[3]))
+            planes.append((-row[0], -row[1], -row[2], row[3] - hi))
+        return [tuple(float(v) for v in p) for p in planes]
+
     def _camera_key(self, camera):
         # the projection enters as the bytes of its matrix, whatever kind of camera made it: every parameter of
         # any projection (fov, width, height, zoom, aspect, depth range) changes the key exactly when it changes
@@ -560,6 +589,11 @@ class SubVolume(_HasWorld):
                 f"render_mode {self.material.render_mode!r} is the march, which samples nearest texels (the reference's "
                 "behaviour); interpolation='linear' applies to the render modes 'composite' and 'iso' and to "
                 "render_slice / render_slab (pass interpolation='linear' to those calls to keep this material nearest)")
+        if len(self.material._u["cut_planes"]) and self.material.render_mode not in ("composite", "iso"):
+            raise ValueError(
+                f"render_mode {self.material.render_mode!r} is the march, which knows no cut planes (it keeps the "
+                "reference's behaviour); cut_planes are honoured by the render modes 'composite' and 'iso' "
+                "(svr_composite and svr_iso), not by 'lmip', 'mip', 'weighted_average', render_slice or render_slab")
         handle = self.prepare()
         cb = self.camera_block(camera)
         fb = self.frame_block(width, height, region)
@@ -587,6 +621,7 @@ class SubVolume(_HasWorld):
             # written by the production kernel
             self._push_transfer_function()
             self._push_interpolation()
+            self._push_cut_planes()
             cp = N.CompositeParams(self.material.alpha_cutoff, 1 if self.material.color_by_label else 0)
             N.check(N.lib().svr_composite(handle, C.byref(cb), C.byref(fb), C.byref(cp), C.byref(ob), C.c_void_p(stream)),
                     "svr_composite")
@@ -596,6 +631,7 @@ class SubVolume(_HasWorld):
             # production kernel
             ip = self._iso_params(res)
             self._push_interpolation()
+            self._push_cut_planes()
             N.check(N.lib().svr_iso(handle, C.byref(cb), C.byref(fb), C.byref(ip), C.byref(ob), C.c_void_p(stream)), "svr_iso")
             return res
         N.check(

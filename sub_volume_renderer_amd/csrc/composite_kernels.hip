@@ -51,6 +51,7 @@ struct CompParams {
     uint32_t* steps;
     unsigned long long* pick; uint32_t pick_id;
     CompLod L[SVR_MAX_LODS];
+    CutParams cut;             // after L[]: every argument above keeps the offset it had before cuts existed
 };
 
 using CompArgs = const CompParams __attribute__((address_space(4)));     // the kernel arguments' own address space
@@ -59,7 +60,10 @@ constexpr int COMP_UNROLL = 8;     // samples whose gathers are in flight togeth
 constexpr int COMP_LIN_UNROLL = 4; // the same under linear sampling: 4 samples x 8 corners = 32 gathers in flight
 
 // LIN: s of every sample is the linear sample of svr.h (svr_set_interpolation); labels stay the nearest sample's.
-template <int NL, int ESH, bool TINT, bool LIN>
+// CUT: the samples svr_set_cut_planes cuts away are treated like samples no LOD holds.  The ray's kept (ANY) or cut
+// (ALL) index interval is found once (cut_span); the loop starts at the batch of the first kept sample and, under ANY,
+// ends after the last one, and a sample is masked by cut_sample.  Without CUT nothing of this is compiled.
+template <int NL, int ESH, bool TINT, bool LIN, bool CUT>
 __global__ __launch_bounds__(256) void composite_kernel(const CompParams P) {
     constexpr int U = LIN ? COMP_LIN_UNROLL : COMP_UNROLL;
     extern __shared__ float4 lut[];
@@ -87,7 +91,20 @@ __global__ __launch_bounds__(256) void composite_kernel(const CompParams P) {
         const float inv_lo = P.clim0, span = P.clim1 - P.clim0;
         const CompArgs* kq = (const CompArgs*)__builtin_amdgcn_kernarg_segment_ptr();     // P itself: the only argument
         bool alive = true;
-        for (int i0 = 0; alive && i0 < R.nsteps; i0 += U) {
+        int i_begin = 0, i_end = R.nsteps;
+        CutSpan cspan = { 0, 0 };
+        bool cut_all = false;
+        if constexpr (CUT) {
+            const CutParams* cq = (const CutParams*)&kq->cut;       // wave-uniform: scalar loads, like the LOD table
+            cut_all = cq->all != 0;
+            cspan = cut_span(*cq, cut_ray(R, P.size), R.nsteps);
+            // the first kept sample (nsteps: none) and one past the last
+            const int kept0 = cut_all ? (cspan.lo > 0 ? 0 : cspan.hi) : (cspan.lo < cspan.hi ? cspan.lo : R.nsteps);
+            i_begin = min((kept0 / U) * U, R.nsteps);
+            if (!cut_all) i_end = cspan.lo < cspan.hi ? cspan.hi : 0;
+            steps = (uint32_t)i_begin;                               // cut samples are counted
+        }
+        for (int i0 = i_begin; alive && i0 < i_end; i0 += U) {
             // The LOD table is read from the kernel arguments afresh in each batch (scalar loads from the constant
             // cache) instead of being held in SGPRs across the loop (slice_kernels.hip does the same).
             asm volatile("" : "+s"(kq));
@@ -108,6 +125,7 @@ __global__ __launch_bounds__(256) void composite_kernel(const CompParams P) {
                 addr[j] = static_cast<const char*>(Ls[0].density);   // a valid address for the unused gather
                 laddr[j] = nullptr;
                 bool done = i0 + j >= R.nsteps;
+                if constexpr (CUT) done = done || cut_sample(cspan, cut_all, i0 + j);
 #pragma unroll
                 for (int l = 0; l < NL; ++l) {
                     size_t idx;
@@ -135,6 +153,7 @@ __global__ __launch_bounds__(256) void composite_kernel(const CompParams P) {
                 svr_linear::LaneLod q = svr_linear::lane_lod_zero();
                 const char* base = static_cast<const char*>(Ls[0].density);   // a valid address for the unused gathers
                 bool done = i0 + j >= R.nsteps;
+                if constexpr (CUT) done = done || cut_sample(cspan, cut_all, i0 + j);
 #pragma unroll
                 for (int l = 0; l < NL; ++l) {
                     size_t idx;
@@ -195,6 +214,7 @@ __global__ __launch_bounds__(256) void composite_kernel(const CompParams P) {
                 if (ca >= P.alpha_cutoff) alive = false;
             }
         }
+        if constexpr (CUT) { if (alive) steps = (uint32_t)R.nsteps; }    // the cut samples after the last kept one
     }
 
     float4 color = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -238,13 +258,19 @@ __global__ __launch_bounds__(256) void composite_kernel(const CompParams P) {
 }  // namespace
 
 // Declared in svr_api.hip, which validates the arguments, orders the launch against the uploads and marks it as a
-// render.  table: the device copy of the transfer function (K entries of RGBA).  interp: SVR_INTERP_*.
+// render.  table: the device copy of the transfer function (K entries of RGBA).  interp: SVR_INTERP_*.  cut_planes:
+// cut_count x abcd of svr_set_cut_planes (host), cut_mode: SVR_CUT_*; any plane selects the CUT instantiations, which
+// doubles the kernels of this file (8 LOD counts x 3 element sizes x TINT x LIN x CUT = 192).
 hipError_t svr_launch_composite(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr,
                                 const svr_composite_params& cp, const svr_outputs& out, const float* table, int K,
-                                int interp, hipStream_t stream) {
+                                int interp, const float* cut_planes, uint32_t cut_count, int cut_mode,
+                                hipStream_t stream) {
     CompParams P;
     memset(&P, 0, sizeof(P));
-    fill_ray_params(c, cam, fr, out, P);
+    CutPlanes cut;
+    cut.count = cut_count; cut.mode = cut_mode;
+    if (cut_count) memcpy(cut.abcd, cut_planes, sizeof(float) * 4 * cut_count);
+    fill_ray_params(c, cam, fr, out, cut, P);
     const svr_material& m = c->material;
     P.clim0 = m.clim[0]; P.clim1 = m.clim[1];
     P.alpha_cutoff = cp.alpha_cutoff;
@@ -252,10 +278,12 @@ hipError_t svr_launch_composite(const svr_ctx* c, const svr_camera& cam, const s
     for (int l = 0; l < c->num_lods; ++l) fill_lod_common(c->lod[l], P.L[l]);
     const dim3 grid((unsigned)(P.tiles_x * P.tiles_y));
     const size_t lds = (size_t)K * 4 * sizeof(float);
-    return with_bool(interp == SVR_INTERP_LINEAR, [&](auto lin) {
-        return with_bool(cp.color_by_label != 0, [&](auto tint) {
-            return with_lods_esh(c->num_lods, esh_of(c), [&](auto nl, auto esh) {
-                return launch_tiles(composite_kernel<nl(), esh(), tint(), lin()>, grid, lds, stream, P);
+    return with_bool(cut_count != 0, [&](auto cutv) {
+        return with_bool(interp == SVR_INTERP_LINEAR, [&](auto lin) {
+            return with_bool(cp.color_by_label != 0, [&](auto tint) {
+                return with_lods_esh(c->num_lods, esh_of(c), [&](auto nl, auto esh) {
+                    return launch_tiles(composite_kernel<nl(), esh(), tint(), lin(), cutv()>, grid, lds, stream, P);
+                });
             });
         });
     });

@@ -66,6 +66,7 @@ struct IsoParams {
     float*    normal;
     uint32_t* counters;
     IsoLod L[SVR_MAX_LODS];
+    CutParams cut;             // after L[]: every argument above keeps the offset it had before cuts existed
 };
 
 using IsoArgs = const IsoParams __attribute__((address_space(4)));     // the kernel arguments' own address space
@@ -185,7 +186,13 @@ constexpr int ISO_LIN_GROUP = 4;   // linear sampling: a stretch's samples go in
 
 // LIN: S(iter) and D(p) are the linear sample of svr.h (svr_set_interpolation); label and LOD of the hit stay the
 // nearest sample's.
-template <int NL, int ESH, bool LIN>
+// CUT: S(iter) has no value where svr_set_cut_planes cuts (coarse and refine searches; D(p) reads the uncut field), and
+// a hit whose predecessor in search order was cut is a cap: its normal is the cutting plane's.  The ray's kept (ANY) or
+// cut (ALL) index interval is found once (cut_span); a coarse sample is masked by cut_sample, and a stretch in which
+// every live lane's samples are cut is passed like an empty one (counted as skipped) before the cell maxima are
+// looked at.  The few fractional points (refine, the cap test) evaluate the predicate itself.  Without CUT nothing of
+// this is compiled.
+template <int NL, int ESH, bool LIN, bool CUT>
 __global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
     const int nblocks = P.tiles_x * P.tiles_y;
     const int t = xcd_remap((int)blockIdx.x, nblocks);
@@ -205,22 +212,39 @@ __global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
     const float iso = P.iso;
     const IsoArgs* kq = (const IsoArgs*)__builtin_amdgcn_kernarg_segment_ptr();     // P itself: the only argument
 
+    const CutParams* cq = (const CutParams*)&kq->cut;       // wave-uniform: scalar loads, like the LOD table
+    CutRay cr = { { 0.f, 0.f, 0.f }, { 0.f, 0.f, 0.f } };
+    CutSpan span = { 0, 0 };
+    bool cut_all = false;
+    if constexpr (CUT) {
+        cut_all = cq->all != 0;
+        cr = cut_ray(R, P.size);
+        span = cut_span(*cq, cr, nsteps);
+    }
+
     int cand = -1;                       // the coarse candidate
     uint32_t marched = 0u, skipped = 0u; // wave-uniform
     for (int i0 = 0; ; i0 += ISO_UNROLL) {
         const bool live = cand < 0 && i0 < nsteps;
         if (!__any(live)) break;
+        bool work = live;
+        if constexpr (CUT) {             // a stretch whose samples are all cut, for every live lane: nothing to fetch
+            const int e = min(i0 + ISO_UNROLL, nsteps);
+            const bool all_cut = cut_all ? (span.lo <= i0 && e <= span.hi) : (e <= span.lo || i0 >= span.hi);
+            work = live && !all_cut;
+            if (!__any(work)) { ++skipped; continue; }
+        }
         // The LOD table is read from the kernel arguments afresh in each stretch (scalar loads from the constant
         // cache) instead of being held in SGPRs across the loop (composite_kernels.hip does the same).
         asm volatile("" : "+s"(kq));
         const IsoLod* Ls = (const IsoLod*)kq->L;
         if (P.skip) {
-            const bool veto = live && stretch_may_reach<NL, ESH, LIN>(Ls, P, R, i0);
+            const bool veto = work && stretch_may_reach<NL, ESH, LIN>(Ls, P, R, i0);
             if (!__any(veto)) { ++skipped; continue; }
         }
         ++marched;
         if constexpr (LIN) {
-            if (live) {
+            if (work) {
 #pragma unroll
                 for (int g0 = 0; g0 < ISO_UNROLL; g0 += ISO_LIN_GROUP) {
                     if (cand >= 0 || i0 + g0 >= nsteps) break;       // the first one wins: later groups cannot
@@ -238,6 +262,7 @@ __global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
                         svr_linear::LaneLod q = svr_linear::lane_lod_zero();
                         const char* base = static_cast<const char*>(Ls[0].density);   // a valid address for the unused gathers
                         bool done = i0 + g0 + j >= nsteps;
+                        if constexpr (CUT) done = done || cut_sample(span, cut_all, i0 + g0 + j);
 #pragma unroll
                         for (int l = 0; l < NL; ++l) {
                             size_t idx;
@@ -265,7 +290,7 @@ __global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
                         if (held[j] && svr_linear::blend(v8[j], frac[j]) >= iso) cand = i0 + g0 + j;
                 }
             }
-        } else if (live) {
+        } else if (work) {
             const char* addr[ISO_UNROLL];
             bool held[ISO_UNROLL];
 #pragma unroll
@@ -278,6 +303,7 @@ __global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
                 held[j] = false;                                     // no LOD holds it (or past the ray's end)
                 addr[j] = static_cast<const char*>(Ls[0].density);   // a valid address for the unused gather
                 bool done = i0 + j >= nsteps;
+                if constexpr (CUT) done = done || cut_sample(span, cut_all, i0 + j);
 #pragma unroll
                 for (int l = 0; l < NL; ++l) {
                     size_t idx;
@@ -311,16 +337,26 @@ __global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
         const IsoLod* Ls = (const IsoLod*)kq->L;
         // refine: the first sub-sample between the samples cand - 1 and cand that reaches the level
         float iter = (float)cand;
+        float pred = (float)(cand - 1);                              // CUT: the point examined just before the hit
         if (cand > 0 && P.refine > 1) {
             const float base = (float)(cand - 1), rf = (float)P.refine;
             for (int k = 1; k < P.refine; ++k) {
                 const float it = base + (float)k / rf;
+                if constexpr (CUT) { if (cut_at(*cq, cr, it)) { pred = it; continue; } }     // no value here
                 const float cx = R.start.x + it * R.step.x, cy = R.start.y + it * R.step.y, cz = R.start.z + it * R.step.z;
                 float v = 0.0f; int lod = 0; size_t idx = 0;
                 if (value_at<NL, ESH, LIN>(Ls, cx * P.size[0], cy * P.size[1], cz * P.size[2], v, lod, idx) && v >= iso) {
                     iter = it;
                     break;
                 }
+                pred = it;
+            }
+        }
+        int cap = -1;                                                // CUT: the plane of a cap
+        if constexpr (CUT) {
+            if (cand > 0 && cut_at(*cq, cr, pred)) {
+                for (uint32_t k = cq->count; k-- > 0u; )             // the lowest index wins
+                    if (cut_all ? !cut_behind(*cq, k, cr, iter) : cut_behind(*cq, k, cr, pred)) cap = (int)k;
             }
         }
         const float cx = R.start.x + iter * R.step.x, cy = R.start.y + iter * R.step.y, cz = R.start.z + iter * R.step.z;
@@ -363,6 +399,12 @@ __global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
         const float gl = sqrtf(dot3(G, G));
         n = v;
         if (gl > 0.0f && gl < INFINITY) n = { -G.x / gl, -G.y / gl, -G.z / gl };
+        if constexpr (CUT) {
+            if (cap >= 0) {                                          // the cutting plane's unit normal, facing the viewer
+                n = { cq->nhat[cap][0], cq->nhat[cap][1], cq->nhat[cap][2] };
+                if (dot3(n, v) < 0.0f) n = { -n.x, -n.y, -n.z };
+            }
+        }
         f3 l = v;
         if (!P.headlight) l = { P.light[0], P.light[1], P.light[2] };
         const f3 hv = { l.x + v.x, l.y + v.y, l.z + v.z };
@@ -401,12 +443,18 @@ __global__ __launch_bounds__(256) void iso_kernel(const IsoParams P) {
 }  // namespace
 
 // Declared in svr_api.hip, which validates the arguments, orders the launch against the uploads and marks it as a
-// render.  interp: SVR_INTERP_*.
+// render.  interp: SVR_INTERP_*.  cut_planes: cut_count x abcd of svr_set_cut_planes (host), cut_mode: SVR_CUT_*; any
+// plane selects the CUT instantiations, which doubles the kernels of this file (8 LOD counts x 3 element sizes x LIN x
+// CUT = 96).
 hipError_t svr_launch_iso(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr, const svr_iso_params& ip,
-                          const svr_outputs& out, int interp, hipStream_t stream) {
+                          const svr_outputs& out, int interp, const float* cut_planes, uint32_t cut_count, int cut_mode,
+                          hipStream_t stream) {
     IsoParams P;
     memset(&P, 0, sizeof(P));
-    fill_ray_params(c, cam, fr, out, P);
+    CutPlanes cut;
+    cut.count = cut_count; cut.mode = cut_mode;
+    if (cut_count) memcpy(cut.abcd, cut_planes, sizeof(float) * 4 * cut_count);
+    fill_ray_params(c, cam, fr, out, cut, P);
     memcpy(P.world_inv, cam.world_inv, sizeof(P.world_inv));
     P.iso = ip.iso_value; P.refine = ip.refine;
     for (int a = 0; a < 3; ++a) { P.base[a] = ip.iso_color[a]; P.light[a] = ip.light_direction[a]; }
@@ -429,9 +477,11 @@ hipError_t svr_launch_iso(const svr_ctx* c, const svr_camera& cam, const svr_fra
     }
     P.skip = any_cells && !ip.no_skip && ip.iso_value > 0.0f;
     const dim3 grid((unsigned)(P.tiles_x * P.tiles_y));
-    return with_bool(interp == SVR_INTERP_LINEAR, [&](auto lin) {
-        return with_lods_esh(c->num_lods, esh_of(c), [&](auto nl, auto esh) {
-            return launch_tiles(iso_kernel<nl(), esh(), lin()>, grid, 0, stream, P);
+    return with_bool(cut_count != 0, [&](auto cutv) {
+        return with_bool(interp == SVR_INTERP_LINEAR, [&](auto lin) {
+            return with_lods_esh(c->num_lods, esh_of(c), [&](auto nl, auto esh) {
+                return launch_tiles(iso_kernel<nl(), esh(), lin(), cutv()>, grid, 0, stream, P);
+            });
         });
     });
 }

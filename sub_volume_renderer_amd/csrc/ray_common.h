@@ -1,6 +1,7 @@
 // What slice_kernels.hip, composite_kernels.hip and iso_kernels.hip share: the small vector helpers, the ring wrap and
-// the LOD window test, the colour and pick helpers, the ray set-up of the march, and the host code that fills the
-// parameter blocks and picks an instantiation.
+// the LOD window test, the colour and pick helpers, the ray set-up of the march, the cut planes of the composite and iso
+// kernels (predicate, per-ray index interval), and the host code that fills the parameter blocks and picks an
+// instantiation.
 //
 // Arithmetic contract: strict IEEE f32 without contraction (-ffp-contract=off), operation order as written in svr.h.
 // The device helpers restate the march's (march_kernel.hip: `mat_vec`, `wrap`, `lod_texel`, `pick_field`, `hsv_to_rgb`,
@@ -173,6 +174,102 @@ __device__ __forceinline__ bool setup_ray(const Params& P, int i, int j, Ray& R)
     return true;
 }
 
+// ---- cut planes (svr_set_cut_planes, include/svr.h) -------------------------------------------------------------------
+
+// The context's planes as the caller gave them (host state, kept by svr_api.hip).
+struct CutPlanes {
+    uint32_t count;
+    int32_t  mode;                                 // SVR_CUT_ANY / SVR_CUT_ALL
+    float    abcd[SVR_MAX_CUT_PLANES][4];          // world space
+};
+
+// What the CUT kernels read: the planes carried into data space for this call's world transform, and the unit normals
+// of the caps.  Appended to CompParams / IsoParams AFTER L[], so every other kernel argument keeps its offset.
+struct CutParams {
+    uint32_t count;
+    int32_t  all;                                  // 1: SVR_CUT_ALL
+    float    gh[SVR_MAX_CUT_PLANES][4];            // g_k.xyz, h_k
+    float    nhat[SVR_MAX_CUT_PLANES][3];
+};
+
+// The predicate of svr.h along one ray: E_k(iter) = A_k + iter * B_k, behind_k = E_k < 0.  p0 and sd are the ray's
+// data-space origin and step.  A_k and B_k are recomputed from the (wave-uniform, scalar) plane data where they are
+// needed rather than held per lane: 8 planes would take 16 VGPRs across the sample loop.
+struct CutRay { f3 p0, sd; };
+
+__device__ __forceinline__ CutRay cut_ray(const Ray& R, const float* size) {
+    CutRay c;
+    c.p0 = { R.start.x * size[0] - 0.5f, R.start.y * size[1] - 0.5f, R.start.z * size[2] - 0.5f };
+    c.sd = { R.step.x * size[0], R.step.y * size[1], R.step.z * size[2] };
+    return c;
+}
+
+template <class Cut>
+__device__ __forceinline__ bool cut_behind(const Cut& C, uint32_t k, const CutRay& c, float iter) {
+    const f3 g = { C.gh[k][0], C.gh[k][1], C.gh[k][2] };
+    const float A = dot3(g, c.p0) + C.gh[k][3];
+    const float B = dot3(g, c.sd);
+    return (A + iter * B) < 0.0f;
+}
+
+template <class Cut>
+__device__ __forceinline__ bool cut_at(const Cut& C, const CutRay& c, float iter) {
+    const bool all = C.all != 0;
+    bool cut = all;
+    for (uint32_t k = 0; k < C.count; ++k) {
+        const bool behind = cut_behind(C, k, c, iter);
+        cut = all ? (cut && behind) : (cut || behind);
+    }
+    return cut;
+}
+
+// The integer samples of a ray in one interval: with `all` the samples i in [lo, hi) are the CUT ones, without it they
+// are the KEPT ones.  Along a ray E_k is monotone in iter under f32 rounding too (iter * B_k is a monotone rounded
+// product, adding A_k is monotone), so each plane's behind-set over i = 0 .. nsteps-1 is a prefix or a suffix: its two
+// ends tell which, and a binary search on the predicate itself finds where it flips (at most 24 probes: nsteps <= 2^24).
+// Under ANY the kept samples are the intersection of the complements, under ALL the cut samples are the intersection of
+// the behind-sets: an interval either way.  The interval agrees with the predicate exactly because it is made of
+// nothing else.
+struct CutSpan { int lo, hi; };
+
+template <class Cut>
+__device__ __forceinline__ CutSpan cut_span(const Cut& C, const CutRay& c, int nsteps) {
+    const bool all = C.all != 0;
+    CutSpan s = { 0, nsteps };
+    for (uint32_t k = 0; k < C.count; ++k) {
+        const f3 g = { C.gh[k][0], C.gh[k][1], C.gh[k][2] };
+        const float A = dot3(g, c.p0) + C.gh[k][3];
+        const float B = dot3(g, c.sd);
+        const bool b0 = (A + 0.0f * B) < 0.0f;
+        const bool bn = (A + (float)(nsteps - 1) * B) < 0.0f;
+        int lo = 0, hi = nsteps;                   // the behind-set [lo, hi)
+        if (b0 == bn) {
+            if (!b0) hi = 0;
+        } else {
+            int a = 0, b = nsteps - 1;             // behind(a) == b0, behind(b) != b0
+            while (b - a > 1) {
+                const int m = a + ((b - a) >> 1);
+                const bool bm = (A + (float)m * B) < 0.0f;
+                if (bm == b0) a = m; else b = m;
+            }
+            if (b0) hi = b; else lo = b;
+        }
+        if (!all) {                                // the kept set of this plane: the complement, an interval too
+            if (lo == 0) { lo = hi; hi = nsteps; } else { hi = lo; lo = 0; }
+        }
+        s.lo = max(s.lo, lo);
+        s.hi = min(s.hi, hi);
+    }
+    if (s.hi <= s.lo) s.lo = s.hi = 0;             // one form for the empty interval
+    return s;
+}
+
+// two integer compares (one after the subtraction)
+__device__ __forceinline__ bool cut_sample(const CutSpan& s, bool all, int i) {
+    const bool inside = (uint32_t)(i - s.lo) < (uint32_t)(s.hi - s.lo);
+    return inside == all;
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------
 
 // f32 matrix helpers in the contract's operation order (see oracle/lmip_oracle.c header)
@@ -199,8 +296,25 @@ void fill_lod_common(const LodStorage& S, Lod& Q) {
 }
 
 // camera, material and outputs of a mode that draws along the march's rays
+// the per-call host part of the cut predicate (svr.h): g_k, h_k from the call's world matrix, and the unit normals
+inline void fill_cut_params(const CutPlanes& cut, const float* m, CutParams& Q) {
+    Q.count = cut.count;
+    Q.all = cut.mode == SVR_CUT_ALL;
+    for (uint32_t k = 0; k < cut.count; ++k) {
+        const float a = cut.abcd[k][0], b = cut.abcd[k][1], c = cut.abcd[k][2], d = cut.abcd[k][3];
+        Q.gh[k][0] = (m[0] * a + m[1] * b) + m[2] * c;
+        Q.gh[k][1] = (m[4] * a + m[5] * b) + m[6] * c;
+        Q.gh[k][2] = (m[8] * a + m[9] * b) + m[10] * c;
+        Q.gh[k][3] = ((m[12] * a + m[13] * b) + m[14] * c) - d;
+        const float len = sqrtf((a * a + b * b) + c * c);
+        Q.nhat[k][0] = a / len; Q.nhat[k][1] = b / len; Q.nhat[k][2] = c / len;
+    }
+}
+
 template <class Params>
-void fill_ray_params(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr, const svr_outputs& out, Params& P) {
+void fill_ray_params(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr, const svr_outputs& out,
+                     const CutPlanes& cut, Params& P) {
+    fill_cut_params(cut, cam.world, P.cut);
     float tmp[16];
     mat_mul4(cam.world_inv, cam.cam_inv, tmp);               // as svr_render (vs_main.wgsl:22, left-assoc)
     mat_mul4(tmp, cam.proj_inv, P.ndc_to_data);

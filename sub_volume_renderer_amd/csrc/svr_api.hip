@@ -51,10 +51,12 @@ hipError_t svr_launch_slab(const svr_ctx* c, const svr_slab_params& sp, const fl
 // composite_kernels.hip (same reason).  table: the device copy of the transfer function, K entries of RGBA.
 hipError_t svr_launch_composite(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr,
                                 const svr_composite_params& cp, const svr_outputs& out, const float* table, int K,
-                                int interp, hipStream_t stream);
-// iso_kernels.hip (same reason).
+                                int interp, const float* cut_planes, uint32_t cut_count, int cut_mode,
+                                hipStream_t stream);
+// iso_kernels.hip (same reason).  cut_planes: cut_count x abcd of svr_set_cut_planes (host), cut_mode: SVR_CUT_*.
 hipError_t svr_launch_iso(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr, const svr_iso_params& ip,
-                          const svr_outputs& out, int interp, hipStream_t stream);
+                          const svr_outputs& out, int interp, const float* cut_planes, uint32_t cut_count, int cut_mode,
+                          hipStream_t stream);
 
 namespace {
 
@@ -62,13 +64,19 @@ namespace {
 // part of the kernel-source stamp).  Like the colour table of svr_set_material, every new table goes into a fresh
 // device buffer; the replaced ones are freed once the device has drained (or with the context).  dev is null until a
 // table has been set.  The entry also carries the context's svr_set_interpolation mode (same reason): no entry means
-// SVR_INTERP_NEAREST.
+// SVR_INTERP_NEAREST.  So does the state of svr_set_cut_planes: no entry means no planes.
+struct CutState {
+    uint32_t count;
+    int mode;
+    float planes[SVR_MAX_CUT_PLANES][4];
+};
 struct TransferTable {
     const svr_ctx* ctx;
     float* dev;
     int K;
     std::vector<float*> retired;
     int interp;
+    CutState cut;
 };
 std::mutex g_tf_mu;
 std::vector<TransferTable> g_tf;
@@ -76,6 +84,21 @@ std::vector<TransferTable> g_tf;
 TransferTable* transfer_table(const svr_ctx* c) {       // (under g_tf_mu)
     for (auto& t : g_tf) if (t.ctx == c) return &t;
     return nullptr;
+}
+
+TransferTable* transfer_table_or_new(const svr_ctx* c) {       // (under g_tf_mu)
+    TransferTable* t = transfer_table(c);
+    if (!t) {
+        g_tf.push_back(TransferTable{ c, nullptr, 0, {}, SVR_INTERP_NEAREST, CutState{} });
+        t = &g_tf.back();
+    }
+    return t;
+}
+
+CutState cut_state_of(const svr_ctx* c) {
+    std::lock_guard<std::mutex> lock(g_tf_mu);
+    const TransferTable* t = transfer_table(c);
+    return t ? t->cut : CutState{};
 }
 
 int interpolation_of(const svr_ctx* c) {
@@ -1279,11 +1302,7 @@ int svr_set_transfer_function(svr_ctx* c, const float* rgba, int32_t K) {
         svr_set_error("svr_set_transfer_function: hipMemcpy failed"); return SVR_ERR_HIP;
     }
     std::lock_guard<std::mutex> lock(g_tf_mu);
-    TransferTable* t = transfer_table(c);
-    if (!t) {
-        g_tf.push_back(TransferTable{ c, nullptr, 0, {}, SVR_INTERP_NEAREST });
-        t = &g_tf.back();
-    }
+    TransferTable* t = transfer_table_or_new(c);
     if (t->dev) t->retired.push_back(t->dev);        // composites still in flight keep reading the old table
     if (t->retired.size() > 32) {                    // bounded: drain once in a long while
         SVR_HIP_TRY(hipDeviceSynchronize());
@@ -1300,12 +1319,29 @@ int svr_set_interpolation(svr_ctx* c, int mode) {
     SVR_REQUIRE(mode == SVR_INTERP_NEAREST || mode == SVR_INTERP_LINEAR,
                 "svr_set_interpolation: mode must be SVR_INTERP_NEAREST or SVR_INTERP_LINEAR");
     std::lock_guard<std::mutex> lock(g_tf_mu);
-    TransferTable* t = transfer_table(c);
-    if (!t) {
-        g_tf.push_back(TransferTable{ c, nullptr, 0, {}, SVR_INTERP_NEAREST });
-        t = &g_tf.back();
-    }
+    TransferTable* t = transfer_table_or_new(c);
     t->interp = mode;
+    return SVR_OK;
+}
+
+int svr_set_cut_planes(svr_ctx* c, const float* planes, uint32_t count, int mode) {
+    SVR_REQUIRE(c, "svr_set_cut_planes: null ctx");
+    SVR_REQUIRE(count <= SVR_MAX_CUT_PLANES, "svr_set_cut_planes: at most SVR_MAX_CUT_PLANES planes");
+    SVR_REQUIRE(planes || count == 0, "svr_set_cut_planes: null planes with a non-zero count");
+    SVR_REQUIRE(mode == SVR_CUT_ANY || mode == SVR_CUT_ALL, "svr_set_cut_planes: mode must be SVR_CUT_ANY or SVR_CUT_ALL");
+    CutState fresh{};
+    fresh.count = count; fresh.mode = mode;
+    for (uint32_t k = 0; k < count; ++k) {
+        const float* p = planes + 4 * k;
+        for (int a = 0; a < 4; ++a) {
+            SVR_REQUIRE(fabsf(p[a]) < INFINITY, "svr_set_cut_planes: every component must be finite");
+            fresh.planes[k][a] = p[a];
+        }
+        const float len = sqrtf((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]);
+        SVR_REQUIRE(len > 0.0f && len < INFINITY, "svr_set_cut_planes: a plane's normal must have a finite, non-zero length");
+    }
+    std::lock_guard<std::mutex> lock(g_tf_mu);
+    transfer_table_or_new(c)->cut = fresh;
     return SVR_OK;
 }
 
@@ -1324,7 +1360,9 @@ int svr_composite(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, const 
         if (t) { table = t->dev; K = t->K; interp = t->interp; }
     }
     SVR_REQUIRE(table, "svr_composite: svr_set_transfer_function has not been called");
-    return SVR_DRAW_ORDERED(c, stream, svr_launch_composite(c, *cam, f, *cp, *out, table, K, interp, s));
+    const CutState cut = cut_state_of(c);
+    return SVR_DRAW_ORDERED(c, stream, svr_launch_composite(c, *cam, f, *cp, *out, table, K, interp, &cut.planes[0][0],
+                                                            cut.count, cut.mode, s));
 }
 
 int svr_iso(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, const svr_iso_params* ip, const svr_outputs* out,
@@ -1347,7 +1385,9 @@ int svr_iso(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, const svr_is
         const float len2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
         SVR_REQUIRE(fabsf(sqrtf(len2) - 1.0f) <= 1e-3f, "svr_iso: light_direction must be finite and of unit length");
     }
-    return SVR_DRAW_ORDERED(c, stream, svr_launch_iso(c, *cam, f, *ip, *out, interpolation_of(c), s));
+    const CutState cut = cut_state_of(c);
+    return SVR_DRAW_ORDERED(c, stream, svr_launch_iso(c, *cam, f, *ip, *out, interpolation_of(c), &cut.planes[0][0],
+                                                      cut.count, cut.mode, s));
 }
 
 int svr_untile_stripes(svr_ctx* c, const void* gathered, void* frame_out, int frame_w, int frame_h,

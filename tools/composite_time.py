@@ -59,6 +59,9 @@ def main():
     ap.add_argument("--volume-n", type=int, default=1024)
     ap.add_argument("--interpolation", default="nearest", choices=("nearest", "linear", "both"),
                     help="svr_set_interpolation mode of the timed calls; both: nearest and linear alternate, case by case")
+    ap.add_argument("--cut", default="none", choices=("none", "half", "wedge", "all-cases"),
+                    help="svr_set_cut_planes state of the timed calls (tools/cut_cases.py: planes through the camera's focus "
+                         "that open the side towards the camera); all-cases: none, half and wedge alternate, case by case")
     ap.add_argument("--stats", default=None, help="print the composite kernels of a --stats run's CSV instead of timing")
     args = ap.parse_args()
     if args.stats:
@@ -69,6 +72,7 @@ def main():
     import torch
 
     import bench
+    import cut_cases
     from sub_volume_renderer_amd import _native as N, synth, testing
 
     if not torch.cuda.is_available():
@@ -110,40 +114,46 @@ def main():
             lmip_full = int(vol.render(cam, W, H, count_steps=True).steps.to(torch.int64).sum())
             m.lmip_threshold = threshold
         m.render_mode, m.transfer_function, m.alpha_cutoff, m.color_by_label = "composite", tf, cutoff, False
-        res = vol.render(cam, W, H, count_steps=True)
-        samples = int(res.steps.to(torch.int64).sum())
-        hits = int((res.flags == N.SVR_PIX_HIT).sum())
-        handle = vol.prepare()
-        vol._push_transfer_function()
-        cb, fb = vol.camera_block(cam), vol.frame_block(W, H, None)
-        cp = N.CompositeParams(cutoff, 0)
-        ob = N.Outputs()
-        ob.rgba, ob.depth, ob.label, ob.flags = (getattr(res, k).data_ptr() for k in ("rgba", "depth", "label", "flags"))
-        ob.steps, ob.pick, ob.pick_id = None, None, vol.id
-        argv = (handle, C.byref(cb), C.byref(fb), C.byref(cp), C.byref(ob), C.c_void_p(stream.cuda_stream))
+        for cut in cut_cases.names_of(args.cut):
+            planes, mode = cut_cases.cut_case(cut, spec.cam_position, spec.cam_target)
+            m.cut_planes, m.cut_mode = planes, mode
+            res = vol.render(cam, W, H, count_steps=True)
+            samples = int(res.steps.to(torch.int64).sum())
+            hits = int((res.flags == N.SVR_PIX_HIT).sum())
+            handle = vol.prepare()
+            vol._push_transfer_function()
+            cb, fb = vol.camera_block(cam), vol.frame_block(W, H, None)
+            cp = N.CompositeParams(cutoff, 0)
+            ob = N.Outputs()
+            ob.rgba, ob.depth, ob.label, ob.flags = (getattr(res, k).data_ptr() for k in ("rgba", "depth", "label", "flags"))
+            ob.steps, ob.pick, ob.pick_id = None, None, vol.id
+            argv = (handle, C.byref(cb), C.byref(fb), C.byref(cp), C.byref(ob), C.c_void_p(stream.cuda_stream))
 
-        def calls(k=args.calls):
-            for _ in range(k):
-                N.check(lib.svr_composite(*argv), "svr_composite")
+            def calls(k=args.calls):
+                for _ in range(k):
+                    N.check(lib.svr_composite(*argv), "svr_composite")
 
-        for interp in (("nearest", "linear") if args.interpolation == "both" else (args.interpolation,)):
-            # (samples and hit_pixels are the nearest render's: the rays are the same, linear values end some earlier or later)
-            N.check(lib.svr_set_interpolation(handle, N.INTERPOLATIONS[interp]), "svr_set_interpolation")
-            calls(5)
-            call_s = [window(calls) / args.calls for _ in range(args.boxes)]
-            hold = int(max(4.0 * max(call_s) * args.calls, 0.02) / per_cycle)
-            gpu_s = [window(calls, hold) / args.calls for _ in range(args.boxes)]
-            torch.cuda.synchronize()
-            gpu = float(np.median(gpu_s))
-            row = {"case": case, "storage": vol._rings.density_storage, "interpolation": interp, "table_entries": tf.size,
-                   "alpha_cutoff": cutoff, "call_ms": round(float(np.median(call_s)) * 1e3, 4), "gpu_ms": round(gpu * 1e3, 4),
-                   "gpu_ms_boxes": [round(t * 1e3, 4) for t in gpu_s],
-                   "calls_per_box": args.calls, "samples": samples, "samples_per_s": float(f"{samples / gpu:.4g}"),
-                   "hit_pixels": hits}
-            if case == "a":
-                row["lmip_full_samples"] = lmip_full
-            print(json.dumps(row), flush=True)
+            for interp in (("nearest", "linear") if args.interpolation == "both" else (args.interpolation,)):
+                # (samples and hit_pixels are the nearest render's: the rays are the same, linear values end some earlier or later)
+                N.check(lib.svr_set_interpolation(handle, N.INTERPOLATIONS[interp]), "svr_set_interpolation")
+                N.check(cut_cases.push(lib, handle, planes, mode, N.CUT_MODES), "svr_set_cut_planes")
+                calls(5)
+                call_s = [window(calls) / args.calls for _ in range(args.boxes)]
+                hold = int(max(4.0 * max(call_s) * args.calls, 0.02) / per_cycle)
+                gpu_s = [window(calls, hold) / args.calls for _ in range(args.boxes)]
+                torch.cuda.synchronize()
+                gpu = float(np.median(gpu_s))
+                row = {"case": case, "storage": vol._rings.density_storage, "interpolation": interp, "cut": cut, "table_entries": tf.size,
+                       "alpha_cutoff": cutoff, "call_ms": round(float(np.median(call_s)) * 1e3, 4), "gpu_ms": round(gpu * 1e3, 4),
+                       "gpu_ms_boxes": [round(t * 1e3, 4) for t in gpu_s],
+                       "calls_per_box": args.calls, "samples": samples, "samples_per_s": float(f"{samples / gpu:.4g}"),
+                       "hit_pixels": hits}
+                if case == "a":
+                    row["lmip_full_samples"] = lmip_full
+                print(json.dumps(row), flush=True)
+        m.cut_planes = ()
         N.check(lib.svr_set_interpolation(handle, 0), "svr_set_interpolation")
+        N.check(cut_cases.push(lib, handle, [], "ANY", N.CUT_MODES), "svr_set_cut_planes")
     vol.close()
 
 

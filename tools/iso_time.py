@@ -15,6 +15,10 @@ The four are timed in alternation, --rounds times.  Also printed: the hit pixels
 visits (the steps plane), and the wave-stretches marched and skipped (svr_iso_params::skip_counters).  Kernel durations
 proper come from a separate traced run:
 
+--cut none|half|wedge|all-cases: the svr_set_cut_planes state of the timed svr_iso and svr_composite calls (tools/
+cut_cases.py: planes through the camera's focus that open the side towards the camera); all-cases: the three alternate
+case by case inside one command and every row names its cut.  The march (B) knows no cuts and runs under "none" only.
+
 usage: python tools/iso_time.py [--camera K1|K2] [--storage native|float32] [--level 0.5] [--calls 20] [--boxes 3]
        rocprofv3 --kernel-trace --stats -d DIR -o iso --output-format csv -- python tools/iso_time.py --calls 20 --boxes 1
        python tools/iso_time.py --stats DIR          (no GPU needed: the kernels of DIR's *kernel_stats.csv)
@@ -62,6 +66,8 @@ def main():
     ap.add_argument("--volume-n", type=int, default=1024)
     ap.add_argument("--interpolation", default="nearest", choices=("nearest", "linear", "both"),
                     help="svr_set_interpolation mode of the timed calls; both: nearest and linear alternate, case by case")
+    ap.add_argument("--cut", default="none", choices=("none", "half", "wedge", "all-cases"),
+                    help="cut planes of the timed iso / composite calls; all-cases: none, half and wedge alternate")
     ap.add_argument("--stats", default=None, help="print the kernels of a --stats run's CSV instead of timing")
     args = ap.parse_args()
     if args.stats:
@@ -72,6 +78,7 @@ def main():
     import torch
 
     import bench
+    import cut_cases
     from sub_volume_renderer_amd import TransferFunction, _native as N, synth, testing
 
     if not torch.cuda.is_available():
@@ -113,29 +120,32 @@ def main():
                       "iso_value": level, "refine": args.refine}), flush=True)
 
     interps = ("nearest", "linear") if args.interpolation == "both" else (args.interpolation,)
+    cuts = {c: cut_cases.cut_case(c, spec.cam_position, spec.cam_target) for c in cut_cases.names_of(args.cut)}
     # one counted render of each (steps planes, skip counters), then the production argument structs
     m.render_mode = "iso"
     info = {}
-    for interp in [i for i in interps if i != "nearest"] + ["nearest"]:     # (nearest last: what the yardsticks below compare with)
-        m.interpolation = interp
-        out = vol.iso_outputs(W, H, count_steps=True, normal=False, skip_counters=True)
-        vol.render(cam, W, H, count_steps=True, out=out)
-        torch.cuda.synchronize()
-        marched, skipped = (int(v) for v in out.skip_counters.cpu().numpy().view(np.uint32))
-        info[("iso", interp)] = {"hit_pixels": int((out.flags == N.SVR_PIX_HIT).sum()),
-                                 "coarse_samples": int(out.steps.to(torch.int64).sum()),
-                                 "wave_stretches_marched": marched, "wave_stretches_skipped": skipped,
-                                 "skipped_share": round(skipped / max(marched + skipped, 1), 4)}
+    for cut in [c for c in cuts if c != "none"] + ["none"]:
+        m.cut_planes, m.cut_mode = cuts.get(cut, ([], "ANY"))
+        for interp in [i for i in interps if i != "nearest"] + ["nearest"]:     # (nearest, uncut last: what the yardsticks below compare with)
+            m.interpolation = interp
+            out = vol.iso_outputs(W, H, count_steps=True, normal=False, skip_counters=True)
+            vol.render(cam, W, H, count_steps=True, out=out)
+            torch.cuda.synchronize()
+            marched, skipped = (int(v) for v in out.skip_counters.cpu().numpy().view(np.uint32))
+            info[("iso", interp, cut)] = {"hit_pixels": int((out.flags == N.SVR_PIX_HIT).sum()),
+                                          "coarse_samples": int(out.steps.to(torch.int64).sum()),
+                                          "wave_stretches_marched": marched, "wave_stretches_skipped": skipped,
+                                          "skipped_share": round(skipped / max(marched + skipped, 1), 4)}
     iso_steps = out.steps.clone()
     m.render_mode = "composite"
     res = vol.render(cam, W, H, count_steps=True)
     torch.cuda.synchronize()
-    info[("A", "nearest")] = {"hit_pixels": int((res.flags == N.SVR_PIX_HIT).sum()), "samples": int(res.steps.to(torch.int64).sum()),
+    info[("A", "nearest", "none")] = {"hit_pixels": int((res.flags == N.SVR_PIX_HIT).sum()), "samples": int(res.steps.to(torch.int64).sum()),
                  "pixels_with_iso_steps": int((res.steps == iso_steps).sum())}
     m.render_mode = "lmip"
     res = vol.render(cam, W, H)
     torch.cuda.synchronize()
-    info[("B", "nearest")] = {"hit_pixels": int((res.flags == N.SVR_PIX_HIT).sum())}
+    info[("B", "nearest", "none")] = {"hit_pixels": int((res.flags == N.SVR_PIX_HIT).sum())}
 
     handle = vol.prepare()
     vol._push_transfer_function()
@@ -157,8 +167,10 @@ def main():
     if args.only:
         runs = {k: v for k, v in runs.items() if k in args.only.split(",")}
     for rnd in range(args.rounds):
-        for name, one, interp in ((n, o, i) for n, o in runs.items() for i in (interps if n != "B" else ("nearest",))):
+        for name, one, interp, cut in ((n, o, i, c) for n, o in runs.items() for i in (interps if n != "B" else ("nearest",))
+                                       for c in (cuts if n != "B" else ("none",))):
             N.check(lib.svr_set_interpolation(handle, N.INTERPOLATIONS[interp]), "svr_set_interpolation")
+            N.check(cut_cases.push(lib, handle, *cuts.get(cut, ([], "ANY")), N.CUT_MODES), "svr_set_cut_planes")
 
             def calls(k=args.calls, one=one):
                 for _ in range(k):
@@ -169,12 +181,13 @@ def main():
             hold = int(max(4.0 * max(call_s) * args.calls, 0.02) / per_cycle)
             gpu_s = [window(calls, hold) / args.calls for _ in range(args.boxes)]
             torch.cuda.synchronize()
-            row = {"case": name, "interpolation": interp, "round": rnd, "call_ms": round(float(np.median(call_s)) * 1e3, 4),
+            row = {"case": name, "interpolation": interp, "cut": cut, "round": rnd, "call_ms": round(float(np.median(call_s)) * 1e3, 4),
                    "gpu_ms": round(float(np.median(gpu_s)) * 1e3, 4), "gpu_ms_min": round(min(gpu_s) * 1e3, 4),
                    "gpu_ms_max": round(max(gpu_s) * 1e3, 4), "calls_per_box": args.calls}
-            row.update(info.get(("iso" if name.startswith("iso") else name, interp), {}))
+            row.update(info.get(("iso" if name.startswith("iso") else name, interp, cut), {}))
             print(json.dumps(row), flush=True)
     N.check(lib.svr_set_interpolation(handle, 0), "svr_set_interpolation")
+    N.check(cut_cases.push(lib, handle, [], "ANY", N.CUT_MODES), "svr_set_cut_planes")
     vol.close()
 
 

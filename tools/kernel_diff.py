@@ -2,7 +2,11 @@
 """Compare the gfx950 kernels of two builds of the same translation unit, kernel by kernel: the code-object metadata
 (registers, spills, scratch, LDS, kernel-argument size) and the disassembly.  Only reads object files.
 
-usage: kernel_diff.py BEFORE.o AFTER.o [more pairs ...]
+usage: kernel_diff.py [-v] [--rename REGEX REPL] BEFORE.o AFTER.o [more pairs ...]
+
+--rename REGEX REPL: re.sub applied to the mangled kernel names of AFTER before pairing, for kernels that gained a
+template parameter (e.g. a trailing `false`: --rename 'Lb0E(EEvNS_\d+\w+ParamsE)$' '\1'); kernels of AFTER that then have
+no partner in BEFORE are counted as new, not as a difference.
 
 Per kernel, one of
   identical   the instruction text is the same (addresses and encodings stripped)
@@ -79,6 +83,11 @@ def demangle(names):
 def main():
     args = [a for a in sys.argv[1:] if a != "-v"]
     verbose = "-v" in sys.argv[1:]
+    rename = None
+    if "--rename" in args:
+        k = args.index("--rename")
+        rename = (re.compile(args[k + 1]), args[k + 2])
+        del args[k:k + 3]
     if not args or len(args) % 2:
         sys.exit(__doc__)
     bad = 0
@@ -87,10 +96,17 @@ def main():
             ca, cb = code_object(before, td, "a"), code_object(after, td, "b")
             na, nb = notes_of(ca), notes_of(cb)
             ka, kb = kernels_of(ca), kernels_of(cb)
+            if rename:
+                paired = {rename[0].sub(rename[1], n): n for n in nb}
+                new = sorted(n for r, n in paired.items() if r not in na)
+                nb = {r: nb[n] for r, n in paired.items() if r in na}
+                kb = {r: kb[n] for r, n in paired.items() if r in na}
             names = sorted(na)
             dem = demangle(names)
             tally = {"identical": [], "renamed": [], "changed": []}
             print(f"== {os.path.basename(after)}: {len(na)} kernels before, {len(nb)} after")
+            if rename:
+                print(f"   new in the second build: {len(new)} kernels")
             for n in sorted(set(na) ^ set(nb)):
                 print(f"   only in one build: {n}")
                 bad += 1
