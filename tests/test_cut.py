@@ -29,8 +29,8 @@ SOLID = np.full((N, N, N), 200, np.uint8)
 def iso(rings, M, planes, mode="ANY", linear=False, **params):
     p = dict(SHADE)
     p.update(params)
-    return cut_twin.iso_cut(rings, M, SIZE, material(), FRAME, FRAME, p, pick_id=5, cut_planes=planes, cut_mode=mode,
-                            linear=linear)
+    return iso_twin.iso_twin(rings, M, SIZE, material(), FRAME, FRAME, p, pick_id=5, cut_planes=planes, cut_mode=mode,
+                             linear=linear)
 
 
 def tilted_world():
@@ -192,8 +192,8 @@ TABLE = np.array([(0.1, 0.2, 0.9, 0.0), (0.9, 0.5, 0.1, 0.15), (1.0, 1.0, 0.4, 0
 
 def comp(rings, M, planes, mode="ANY", linear=False, tint=False):
     mat = material(clim=(0.0, 255.0))
-    return cut_twin.composite_cut(rings, M, SIZE, mat, TABLE, FRAME, FRAME, 0.95, tint, pick_id=5, cut_planes=planes,
-                                  cut_mode=mode, linear=linear)
+    return composite_twin.composite_twin(rings, M, SIZE, mat, TABLE, FRAME, FRAME, 0.95, tint, pick_id=5,
+                                         cut_planes=planes, cut_mode=mode, linear=linear)
 
 
 @pytest.mark.parametrize("linear", [False, True])
@@ -259,7 +259,7 @@ def test_a_composite_ray_cut_in_the_middle_composes_the_two_outer_runs_in_order(
     planes = [(-1.0, 0.0, 0.0, -10.2), (1.0, 0.0, 0.0, 20.3)]
     T = np.array([(0.2, 0.4, 0.9, 0.0), (1.0, 0.3, 0.1, 0.25)], f32)
     mat = material(clim=(0.0, 255.0))
-    out = cut_twin.composite_cut([ring(d)], spec.matrices(), SIZE, mat, T, FRAME, FRAME, 0.999, cut_planes=planes, cut_mode="ALL")
+    out = composite_twin.composite_twin([ring(d)], spec.matrices(), SIZE, mat, T, FRAME, FRAME, 0.999, cut_planes=planes, cut_mode="ALL")
     kept = [i for i in range(NSTEPS) if not 38 <= i <= 73]
     R = G = B = A = f32(0.0)
     w_best, best = f32(0.0), -1
@@ -283,10 +283,10 @@ def test_a_composite_ray_cut_in_the_middle_composes_the_two_outer_runs_in_order(
     word = int(out["pick"][0, 0])
     assert (word >> 20) & 0x3FFF == int(f32(best) * f32(1.0 / NSTEPS) * f32(16383.0)) or \
         abs(((word >> 20) & 0x3FFF) - best / NSTEPS * 16383.0) <= 1.0
-    uncut = cut_twin.composite_cut([ring(d)], spec.matrices(), SIZE, mat, T, FRAME, FRAME, 0.999)
+    uncut = composite_twin.composite_twin([ring(d)], spec.matrices(), SIZE, mat, T, FRAME, FRAME, 0.999)
     assert np.abs(uncut["rgba"] - out["rgba"]).max() > 1e-2
     # under ANY the same two planes keep nothing (no point is in front of both), and a cut-off first half moves `first`
-    half = cut_twin.composite_cut([ring(d)], spec.matrices(), SIZE, mat, T, FRAME, FRAME, 0.999, cut_planes=planes[1:])
+    half = composite_twin.composite_twin([ring(d)], spec.matrices(), SIZE, mat, T, FRAME, FRAME, 0.999, cut_planes=planes[1:])
     assert (half["first"] == 74).all() and (half["steps"] > 74).all()
 
 

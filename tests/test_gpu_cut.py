@@ -1,6 +1,6 @@
-"""GPU: svr_composite and svr_iso under svr_set_cut_planes (include/svr.h, "cut planes") == the numpy restatement of
-tests/cut_twin.py, compared as tests/test_gpu_iso.py::check does: flags, steps, label and pick bit for bit, rgba, depth
-and normal within 1e-4, no pixel left out.  Two cuts, both opening the side towards camera K1: H, a half-space (ANY),
+"""GPU: svr_composite and svr_iso under svr_set_cut_planes (include/svr.h, "cut planes") == their numpy twins with the
+predicate of tests/cut_twin.py, compared as tests/test_gpu_iso.py::check does: flags, steps, label and pick bit for bit,
+rgba, depth and normal within 1e-4, no pixel left out.  Two cuts, both opening the side towards camera K1: H, a half-space (ANY),
 and W, a wedge (ALL, the octant).  Over the iso grid (u8 / u16 / float32 rings, with and without labels, 1 and 3 LODs,
 the demo, perspective and orthographic cameras, a rotated and scaled world, clipping planes as well, linear sampling),
 the composite mode with and without the label tint under both samplings, and: no planes == planes set and cleared, the
@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-import cut_twin
+from composite_twin import composite_twin
 from iso_twin import iso_twin, material_of, matrices_of, params_of
 from oracle import lmip
 from slice_twin import DISCARD, HIT, MISS
@@ -42,17 +42,17 @@ def set_cut(vol, kind, c):
 
 def iso_ref(vol, cam, spec, rings, orac, **kw):
     m = vol.material
-    return cut_twin.iso_cut(rings, matrices_of(vol, cam), orac.volume_dimensions_shader, material_of(spec.material),
-                            kw.pop("width", spec.width), kw.pop("height", spec.height), params_of(m), pick_id=vol.id,
-                            cut_planes=m.cut_planes, cut_mode=m.cut_mode, linear=(m.interpolation == "linear"), **kw)
+    return iso_twin(rings, matrices_of(vol, cam), orac.volume_dimensions_shader, material_of(spec.material),
+                    kw.pop("width", spec.width), kw.pop("height", spec.height), params_of(m), pick_id=vol.id,
+                    cut_planes=m.cut_planes, cut_mode=m.cut_mode, linear=(m.interpolation == "linear"), **kw)
 
 
 def comp_ref(vol, cam, spec, rings, orac, tf, **kw):
     m = vol.material
-    return cut_twin.composite_cut(rings, matrices_of(vol, cam), orac.volume_dimensions_shader, material_of(spec.material),
-                                  tf.device_table(vol._volume_dimensions), kw.pop("width", spec.width),
-                                  kw.pop("height", spec.height), m.alpha_cutoff, m.color_by_label, pick_id=vol.id,
-                                  cut_planes=m.cut_planes, cut_mode=m.cut_mode, linear=(m.interpolation == "linear"), **kw)
+    return composite_twin(rings, matrices_of(vol, cam), orac.volume_dimensions_shader, material_of(spec.material),
+                          tf.device_table(vol._volume_dimensions), kw.pop("width", spec.width),
+                          kw.pop("height", spec.height), m.alpha_cutoff, m.color_by_label, pick_id=vol.id,
+                          cut_planes=m.cut_planes, cut_mode=m.cut_mode, linear=(m.interpolation == "linear"), **kw)
 
 
 def iso_render(vol, cam, w, h, **kw):
