@@ -13,6 +13,7 @@
 
 #include "svr_internal.h"
 #include "twin_address.h"
+#include "slab_box.h"
 
 namespace {
 
@@ -600,32 +601,6 @@ __device__ __forceinline__ uint32_t dot2_u16(uint32_t a, uint32_t b, uint32_t c)
 // a register with no defined value and no instruction (lanes whose value is never looked at)
 template <typename T> __device__ __forceinline__ T undefined_value() { T v; asm volatile("" : "=v"(v)); return v; }
 
-// Six wave64 reductions at once: min of a, b, c and max of d, e, f over all lanes; every lane of row 3
-// (lane 63 is read) ends up with the results.  Written out with DPP-fused VOP2 ops and the six
-// independent chains interleaved, so the two wait states a DPP read needs after a VALU write of its
-// source are always covered by the other chains (the compiler emits mov + nop + mov_dpp + op per step).
-__device__ __forceinline__ void wave_min3_max3(int& a, int& b, int& c, int& d, int& e, int& f) {
-#define SVR_STEP6(ctrl)                              \
-    "v_min_i32_dpp %0, %0, %0 " ctrl "\n"            \
-    "v_min_i32_dpp %1, %1, %1 " ctrl "\n"            \
-    "v_min_i32_dpp %2, %2, %2 " ctrl "\n"            \
-    "v_max_i32_dpp %3, %3, %3 " ctrl "\n"            \
-    "v_max_i32_dpp %4, %4, %4 " ctrl "\n"            \
-    "v_max_i32_dpp %5, %5, %5 " ctrl "\n"
-    asm volatile("s_nop 1\n"
-                 SVR_STEP6("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
-                 SVR_STEP6("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
-                 SVR_STEP6("row_half_mirror row_mask:0xf bank_mask:0xf")
-                 SVR_STEP6("row_mirror row_mask:0xf bank_mask:0xf")
-                 SVR_STEP6("row_bcast:15 row_mask:0xa bank_mask:0xf")
-                 SVR_STEP6("row_bcast:31 row_mask:0xc bank_mask:0xf")
-                 "s_nop 0"
-                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f));
-#undef SVR_STEP6
-    a = __builtin_amdgcn_readlane(a, 63); b = __builtin_amdgcn_readlane(b, 63); c = __builtin_amdgcn_readlane(c, 63);
-    d = __builtin_amdgcn_readlane(d, 63); e = __builtin_amdgcn_readlane(e, 63); f = __builtin_amdgcn_readlane(f, 63);
-}
-
 // wave64 min / max of an int via DPP (no LDS traffic); result is wave-uniform.  DPP-fused VOP2 ops
 // (a DPP read needs two wait states after the VALU write of its source)
 template <bool MAX>
@@ -1200,20 +1175,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
                     const float2_t ey = coord_pair<SCALED>(it, Rsy, Rty, ssy);
                     const float2_t ez = coord_pair<SCALED>(it, Rsz, Rtz, ssz);
                     // exact box of the wave's samples: min / max per axis over the live lanes
+#if defined(SVR_EXPERIMENTS) && defined(SVR_EXP_NO_BOX_REDUCE)
                     const int big = 0x7fffffff;
                     int lx = live ? min((int)ex.x, (int)ex.y) : big, hx = live ? max((int)ex.x, (int)ex.y) : -big;
                     int ly = live ? min((int)ey.x, (int)ey.y) : big, hy = live ? max((int)ey.x, (int)ey.y) : -big;
                     int lz = live ? min((int)ez.x, (int)ez.y) : big, hz = live ? max((int)ez.x, (int)ez.y) : -big;
-#if defined(SVR_EXPERIMENTS) && defined(SVR_EXP_NO_BOX_REDUCE)
-                    // ablation (wrong pixels): lane 0's box stands for the wave's — the six DPP reductions are gone
+                    // ablation (wrong pixels): lane 0's box stands for the wave's — the reduction is gone
                     lx = __builtin_amdgcn_readfirstlane(lx); ly = __builtin_amdgcn_readfirstlane(ly); lz = __builtin_amdgcn_readfirstlane(lz);
                     hx = lx + 12; hy = ly + 10; hz = lz + 10;
+                    const bool none_live = lx == big;
 #else
-                    wave_min3_max3(lx, ly, lz, hx, hy, hz);
+                    // (a LOD stages bricks only where its indices fit 16 bits — svr_slab_box_fits16, fill_params —: the six
+                    //  bounds travel as three words of packed halves and one packed-min reduction, slab_box.h)
+                    const svr_slab_box box = svr_slab_box_reduce(svr_slab_box_pack(ex.x, ex.y, ey.x, ey.y, ez.x, ez.y, live));
+                    const int lx = box.lx, ly = box.ly, lz = box.lz, hx = box.hx, hy = box.hy, hz = box.hz;
+                    const bool none_live = box.none;
 #endif
                     if (COUNT) ++c_slabs;
                     lap(8);
-                    if (lx == big) { run = 0; break; }                   // no live lane left
+                    if (none_live) { run = 0; break; }                   // no live lane left
                     // 16-voxel groups aligned in RING space, so a group never straddles the wrap
                     constexpr int GSH = 4 - ESH;                             // log2 of the voxels in a 16-byte group
                     const int gx0 = lx - ((lx + L.addw[0]) & ((1 << GSH) - 1));
@@ -1235,9 +1215,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
                     // group) plus a wave-uniform z term, so the loop body is one VALU add.  Lanes of a padding
                     // group, or beyond the plane's rows, are masked off (they leave their slot alone).
                     const float rgp = __builtin_amdgcn_rcpf((float)gp);     // 1 ulp is plenty: see below
-                    const int rows_per = (int)(64.5f * rgp);                 // floor(64 / gp): x.5 / gp is never an integer
-                    const int ly_lane = (int)(((float)lane + 0.5f) * rgp);   // lane / gp, exactly
-                    const int g_lane = lane - ly_lane * gp;
+                    const int ly_lane = (int)(((float)lane + 0.5f) * rgp);   // lane / gp, exactly: x.5 / gp is never an integer
+                    // floor(64 / gp) on the scalar side, from the last lane's row: floor(63 / gp), and one more where gp divides 64
+                    const int rows_per = __builtin_amdgcn_readlane(ly_lane, 63) + ((gp & (gp - 1)) == 0 && gp <= 64 ? 1 : 0);
+                    const int g_lane = lane - __mul24(ly_lane, gp);        // (both below 2^23: a full-rate multiply)
                     uint32_t wx = (uint32_t)(gx0 + (g_lane << GSH) + L.addw[0]);
                     wx = min(wx, wx - L.ring[0]);
                     wx <<= ESH;                                              // byte offset inside the ring row

@@ -16,6 +16,7 @@
 #include "ring_parts.h"
 #include "march_pow2.h"
 #include "twin_address.h"
+#include "slab_box.h"
 
 static thread_local std::string g_err;
 void svr_set_error(const std::string& msg) { g_err = msg; }
@@ -1098,7 +1099,8 @@ static int fill_params(svr_ctx* c, const svr_camera* cam, const svr_frame* fr, c
             const int slab = std::max(8, (smax > 0.75f ? 16 : (smax > 0.375f ? 32 : 64)) >> slab_shift);
             // (ring rows must be whole 16-byte groups: 16 / 8 / 4 voxels for u8 / u16 / f32 rings)
             bool ok = ((Q.ring[0] * des) & 15u) == 0u && (brick_mask >> l & 1);
-            for (int a = 0; a < 3; ++a) ok = ok && (long long)Q.off[a] + (long long)Q.shape[a] < 32768;
+            // (the wave's box is reduced as packed 16-bit halves, slab_box.h: a LOD whose window leaves [0, 32767] stages none)
+            ok = ok && svr_slab_box_mode_of(Q.off, Q.shape) == SVR_SLAB_BOX_PACKED;
             Q.slab = ok ? slab : 0;
             // empty-space skipping: cell tests every `skip_batches` batches of 8 iterations, such that a ray
             // (0.8 voxels of the finest level per iteration, fs_main.wgsl:20) travels at most one cell between two
