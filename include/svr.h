@@ -662,6 +662,53 @@ int  svr_set_interpolation(svr_ctx* ctx, int mode);
 #define SVR_CUT_ALL 1
 int  svr_set_cut_planes(svr_ctx* ctx, const float* planes, uint32_t count, int mode);
 
+/* ---- intensity histograms of the resident rings: what values does a window hold?  (No counterpart in the reference;
+ * the histogram panel behind a transfer-function editor, an auto-contrast button, a first iso_value, the distribution
+ * of a selected object.)  An addition within ABI version 9: one new symbol and two new structs, nothing older changes.
+ * One streaming pass over the ring in HBM; nothing is copied to the host.
+ * Defined HERE (numpy restatement: tests/histogram_twin.py):
+ *   considered  the logical voxels (x, y, z) of LOD `lod` in the intersection of box and window, the window being [offset, offset + shape) of
+ *               svr_set_lod_state and the box [box_off, box_off + box_shape) (use_box == 0: the whole window).  A window
+ *               of None (offset == shape == 0) and a box that misses the window consider nothing.  With
+ *               selected_count > 0 only the voxels whose label texel is one of selected[0 .. selected_count); without
+ *               label rings every label reads as 0, as in svr_read_region.
+ *   texel       ring slot (x % ring_x, y % ring_y, z % ring_z) of the row-major ring (the micro-block copy is never
+ *               read); v = the element converted to f32, exactly for u8 and u16, as the nearest sample of the other
+ *               modes converts it.
+ *   binning     in f32, in this order, with no fused operations; inv = (float)K / (hi - lo), computed once on the host:
+ *                 v is NaN   tail[2] += 1
+ *                 v < lo     tail[0] += 1
+ *                 v > hi     tail[1] += 1
+ *                 otherwise  j = min((int)((v - lo) * inv), K - 1);  counts[j] += 1      (closed at hi, as numpy's is)
+ *               A range wider than f32 (hi - lo overflows to inf) is accepted: inv is then 0 and every value inside the
+ *               range counts in bin 0, those whose v - lo overflows too (the product inf * 0 is NaN) included.
+ *   range       the minimum and maximum of the considered values that are not NaN, those under and over included;
+ *               (+inf, -inf) when there are none.
+ *   tail[3]     the number of considered voxels = sum(counts) + tail[0] + tail[1] + tail[2].
+ * The call OVERWRITES its outputs: it zeroes them on `stream`, then fills them.  Counts are integers, so the result
+ * does not depend on the order in which the device visits the voxels.  A render-thread call ordered like svr_slice: it
+ * waits for published uploads, and later uploads are ordered behind it.  Enqueued on `stream`; asynchronous.  The
+ * material, the variant, the interpolation and the cut planes are not read.
+ * SVR_ERR_INVALID, with nothing enqueued and the outputs untouched, for: a NULL params, outputs or counts; lod out of
+ * range; bins outside 1 .. SVR_HIST_MAX_BINS; lo or hi not finite, or lo >= hi; an inv that is not finite; a negative
+ * box_shape component (with use_box != 0); selected == NULL with selected_count > 0. */
+#define SVR_HIST_MAX_BINS 4096          /* = SVR_TF_MAX_ENTRIES: one bin per transfer-function entry */
+typedef struct svr_histogram_params {
+    int32_t lod;
+    int32_t use_box;                    /* 0: the LOD's whole resident window */
+    int32_t box_off[3], box_shape[3];   /* LOD-l logical voxels, shader order: the coordinates of svr_lod_state */
+    float   lo, hi;                     /* finite, lo < hi */
+    int32_t bins;                       /* K, 1 .. SVR_HIST_MAX_BINS */
+    const uint32_t* selected;           /* DEVICE, sorted ascending, like svr_outline's; NULL when the count is 0 */
+    uint32_t selected_count;            /* 0: every voxel */
+} svr_histogram_params;
+typedef struct svr_histogram_outputs {  /* DEVICE pointers; counts required, the others may be NULL */
+    uint64_t* counts;                   /* K */
+    uint64_t* tail;                     /* 4: [0] under, [1] over, [2] NaN, [3] voxels considered */
+    float*    range;                    /* 2: min and max of the considered non-NaN values; (+inf, -inf) when there are none */
+} svr_histogram_outputs;
+int  svr_histogram(svr_ctx* ctx, const svr_histogram_params* params, const svr_histogram_outputs* out, void* stream);
+
 /* ---- sync */
 int  svr_sync(svr_ctx* ctx);                 /* both streams idle */
 int  svr_sync_uploads(svr_ctx* ctx);         /* upload stream idle */

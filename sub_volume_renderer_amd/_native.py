@@ -172,6 +172,26 @@ class IsoParams(C.Structure):
     ]
 
 
+class HistogramParams(C.Structure):
+    _fields_ = [
+        ("lod", C.c_int32),
+        ("use_box", C.c_int32),
+        ("box_off", C.c_int32 * 3),
+        ("box_shape", C.c_int32 * 3),
+        ("lo", C.c_float),
+        ("hi", C.c_float),
+        ("bins", C.c_int32),
+        ("selected", C.c_void_p),
+        ("selected_count", C.c_uint32),
+    ]
+
+
+class HistogramOutputs(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("counts", "tail", "range")]
+
+
+HIST_MAX_BINS = 4096                                # SVR_HIST_MAX_BINS
+
 INTERPOLATIONS = {"nearest": 0, "linear": 1}      # SVR_INTERP_*
 CUT_MODES = {"ANY": 0, "ALL": 1}                  # SVR_CUT_*
 MAX_CUT_PLANES = 8                                # SVR_MAX_CUT_PLANES
@@ -231,6 +251,7 @@ SIGNATURES = {
                           C.c_void_p]),
     "svr_set_interpolation": (C.c_int, [C.c_void_p, C.c_int]),
     "svr_set_cut_planes": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int]),
+    "svr_histogram": (C.c_int, [C.c_void_p, C.POINTER(HistogramParams), C.POINTER(HistogramOutputs), C.c_void_p]),
     "svr_sync": (C.c_int, [C.c_void_p]),
     "svr_sync_uploads": (C.c_int, [C.c_void_p]),
     "svr_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),

@@ -103,6 +103,105 @@ def _vec3(name, value):
     return [float(c) for c in vals]
 
 
+_HIST_WIDE = 2.0 ** 100     # float32 rings, range=None: the K = 1 pass that only takes min and max runs over (-2^100, 2^100)
+
+
+@dataclass
+class HistogramResult:
+    """What one ``svr_histogram`` call wrote (include/svr.h).  ``counts`` stays on the device; the scalars are read
+    from the device (after a synchronisation) the first time one of them is asked for."""
+
+    counts: "object"          # torch i64 [bins]     voxels per bin (bit pattern of the u64 counts)
+    tail: "object"            # torch i64 [4]        under, over, NaN, considered
+    range: "object"           # torch f32 [2]        min and max of the considered non-NaN values
+    edges: np.ndarray         # float64 [bins + 1]   bin j is [edges[j], edges[j + 1]), the last one closed
+    lod: int
+    selected: "object | None" = None    # torch i32 [n]  the sorted id list the kernel searched (kept alive with the result)
+    _host: "tuple | None" = None
+
+    def _scalars(self):
+        if self._host is None:
+            import torch
+
+            torch.cuda.synchronize(self.counts.device)
+            t, r = self.tail.cpu().numpy(), self.range.cpu().numpy()
+            self._host = (int(t[0]), int(t[1]), int(t[2]), int(t[3]), float(r[0]), float(r[1]))
+        return self._host
+
+    under = property(lambda self: self._scalars()[0], doc="considered voxels below the range")
+    over = property(lambda self: self._scalars()[1], doc="considered voxels above the range")
+    nan = property(lambda self: self._scalars()[2], doc="considered voxels that are NaN")
+    considered = property(lambda self: self._scalars()[3], doc="voxels considered: sum(counts) + under + over + nan")
+    min = property(lambda self: self._scalars()[4], doc="smallest considered non-NaN value (+inf: none)")
+    max = property(lambda self: self._scalars()[5], doc="largest considered non-NaN value (-inf: none)")
+
+
+def histogram_edges(lo: float, hi: float, bins: int) -> np.ndarray:
+    """The K + 1 bin edges of a histogram over the float32 range [lo, hi], in float64."""
+    lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    return lo + (hi - lo) * (np.arange(bins + 1, dtype=np.float64) / float(bins))
+
+
+def clim_from_counts(counts, edges, percentiles=(0.5, 99.5)):
+    """Contrast limits from a histogram's counts alone, in float64: with N = sum(counts) and c_j their cumulative sum,
+    the left edge of the first bin with c_j > N * p_lo / 100 and the right edge of the first bin with
+    c_j >= N * p_hi / 100; one bin width apart when the two coincide.  ``ValueError`` when N == 0."""
+    counts = np.asarray(counts, np.float64).reshape(-1)
+    edges = np.asarray(edges, np.float64).reshape(-1)
+    if len(edges) != len(counts) + 1:
+        raise ValueError("edges must hold one more entry than counts")
+    try:
+        p_lo, p_hi = (float(p) for p in percentiles)
+    except (TypeError, ValueError):
+        raise ValueError("percentiles must be two numbers") from None
+    if not 0.0 <= p_lo <= p_hi <= 100.0:
+        raise ValueError("percentiles must satisfy 0 <= low <= high <= 100")
+    total = counts.sum()
+    if not total > 0:
+        raise ValueError("auto_clim: the histogram is empty (nothing resident in the box, or every voxel outside the range)")
+    cum = np.cumsum(counts)
+    k = len(counts)
+    j_lo = min(int(np.argmax(cum > total * p_lo / 100.0)) if (cum > total * p_lo / 100.0).any() else k - 1, k - 1)
+    j_hi = min(int(np.argmax(cum >= total * p_hi / 100.0)) if (cum >= total * p_hi / 100.0).any() else k - 1, k - 1)
+    lower, upper = float(edges[j_lo]), float(edges[j_hi + 1])
+    if upper <= lower:                 # only with low == high, when a cumulative count meets the target exactly
+        upper = lower + float(edges[j_lo + 1] - edges[j_lo])
+    return lower, upper
+
+
+def label_ids(labels) -> np.ndarray:
+    """An iterable of label ids -> the sorted, unique uint32 array ``svr_histogram`` searches."""
+    if isinstance(labels, (str, bytes)):
+        raise ValueError("labels must be an iterable of integer ids")
+    try:
+        vals = [v for v in labels]
+    except TypeError:
+        raise ValueError("labels must be an iterable of integer ids") from None
+    if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in vals):
+        raise ValueError("labels must hold integers")
+    if not vals:
+        raise ValueError("labels must hold at least one id (None counts every voxel)")
+    if min(int(v) for v in vals) < 0 or max(int(v) for v in vals) > 0xFFFFFFFF:
+        raise ValueError("label ids must lie in [0, 2^32)")
+    return np.unique(np.array([int(v) for v in vals], np.uint64)).astype(np.uint32)
+
+
+def lod_box(begin, end, scale_factor):
+    """A voxel box ``[begin, end)`` of the finest scale (numpy order, the convention of ``crop_planes``) in the voxels
+    of a LOD with ``scale_factor``: ``(floor(begin * scale), ceil(end * scale))`` per axis, as ints (numpy order)."""
+    begin = np.asarray(begin, np.float64).reshape(-1)
+    end = np.asarray(end, np.float64).reshape(-1)
+    if begin.shape != (3,) or end.shape != (3,) or not (np.all(np.isfinite(begin)) and np.all(np.isfinite(end))):
+        raise ValueError("begin and end must be three finite numbers each")
+    if not np.all(end > begin):
+        raise ValueError("end must exceed begin on every axis")
+    scale = np.asarray(scale_factor, np.float64)
+    b, e = np.floor(begin * scale), np.ceil(end * scale)
+    if np.any(np.abs(b) >= 2.0 ** 31) or np.any(np.abs(e) >= 2.0 ** 31) or np.any(e - b >= 2.0 ** 31):
+        raise ValueError("the box does not fit 32-bit voxel coordinates")
+    return tuple(int(v) for v in b), tuple(int(v) for v in e)
+
+
 _SLICE_CACHE_SIZES = 4      # output sets kept per volume: e.g. the three axis views of a viewer, each of its own size
 
 
@@ -825,6 +924,113 @@ class SubVolume(_HasWorld):
         import torch
 
         return torch.cuda.current_stream(self._rings.device).cuda_stream if stream is None else stream
+
+    # -- what values are resident? ------------------------------------------------
+    def histogram(self, lod: int = 0, bins: int = 256, range=None, box=None, labels=None, stream=None) -> HistogramResult:
+        """Intensity histogram of what LOD ``lod`` holds in HBM (definition: ``svr_histogram`` in include/svr.h): one
+        pass over the ring on the device, nothing is read back.  ``range=(lo, hi)``: the binned interval, closed at
+        ``hi``; None: (0, 256) on uint8 rings, (0, 65536) on uint16 rings, and on float32 rings the minimum and maximum
+        of the considered values, found by a first pass (``ValueError`` when nothing is resident, the values are all
+        equal, or one of them is infinite).  ``box=(begin, end)``: only the voxels of that box of the finest scale
+        (numpy order, the convention of :meth:`crop_planes`), mapped to the LOD by floor(begin * scale) and
+        ceil(end * scale); None: the LOD's whole resident window.  ``labels``: count only voxels whose label is one of
+        these ids (a volume without segmentation reads label 0 everywhere).  Asynchronous on the current torch stream
+        (or ``stream``); the volume's pending uniforms are pushed and asynchronous uploads polled first, as
+        :meth:`render_slice` does."""
+        import torch
+
+        if isinstance(lod, bool) or not isinstance(lod, (int, np.integer)) or not 0 <= lod < len(self.wrapping_buffers):
+            raise ValueError(f"lod must be an integer in 0 .. {len(self.wrapping_buffers) - 1}")
+        if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= bins <= N.HIST_MAX_BINS:
+            raise ValueError(f"bins must be an integer in 1 .. {N.HIST_MAX_BINS}")
+        lod, bins = int(lod), int(bins)
+        storage = self._rings.density_storage
+        if range is not None:
+            try:
+                lo, hi = (float(v) for v in range)
+            except (TypeError, ValueError):
+                raise ValueError("range must be two numbers (lo, hi)") from None
+            with np.errstate(over="ignore"):
+                lo32, hi32 = np.float32(lo), np.float32(hi)
+            if not (np.isfinite(lo32) and np.isfinite(hi32) and lo32 < hi32):
+                raise ValueError("range must be finite in float32 with lo < hi")
+        hp = N.HistogramParams()
+        hp.lod = lod
+        if box is not None:
+            try:
+                begin, end = box
+            except (TypeError, ValueError):
+                raise ValueError("box must be (begin, end)") from None
+            b, e = lod_box(begin, end, self.wrapping_buffers[lod].scale_factor)
+            hp.use_box = 1
+            hp.box_off[:] = b[::-1]                                   # shader order
+            hp.box_shape[:] = [ev - bv for bv, ev in zip(b[::-1], e[::-1])]
+        ids = None
+        if labels is not None:
+            ids = label_ids(labels)
+        handle = self.prepare()
+        dev = torch.device("cuda", self._rings.device)
+        sel = None
+        if ids is not None:
+            sel = torch.from_numpy(ids.view(np.int32)).to(dev)
+            if stream is not None:
+                # the id list was copied on torch's stream and is read on the caller's: the copy must have landed, and
+                # the caching allocator must not hand the memory out again before that stream has passed the kernel
+                torch.cuda.current_stream(dev).synchronize()
+                sel.record_stream(torch.cuda.ExternalStream(int(stream), device=dev))
+        hp.selected = sel.data_ptr() if sel is not None else None
+        hp.selected_count = int(sel.numel()) if sel is not None else 0
+        stream_given = stream is not None
+        stream = self._plane_stream(stream)
+
+        def run(lo, hi, k):
+            counts = torch.empty(k, dtype=torch.int64, device=dev)
+            tail = torch.empty(4, dtype=torch.int64, device=dev)
+            rng = torch.empty(2, dtype=torch.float32, device=dev)
+            hp.lo, hp.hi, hp.bins = lo, hi, k
+            ho = N.HistogramOutputs(counts.data_ptr(), tail.data_ptr(), rng.data_ptr())
+            N.check(N.lib().svr_histogram(handle, C.byref(hp), C.byref(ho), C.c_void_p(stream)), "svr_histogram")
+            if stream_given:                                          # outputs dropped early must outlive the kernel too
+                for t in (counts, tail, rng):
+                    t.record_stream(torch.cuda.ExternalStream(int(stream), device=dev))
+            return HistogramResult(counts, tail, rng, histogram_edges(lo, hi, k), lod, selected=sel)
+
+        if range is None:
+            if storage == "uint8":
+                lo, hi = 0.0, 256.0
+            elif storage == "uint16":
+                lo, hi = 0.0, 65536.0
+            else:
+                first = run(-_HIST_WIDE, _HIST_WIDE, 1)
+                lo, hi = first.min, first.max                         # synchronises
+                if not lo <= hi:
+                    raise ValueError("histogram: nothing is resident in the box (pass range=)")
+                if lo == hi:
+                    raise ValueError(f"histogram: every considered value equals {lo} (pass range=)")
+        return run(float(np.float32(lo)), float(np.float32(hi)), bins)
+
+    def auto_clim(self, percentiles=(0.5, 99.5), lod=None, bins=None, range=None, box=None, labels=None):
+        """Contrast limits ``(low, high)`` that clip ``percentiles`` of the resident values, from :meth:`histogram`'s
+        counts (:func:`clim_from_counts`; values outside ``range`` do not count).  ``lod=None``: the coarsest LOD that
+        has a window, which covers the most space for the fewest bytes.  ``bins=None``: 256 on uint8 rings, else 4096.
+        Only returns the pair: assign it to ``material.clim``."""
+        try:
+            p_lo, p_hi = (float(p) for p in percentiles)
+        except (TypeError, ValueError):
+            raise ValueError("percentiles must be two numbers") from None
+        if not 0.0 <= p_lo <= p_hi <= 100.0:
+            raise ValueError("percentiles must satisfy 0 <= low <= high <= 100")
+        if lod is None:
+            if self._submitted != self._completed:
+                self.poll_uploads()
+            resident = [i for i, b in enumerate(self.wrapping_buffers) if b._current_logical_roi_in_pixels is not None]
+            if not resident:
+                raise ValueError("auto_clim: no LOD has a resident window")
+            lod = resident[-1]
+        if bins is None:
+            bins = 256 if self._rings.density_storage == "uint8" else N.HIST_MAX_BINS
+        res = self.histogram(lod=lod, bins=bins, range=range, box=box, labels=labels)
+        return clim_from_counts(res.counts.cpu().numpy(), res.edges, (p_lo, p_hi))
 
     def synchronize(self):
         N.check(N.lib().svr_sync(self._rings.handle), "svr_sync")

@@ -58,6 +58,11 @@ hipError_t svr_launch_composite(const svr_ctx* c, const svr_camera& cam, const s
 hipError_t svr_launch_iso(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr, const svr_iso_params& ip,
                           const svr_outputs& out, int interp, const float* cut_planes, uint32_t cut_count, int cut_mode,
                           hipStream_t stream);
+// histogram_kernels.hip (same reason).  lo, n: box and window intersected, in the LOD's logical voxels (an n <= 0: nothing
+// to count); inv = (float)K / (hi - lo); everything checked by svr_histogram.
+hipError_t svr_launch_histogram(const svr_ctx* c, int lod, const int64_t lo[3], const int64_t n[3], float flo, float fhi,
+                                float inv, int K, const uint32_t* sel, uint32_t nsel, const svr_histogram_outputs& out,
+                                hipStream_t stream);
 
 namespace {
 
@@ -1287,6 +1292,33 @@ int svr_slab(svr_ctx* c, const svr_slab_params* sp, const svr_frame* fr, const s
     SVR_REQUIRE((uintptr_t)out->rgba % 16 == 0, "svr_slab: rgba must be 16-byte aligned");
     const int twin_mode = (c->variant & 256) ? 0 : ((c->variant & 512) ? 2 : 1);
     return SVR_DRAW_ORDERED(c, stream, svr_launch_slab(c, *sp, dw, f, *out, twin_mode, interpolation_of(c), s));
+}
+
+int svr_histogram(svr_ctx* c, const svr_histogram_params* hp, const svr_histogram_outputs* out, void* stream) {
+    SVR_REQUIRE(c && hp && out && out->counts, "svr_histogram: null argument");
+    SVR_REQUIRE(hp->lod >= 0 && hp->lod < c->num_lods, "svr_histogram: lod out of range");
+    SVR_REQUIRE(hp->bins >= 1 && hp->bins <= SVR_HIST_MAX_BINS, "svr_histogram: bins must be in 1 .. 4096");
+    SVR_REQUIRE(isfinite(hp->lo) && isfinite(hp->hi) && hp->lo < hp->hi, "svr_histogram: lo and hi must be finite, lo < hi");
+    const float inv = (float)hp->bins / (hp->hi - hp->lo);
+    SVR_REQUIRE(isfinite(inv), "svr_histogram: bins / (hi - lo) is not finite in f32");
+    if (hp->use_box)
+        for (int a = 0; a < 3; ++a) SVR_REQUIRE(hp->box_shape[a] >= 0, "svr_histogram: negative box_shape");
+    SVR_REQUIRE(hp->selected_count == 0 || hp->selected, "svr_histogram: selected_count > 0 with a NULL selected pointer");
+    // the intersection of box and window, in 64 bits (box_off + box_shape may pass 2^31); a window of None has shape 0 and holds nothing
+    const svr_lod_state& st = c->lod[hp->lod].state;
+    int64_t lo[3], n[3];
+    for (int a = 0; a < 3; ++a) {
+        int64_t b = st.offset[a], e = (int64_t)st.offset[a] + st.shape[a];
+        if (hp->use_box) {
+            b = std::max<int64_t>(b, hp->box_off[a]);
+            e = std::min<int64_t>(e, (int64_t)hp->box_off[a] + hp->box_shape[a]);
+        }
+        lo[a] = b; n[a] = e - b;
+    }
+    const int lod = hp->lod, K = hp->bins;
+    const float flo = hp->lo, fhi = hp->hi;
+    const uint32_t* sel = hp->selected; const uint32_t nsel = hp->selected_count;
+    return SVR_DRAW_ORDERED(c, stream, svr_launch_histogram(c, lod, lo, n, flo, fhi, inv, K, sel, nsel, *out, s));
 }
 
 int svr_set_transfer_function(svr_ctx* c, const float* rgba, int32_t K) {
