@@ -709,6 +709,70 @@ typedef struct svr_histogram_outputs {  /* DEVICE pointers; counts required, the
 } svr_histogram_outputs;
 int  svr_histogram(svr_ctx* ctx, const svr_histogram_params* params, const svr_histogram_outputs* out, void* stream);
 
+/* ---- per-object measurements of the resident rings: which objects are resident, how big is each, where is it, what
+ * is its mean intensity?  (No counterpart in the reference; the rows of a segment table, the box that crops a view to a
+ * picked object, the point to fly to.)  An addition within ABI version 9: one new symbol and three new structs, nothing
+ * older changes.  One streaming pass over the label and density rings in HBM fills a table of records, one per label;
+ * nothing is copied to the host.
+ * Defined HERE (numpy restatement: tests/objects_twin.py):
+ *   considered  exactly svr_histogram's voxels: the logical voxels (x, y, z) of LOD `lod` in the intersection of box and
+ *               window, read from ring slot (x % ring_x, y % ring_y, z % ring_z) of the row-major ring (the micro-block
+ *               copy is never read); without label rings every label reads as 0.  Then, with selected_count > 0, only
+ *               the voxels whose label is one of selected[0 .. selected_count).  Then, with ignore_zero != 0, the
+ *               voxels of label 0 are dropped: they are counted in header[3] and nowhere else.  A window of None and a
+ *               box that misses the window consider nothing.
+ *   records     `capacity` records of 96 bytes.  One record per distinct considered label that found a slot, in no
+ *               particular order; every byte of an unused record is 0.  Labels 0 and 0xFFFFFFFF are ordinary labels.
+ *   header      8 x uint64_t:
+ *                 [0] occupied records
+ *                 [1] considered voxels
+ *                 [2] overflow: the considered voxels whose label found no slot
+ *                 [3] label-0 voxels dropped by ignore_zero (they passed box and `selected`; not part of [1])
+ *                 [4..6] the window offset (x, y, z) of the LOD the call used, as int64 bit patterns; sum[] is relative to it
+ *                 [7] 0
+ *   slots       an insertion can reach every record (linear probing over the whole table), so header[2] != 0 if and
+ *               only if more than `capacity` distinct labels are considered.  Then exactly `capacity` records are
+ *               occupied, every one of them is complete and exact for its label (a label that owns a record never
+ *               loses voxels), and sum(voxels) + header[2] == header[1].  Which labels got records is unspecified.
+ *   value       the raw ring element.  u8 / u16 rings: value_sum is the u64 sum, finite == voxels, vmin / vmax the
+ *               extremes as f32 (exact).  float32 rings: only finite values count in finite, value_sum, vmin and vmax;
+ *               value_sum holds the BITS of an f64 sum whose every partial sum is held in f64.
+ * The call OVERWRITES its outputs: it zeroes them on `stream`, then fills them.  On integer rings every field is an
+ * integer sum, a minimum or a maximum: the result does not depend on the order in which the device visits the voxels.
+ * On float32 rings value_sum is the one order-dependent field (f64 additions in any order).  A render-thread call
+ * ordered like svr_histogram: it waits for published uploads, and later uploads are ordered behind it.  Enqueued on
+ * `stream`; asynchronous.  The material, the variant, the interpolation and the cut planes are not read.
+ * SVR_ERR_INVALID, with nothing enqueued and the outputs untouched, for: a NULL ctx, params, outputs, records or
+ * header; lod out of range; capacity 0 or above SVR_OBJECTS_MAX_CAPACITY; a negative box_shape component (with
+ * use_box != 0); selected == NULL with selected_count > 0. */
+#define SVR_OBJECTS_MAX_CAPACITY (1u << 26)
+typedef struct svr_objects_params {
+    int32_t lod;
+    int32_t use_box;                    /* 0: the LOD's whole resident window */
+    int32_t box_off[3], box_shape[3];   /* LOD-l logical voxels, shader order: svr_histogram_params' */
+    const uint32_t* selected;           /* DEVICE, sorted ascending; NULL when the count is 0 */
+    uint32_t selected_count;            /* 0: every label */
+    int32_t  ignore_zero;               /* != 0: voxels of label 0 take no part; they are counted in header[3] */
+    uint32_t capacity;                  /* records in svr_objects_outputs::records, 1 .. SVR_OBJECTS_MAX_CAPACITY (any integer) */
+} svr_objects_params;
+typedef struct svr_object_record {
+    uint32_t label;
+    uint32_t used;        /* 1: occupied; 0: empty, every byte of the record is 0 */
+    uint64_t voxels;      /* considered voxels with this label */
+    uint64_t sum[3];      /* sum over them of (x - off_x), (y - off_y), (z - off_z); off = header[4..6] */
+    int32_t  lo[3], hi[3];/* smallest and largest logical voxel coordinate, both inclusive, shader order, LOD voxels */
+    uint64_t finite;      /* those whose value is finite (u8 / u16 rings: == voxels) */
+    uint64_t value_sum;   /* u8 / u16 rings: the u64 sum of the raw values.  float32 rings: the BITS of an f64 sum
+                             of the finite values, every partial sum held in f64 */
+    float    vmin, vmax;  /* over the finite values; (+inf, -inf) when finite == 0 */
+    uint64_t reserved;    /* 0 */
+} svr_object_record;
+typedef struct svr_objects_outputs {    /* DEVICE pointers, both required */
+    svr_object_record* records;         /* capacity */
+    uint64_t* header;                   /* 8 */
+} svr_objects_outputs;
+int  svr_objects(svr_ctx* ctx, const svr_objects_params* params, const svr_objects_outputs* out, void* stream);
+
 /* ---- sync */
 int  svr_sync(svr_ctx* ctx);                 /* both streams idle */
 int  svr_sync_uploads(svr_ctx* ctx);         /* upload stream idle */

@@ -13,7 +13,7 @@ from .outline import outline
 from ._material import SubVolumeMaterial
 from ._transfer import TransferFunction
 from ._transform import AffineTransform, OrthographicCamera, PerspectiveCamera
-from ._wobject import FrameRegion, HistogramResult, IsoResult, RenderResult, SliceResult, SubVolume
+from ._wobject import FrameRegion, HistogramResult, IsoResult, ObjectTable, RenderResult, SliceResult, SubVolume
 from ._wrapping_buffer import WrappingBuffer, subtract_rois
 
 __all__ = [
@@ -32,6 +32,7 @@ __all__ = [
     "SliceResult",
     "IsoResult",
     "HistogramResult",
+    "ObjectTable",
     "subtract_rois",
     # display-side output of a render (pygfx's job in the reference)
     "compose",

@@ -192,6 +192,43 @@ class HistogramOutputs(C.Structure):
 
 HIST_MAX_BINS = 4096                                # SVR_HIST_MAX_BINS
 
+
+class ObjectsParams(C.Structure):
+    _fields_ = [
+        ("lod", C.c_int32),
+        ("use_box", C.c_int32),
+        ("box_off", C.c_int32 * 3),
+        ("box_shape", C.c_int32 * 3),
+        ("selected", C.c_void_p),
+        ("selected_count", C.c_uint32),
+        ("ignore_zero", C.c_int32),
+        ("capacity", C.c_uint32),
+    ]
+
+
+class ObjectRecord(C.Structure):
+    _fields_ = [
+        ("label", C.c_uint32),
+        ("used", C.c_uint32),
+        ("voxels", C.c_uint64),
+        ("sum", C.c_uint64 * 3),
+        ("lo", C.c_int32 * 3),
+        ("hi", C.c_int32 * 3),
+        ("finite", C.c_uint64),
+        ("value_sum", C.c_uint64),
+        ("vmin", C.c_float),
+        ("vmax", C.c_float),
+        ("reserved", C.c_uint64),
+    ]
+
+
+class ObjectsOutputs(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("records", "header")]
+
+
+OBJECTS_MAX_CAPACITY = 1 << 26                      # SVR_OBJECTS_MAX_CAPACITY
+OBJECT_RECORD_BYTES = 96                            # sizeof(svr_object_record)
+
 INTERPOLATIONS = {"nearest": 0, "linear": 1}      # SVR_INTERP_*
 CUT_MODES = {"ANY": 0, "ALL": 1}                  # SVR_CUT_*
 MAX_CUT_PLANES = 8                                # SVR_MAX_CUT_PLANES
@@ -252,6 +289,7 @@ SIGNATURES = {
     "svr_set_interpolation": (C.c_int, [C.c_void_p, C.c_int]),
     "svr_set_cut_planes": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int]),
     "svr_histogram": (C.c_int, [C.c_void_p, C.POINTER(HistogramParams), C.POINTER(HistogramOutputs), C.c_void_p]),
+    "svr_objects": (C.c_int, [C.c_void_p, C.POINTER(ObjectsParams), C.POINTER(ObjectsOutputs), C.c_void_p]),
     "svr_sync": (C.c_int, [C.c_void_p]),
     "svr_sync_uploads": (C.c_int, [C.c_void_p]),
     "svr_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),

@@ -202,6 +202,92 @@ def lod_box(begin, end, scale_factor):
     return tuple(int(v) for v in b), tuple(int(v) for v in e)
 
 
+_OBJECTS_FIRST_CAPACITY = 4096      # records of the first pass of ``SubVolume.objects(capacity=None)``; 8 times more per rerun
+
+
+def objects_capacity(capacity, id_count=None):
+    """``(records of the first pass, automatic)`` of ``SubVolume.objects``: an explicit integer capacity in
+    1 .. SVR_OBJECTS_MAX_CAPACITY runs once; None starts at ``_OBJECTS_FIRST_CAPACITY``, or at the number of ids when
+    ``labels`` are given, which can never overflow."""
+    if capacity is None:
+        return (_OBJECTS_FIRST_CAPACITY if id_count is None else int(id_count)), True
+    if isinstance(capacity, (bool, np.bool_)) or not isinstance(capacity, (int, np.integer)) or not 1 <= capacity <= N.OBJECTS_MAX_CAPACITY:
+        raise ValueError(f"capacity must be None or an integer in 1 .. {N.OBJECTS_MAX_CAPACITY}")
+    return int(capacity), False
+
+
+def finest_box(begin, end, scale_factor):
+    """The inverse of :func:`lod_box`: the voxel box ``[begin, end)`` of a LOD with ``scale_factor`` (numpy order) in
+    voxels of the finest scale, ``(floor(begin / scale), ceil(end / scale))`` per axis, as ints."""
+    scale = np.asarray(scale_factor, np.float64).reshape(-1)
+    b = np.floor(np.asarray(begin, np.float64).reshape(-1) / scale)
+    e = np.ceil(np.asarray(end, np.float64).reshape(-1) / scale)
+    return tuple(int(v) for v in b), tuple(int(v) for v in e)
+
+
+def lod_center_to_data(center, scale_factor):
+    """A point in a LOD's voxel coordinates (integer c: the centre of voxel c; any order, ``scale_factor`` in the same
+    one) as a data coordinate of the finest scale.  LOD voxel c covers the finest index interval [c / scale,
+    (c + 1) / scale) and finest voxel i is centred on data coordinate i (it covers [i - 0.5, i + 0.5), the convention of
+    :meth:`SubVolume.crop_planes`), so the centre maps to ``(c + 0.5) / scale - 0.5``."""
+    c = np.asarray(center, np.float64)
+    return (c + 0.5) / np.asarray(scale_factor, np.float64) - 0.5
+
+
+@dataclass
+class ObjectTable:
+    """The occupied records of one ``svr_objects`` call (include/svr.h), compacted and sorted by id on the device.
+    Coordinates are LOD voxels in numpy order (z, y, x)."""
+
+    ids: "object"             # torch i64 [n]        the labels, ascending
+    voxels: "object"          # torch i64 [n]
+    begin: "object"           # torch i64 [n, 3]     smallest voxel coordinate
+    end: "object"             # torch i64 [n, 3]     largest voxel coordinate + 1
+    centroid: "object"        # torch f64 [n, 3]     window offset + sum / voxels
+    finite: "object"          # torch i64 [n]        voxels whose value is finite
+    mean: "object"            # torch f64 [n]        of the finite values; NaN where there are none
+    min: "object"             # torch f32 [n]        +inf where finite == 0
+    max: "object"             # torch f32 [n]        -inf where finite == 0
+    considered: int           # voxels that took part
+    background: int           # label-0 voxels left out by background=False
+    lod: int
+    scale_factor: tuple = (1.0, 1.0, 1.0)       # of the LOD, numpy order
+    volume: "object | None" = None              # the SubVolume, for its world transform
+    _host: "dict | None" = None
+
+    def __len__(self):
+        return int(self.ids.numel())
+
+    def _rows(self):
+        if self._host is None:
+            self._host = {k: getattr(self, k).cpu().numpy() for k in ("ids", "begin", "end", "centroid")}
+        return self._host
+
+    def index(self, label) -> int:
+        """The row of ``label``; ``KeyError`` when the table does not hold it."""
+        ids = self._rows()["ids"]
+        i = int(np.searchsorted(ids, int(label)))
+        if i >= len(ids) or int(ids[i]) != int(label):
+            raise KeyError(label)
+        return i
+
+    def box(self, label):
+        """``(begin, end)`` of the object's bounding box in voxels of the finest scale (numpy order, ints), ready for
+        :meth:`SubVolume.crop_planes` and ``histogram(box=)``: :func:`finest_box` of its LOD box."""
+        i = self.index(label)
+        rows = self._rows()
+        return finest_box(rows["begin"][i], rows["end"][i], self.scale_factor)
+
+    def position(self, label):
+        """The world-space position (x, y, z) of the object's centroid, for :meth:`SubVolume.center_on_position`: the
+        centroid in LOD voxels mapped to the finest data coordinate by :func:`lod_center_to_data`
+        (``(c + 0.5) / scale - 0.5``), then through the volume's world transform."""
+        i = self.index(label)
+        data = lod_center_to_data(self._rows()["centroid"][i], self.scale_factor)[::-1]       # shader order
+        world = np.asarray(self.volume.world.matrix, np.float64) @ np.array([*data, 1.0])
+        return tuple(float(v) for v in world[:3])
+
+
 _SLICE_CACHE_SIZES = 4      # output sets kept per volume: e.g. the three axis views of a viewer, each of its own size
 
 
@@ -1031,6 +1117,90 @@ class SubVolume(_HasWorld):
             bins = 256 if self._rings.density_storage == "uint8" else N.HIST_MAX_BINS
         res = self.histogram(lod=lod, bins=bins, range=range, box=box, labels=labels)
         return clim_from_counts(res.counts.cpu().numpy(), res.edges, (p_lo, p_hi))
+
+    # -- which objects are resident? ----------------------------------------------
+    def objects(self, lod: int = 0, box=None, labels=None, background: bool = False, capacity=None, stream=None) -> ObjectTable:
+        """Per-object measurements of what LOD ``lod`` holds in HBM (definition: ``svr_objects`` in include/svr.h): one
+        pass over the label and density rings on the device -> one row per resident label with its voxel count,
+        bounding box, centroid, and the mean, minimum and maximum of its values.  ``box`` and ``labels`` mean what they
+        mean in :meth:`histogram`.  ``background=False`` leaves the voxels of label 0 out (they are counted in
+        ``ObjectTable.background``).  ``capacity``: the records of the device table; None starts at
+        ``_OBJECTS_FIRST_CAPACITY`` (or at the number of ``labels``) and reruns the pass with 8 times more while labels
+        found no record, up to ``SVR_OBJECTS_MAX_CAPACITY`` (then ``ValueError``); an explicit integer runs once and
+        raises ``ValueError`` when the table was too small.  The call SYNCHRONISES: the header of every pass is read
+        from the device (on ``stream`` when one is given) before the table is compacted and sorted with torch ops."""
+        import torch
+
+        if isinstance(lod, bool) or not isinstance(lod, (int, np.integer)) or not 0 <= lod < len(self.wrapping_buffers):
+            raise ValueError(f"lod must be an integer in 0 .. {len(self.wrapping_buffers) - 1}")
+        lod = int(lod)
+        ids = label_ids(labels) if labels is not None else None
+        cap, automatic = objects_capacity(capacity, None if ids is None else len(ids))
+        op = N.ObjectsParams()
+        op.lod = lod
+        op.ignore_zero = 0 if background else 1
+        scale = tuple(float(v) for v in self.wrapping_buffers[lod].scale_factor)
+        if box is not None:
+            try:
+                begin, end = box
+            except (TypeError, ValueError):
+                raise ValueError("box must be (begin, end)") from None
+            b, e = lod_box(begin, end, scale)
+            op.use_box = 1
+            op.box_off[:] = b[::-1]                                   # shader order
+            op.box_shape[:] = [ev - bv for bv, ev in zip(b[::-1], e[::-1])]
+        handle = self.prepare()
+        dev = torch.device("cuda", self._rings.device)
+        side = torch.cuda.ExternalStream(int(stream), device=dev) if stream is not None else None
+        sel = None
+        if ids is not None:
+            sel = torch.from_numpy(ids.view(np.int32)).to(dev)
+            if side is not None:                                      # copied on torch's stream, read on the caller's
+                torch.cuda.current_stream(dev).synchronize()
+                sel.record_stream(side)
+            op.selected, op.selected_count = sel.data_ptr(), int(sel.numel())
+        stream = self._plane_stream(stream)
+        while True:
+            records = torch.empty((cap, N.OBJECT_RECORD_BYTES // 8), dtype=torch.int64, device=dev)
+            header = torch.empty(8, dtype=torch.int64, device=dev)
+            if side is not None:
+                torch.cuda.current_stream(dev).synchronize()          # the allocator's memory may still be in use there
+            op.capacity = cap
+            oo = N.ObjectsOutputs(records.data_ptr(), header.data_ptr())
+            N.check(N.lib().svr_objects(handle, C.byref(op), C.byref(oo), C.c_void_p(stream)), "svr_objects")
+            if side is not None:
+                for t in (records, header):
+                    t.record_stream(side)
+                side.synchronize()
+            head = [int(v) for v in header.cpu().numpy()]             # synchronises
+            if head[2] == 0:
+                break
+            if not automatic:
+                raise ValueError(f"objects: capacity {cap} is too small: {head[2]} of {head[1]} voxels belong to labels "
+                                 f"that found no record (pass a larger capacity, or None)")
+            if cap >= N.OBJECTS_MAX_CAPACITY:
+                raise ValueError(f"objects: more than {N.OBJECTS_MAX_CAPACITY} distinct labels are resident")
+            cap = min(cap * 8, N.OBJECTS_MAX_CAPACITY)
+        # compact and sort on the device; record fields by their 4- and 8-byte columns (svr_object_record)
+        w32 = records.view(torch.int32)
+        rows = torch.nonzero(w32[:, 1] == 1).reshape(-1)
+        label = w32[rows, 0].to(torch.int64) & 0xFFFFFFFF
+        label, order = torch.sort(label)
+        rows = rows[order]
+        r64, r32 = records[rows], w32[rows]
+        voxels, finite = r64[:, 1], r64[:, 8]
+        offset = torch.tensor([head[4], head[5], head[6]], dtype=torch.int64, device=dev)      # read as int64: signed already
+        centroid = (offset.to(torch.float64) + r64[:, 2:5].to(torch.float64) / voxels.to(torch.float64).unsqueeze(1)).flip(1)
+        if self._rings.density_storage == "float32":
+            total = r64[:, 9].contiguous().view(torch.float64)
+        else:
+            total = r64[:, 9].to(torch.float64)
+        mean = torch.where(finite > 0, total / finite.to(torch.float64), torch.full_like(total, float("nan")))
+        vmm = r32[:, 20:22].contiguous().view(torch.float32)
+        return ObjectTable(ids=label, voxels=voxels.contiguous(), begin=r32[:, 10:13].flip(1).to(torch.int64),
+                           end=r32[:, 13:16].flip(1).to(torch.int64) + 1, centroid=centroid, finite=finite.contiguous(), mean=mean,
+                           min=vmm[:, 0].contiguous(), max=vmm[:, 1].contiguous(), considered=head[1], background=head[3], lod=lod,
+                           scale_factor=scale, volume=self)
 
     def synchronize(self):
         N.check(N.lib().svr_sync(self._rings.handle), "svr_sync")

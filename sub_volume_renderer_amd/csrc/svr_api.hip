@@ -63,6 +63,9 @@ hipError_t svr_launch_iso(const svr_ctx* c, const svr_camera& cam, const svr_fra
 hipError_t svr_launch_histogram(const svr_ctx* c, int lod, const int64_t lo[3], const int64_t n[3], float flo, float fhi,
                                 float inv, int K, const uint32_t* sel, uint32_t nsel, const svr_histogram_outputs& out,
                                 hipStream_t stream);
+// object_kernels.hip (same reason).  lo, n as above; everything checked by svr_objects.
+hipError_t svr_launch_objects(const svr_ctx* c, int lod, const int64_t lo[3], const int64_t n[3], const uint32_t* sel, uint32_t nsel,
+                              int ignore_zero, uint32_t capacity, const svr_objects_outputs& out, hipStream_t stream);
 
 namespace {
 
@@ -1319,6 +1322,29 @@ int svr_histogram(svr_ctx* c, const svr_histogram_params* hp, const svr_histogra
     const float flo = hp->lo, fhi = hp->hi;
     const uint32_t* sel = hp->selected; const uint32_t nsel = hp->selected_count;
     return SVR_DRAW_ORDERED(c, stream, svr_launch_histogram(c, lod, lo, n, flo, fhi, inv, K, sel, nsel, *out, s));
+}
+
+int svr_objects(svr_ctx* c, const svr_objects_params* op, const svr_objects_outputs* out, void* stream) {
+    SVR_REQUIRE(c && op && out && out->records && out->header, "svr_objects: null argument");
+    SVR_REQUIRE(op->lod >= 0 && op->lod < c->num_lods, "svr_objects: lod out of range");
+    SVR_REQUIRE(op->capacity >= 1 && op->capacity <= SVR_OBJECTS_MAX_CAPACITY, "svr_objects: capacity must be in 1 .. 2^26");
+    if (op->use_box)
+        for (int a = 0; a < 3; ++a) SVR_REQUIRE(op->box_shape[a] >= 0, "svr_objects: negative box_shape");
+    SVR_REQUIRE(op->selected_count == 0 || op->selected, "svr_objects: selected_count > 0 with a NULL selected pointer");
+    // the intersection of box and window, as svr_histogram takes it
+    const svr_lod_state& st = c->lod[op->lod].state;
+    int64_t lo[3], n[3];
+    for (int a = 0; a < 3; ++a) {
+        int64_t b = st.offset[a], e = (int64_t)st.offset[a] + st.shape[a];
+        if (op->use_box) {
+            b = std::max<int64_t>(b, op->box_off[a]);
+            e = std::min<int64_t>(e, (int64_t)op->box_off[a] + op->box_shape[a]);
+        }
+        lo[a] = b; n[a] = e - b;
+    }
+    const int lod = op->lod, ignore_zero = op->ignore_zero;
+    const uint32_t* sel = op->selected; const uint32_t nsel = op->selected_count, capacity = op->capacity;
+    return SVR_DRAW_ORDERED(c, stream, svr_launch_objects(c, lod, lo, n, sel, nsel, ignore_zero, capacity, *out, s));
 }
 
 int svr_set_transfer_function(svr_ctx* c, const float* rgba, int32_t K) {
