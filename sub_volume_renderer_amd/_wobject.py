@@ -1011,6 +1011,42 @@ class SubVolume(_HasWorld):
 
         return torch.cuda.current_stream(self._rings.device).cuda_stream if stream is None else stream
 
+    # -- passes over one LOD's resident window: what histogram() and objects() share ------
+    def _check_lod(self, lod):
+        if isinstance(lod, bool) or not isinstance(lod, (int, np.integer)) or not 0 <= lod < len(self.wrapping_buffers):
+            raise ValueError(f"lod must be an integer in 0 .. {len(self.wrapping_buffers) - 1}")
+        return int(lod)
+
+    def _box_params(self, params, lod, box):
+        """``box=(begin, end)`` of the finest scale into ``use_box`` / ``box_off`` / ``box_shape`` of a params struct."""
+        if box is None:
+            return
+        try:
+            begin, end = box
+        except (TypeError, ValueError):
+            raise ValueError("box must be (begin, end)") from None
+        b, e = lod_box(begin, end, self.wrapping_buffers[lod].scale_factor)
+        params.use_box = 1
+        params.box_off[:] = b[::-1]                                   # shader order
+        params.box_shape[:] = [ev - bv for bv, ev in zip(b[::-1], e[::-1])]
+
+    @staticmethod
+    def _upload_ids(params, ids, dev, side):
+        """The sorted id list as a device tensor behind ``selected`` / ``selected_count`` of a params struct -> the
+        tensor (None without ids).  ``side``: the caller's stream as a torch stream, or None for torch's current one."""
+        import torch
+
+        if ids is None:
+            return None
+        sel = torch.from_numpy(ids.view(np.int32)).to(dev)
+        if side is not None:
+            # the id list was copied on torch's stream and is read on the caller's: the copy must have landed, and
+            # the caching allocator must not hand the memory out again before that stream has passed the kernel
+            torch.cuda.current_stream(dev).synchronize()
+            sel.record_stream(side)
+        params.selected, params.selected_count = sel.data_ptr(), int(sel.numel())
+        return sel
+
     # -- what values are resident? ------------------------------------------------
     def histogram(self, lod: int = 0, bins: int = 256, range=None, box=None, labels=None, stream=None) -> HistogramResult:
         """Intensity histogram of what LOD ``lod`` holds in HBM (definition: ``svr_histogram`` in include/svr.h): one
@@ -1025,11 +1061,10 @@ class SubVolume(_HasWorld):
         :meth:`render_slice` does."""
         import torch
 
-        if isinstance(lod, bool) or not isinstance(lod, (int, np.integer)) or not 0 <= lod < len(self.wrapping_buffers):
-            raise ValueError(f"lod must be an integer in 0 .. {len(self.wrapping_buffers) - 1}")
+        lod = self._check_lod(lod)
         if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= bins <= N.HIST_MAX_BINS:
             raise ValueError(f"bins must be an integer in 1 .. {N.HIST_MAX_BINS}")
-        lod, bins = int(lod), int(bins)
+        bins = int(bins)
         storage = self._rings.density_storage
         if range is not None:
             try:
@@ -1042,31 +1077,12 @@ class SubVolume(_HasWorld):
                 raise ValueError("range must be finite in float32 with lo < hi")
         hp = N.HistogramParams()
         hp.lod = lod
-        if box is not None:
-            try:
-                begin, end = box
-            except (TypeError, ValueError):
-                raise ValueError("box must be (begin, end)") from None
-            b, e = lod_box(begin, end, self.wrapping_buffers[lod].scale_factor)
-            hp.use_box = 1
-            hp.box_off[:] = b[::-1]                                   # shader order
-            hp.box_shape[:] = [ev - bv for bv, ev in zip(b[::-1], e[::-1])]
-        ids = None
-        if labels is not None:
-            ids = label_ids(labels)
+        self._box_params(hp, lod, box)
+        ids = label_ids(labels) if labels is not None else None
         handle = self.prepare()
         dev = torch.device("cuda", self._rings.device)
-        sel = None
-        if ids is not None:
-            sel = torch.from_numpy(ids.view(np.int32)).to(dev)
-            if stream is not None:
-                # the id list was copied on torch's stream and is read on the caller's: the copy must have landed, and
-                # the caching allocator must not hand the memory out again before that stream has passed the kernel
-                torch.cuda.current_stream(dev).synchronize()
-                sel.record_stream(torch.cuda.ExternalStream(int(stream), device=dev))
-        hp.selected = sel.data_ptr() if sel is not None else None
-        hp.selected_count = int(sel.numel()) if sel is not None else 0
-        stream_given = stream is not None
+        side = torch.cuda.ExternalStream(int(stream), device=dev) if stream is not None else None
+        sel = self._upload_ids(hp, ids, dev, side)
         stream = self._plane_stream(stream)
 
         def run(lo, hi, k):
@@ -1076,9 +1092,9 @@ class SubVolume(_HasWorld):
             hp.lo, hp.hi, hp.bins = lo, hi, k
             ho = N.HistogramOutputs(counts.data_ptr(), tail.data_ptr(), rng.data_ptr())
             N.check(N.lib().svr_histogram(handle, C.byref(hp), C.byref(ho), C.c_void_p(stream)), "svr_histogram")
-            if stream_given:                                          # outputs dropped early must outlive the kernel too
+            if side is not None:                                      # outputs dropped early must outlive the kernel too
                 for t in (counts, tail, rng):
-                    t.record_stream(torch.cuda.ExternalStream(int(stream), device=dev))
+                    t.record_stream(side)
             return HistogramResult(counts, tail, rng, histogram_edges(lo, hi, k), lod, selected=sel)
 
         if range is None:
@@ -1131,34 +1147,18 @@ class SubVolume(_HasWorld):
         from the device (on ``stream`` when one is given) before the table is compacted and sorted with torch ops."""
         import torch
 
-        if isinstance(lod, bool) or not isinstance(lod, (int, np.integer)) or not 0 <= lod < len(self.wrapping_buffers):
-            raise ValueError(f"lod must be an integer in 0 .. {len(self.wrapping_buffers) - 1}")
-        lod = int(lod)
+        lod = self._check_lod(lod)
         ids = label_ids(labels) if labels is not None else None
         cap, automatic = objects_capacity(capacity, None if ids is None else len(ids))
         op = N.ObjectsParams()
         op.lod = lod
         op.ignore_zero = 0 if background else 1
         scale = tuple(float(v) for v in self.wrapping_buffers[lod].scale_factor)
-        if box is not None:
-            try:
-                begin, end = box
-            except (TypeError, ValueError):
-                raise ValueError("box must be (begin, end)") from None
-            b, e = lod_box(begin, end, scale)
-            op.use_box = 1
-            op.box_off[:] = b[::-1]                                   # shader order
-            op.box_shape[:] = [ev - bv for bv, ev in zip(b[::-1], e[::-1])]
+        self._box_params(op, lod, box)
         handle = self.prepare()
         dev = torch.device("cuda", self._rings.device)
         side = torch.cuda.ExternalStream(int(stream), device=dev) if stream is not None else None
-        sel = None
-        if ids is not None:
-            sel = torch.from_numpy(ids.view(np.int32)).to(dev)
-            if side is not None:                                      # copied on torch's stream, read on the caller's
-                torch.cuda.current_stream(dev).synchronize()
-                sel.record_stream(side)
-            op.selected, op.selected_count = sel.data_ptr(), int(sel.numel())
+        sel = self._upload_ids(op, ids, dev, side)                    # held until the passes below have run
         stream = self._plane_stream(stream)
         while True:
             records = torch.empty((cap, N.OBJECT_RECORD_BYTES // 8), dtype=torch.int64, device=dev)

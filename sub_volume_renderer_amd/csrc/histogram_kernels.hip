@@ -1,14 +1,14 @@
 // Intensity histograms of the resident rings (svr_histogram, include/svr.h): one streaming pass over a box of one
 // LOD's window.  gfx950.
 //
-// Decomposition.  The host cuts the intersection of box and window at the ring's wrap seams into at most 2 x 2 x 2 pieces; each piece is a
-// dense sub-block of the row-major ring (the micro-block copy is never read), so the kernel sees straight rows.  A
-// workgroup of 256 threads takes a run of whole rows of one piece, sized so that it sees fewer than 2^32 voxels (its
-// LDS counters are u32).  A row is read in 16-byte slots aligned in MEMORY: slot k of a row covers the 16 bytes at
-// (row start rounded down to 16) + 16 k.  A slot that lies wholly inside the row is one 16-byte load; the slots that
-// hold the row's head and tail read only their own elements, one by one.  2^k lanes share a row (the smallest power
-// of two that covers its slots; for rows of more than 8 slots the one from 8 to 256 that wastes the fewest lanes), so
-// short rows still fill the wave.
+// Decomposition (ring_pieces.h, shared with object_kernels.hip).  The host cuts the intersection of box and window at
+// the ring's wrap seams into at most 2 x 2 x 2 pieces; each piece is a dense sub-block of the row-major ring (the
+// micro-block copy is never read), so the kernel sees straight rows.  A workgroup of 256 threads takes a run of whole
+// rows of one piece, sized so that it sees fewer than 2^32 voxels (its LDS counters are u32).  A row is read in
+// 16-byte slots aligned in MEMORY: slot k of a row covers the 16 bytes at (row start rounded down to 16) + 16 k.  A
+// slot that lies wholly inside the row is one 16-byte load; the slots that hold the row's head and tail read only
+// their own elements, one by one.  2^k lanes share a row (the smallest power of two that covers its slots; for rows of
+// more than 8 slots the one from 8 to 256 that wastes the fewest lanes), so short rows still fill the wave.
 //
 // Counting.  Per-workgroup LDS sub-histogram of K + 3 u32 words (the three tails are bins K .. K + 2), flushed with
 // one 64-bit global atomic per non-zero word.  Contention: a ring that is mostly one value sends nearly every lane
@@ -21,25 +21,15 @@
 // A constant ring thus costs one LDS atomic per wave and 1 KiB read.  Counts are integers: the result does not
 // depend on arrival order.  No float atomics anywhere: min / max travel as u32 keys that order like the floats.
 #include "svr_internal.h"
+#include "ring_pieces.h"
 
 namespace {
 
 constexpr int kHistThreads = 256;
-constexpr int kHistMaxPieces = 8;
 // Every workgroup holds the counters of the largest K (16.4 KB of static LDS, whatever K the call has): that, not
 // registers, bounds a CU at nine workgroups of the 160 KB; the grid is sized for eight.
-constexpr size_t kHistWgPerCu = 8;
-constexpr size_t kHistMinShare = 16384;    // bytes of voxels
-
-struct HistPiece {
-    uint32_t s[3];             // first ring slot (x, y, z)
-    uint32_t n[3];             // extent; s + n <= ring on every axis
-    uint32_t rows;             // n[1] * n[2]
-    uint32_t rows_per_wg;
-    uint32_t block0;           // first workgroup of this piece
-    uint32_t lpr_log2;         // log2 of the lanes that share a row
-    uint32_t spr;              // 16-byte slots a row can touch
-};
+constexpr uint64_t kHistWgPerCu = 8;
+constexpr uint64_t kHistMinShare = 16384;    // bytes of voxels
 
 struct HistArgs {
     const void* density;
@@ -52,29 +42,8 @@ struct HistArgs {
     unsigned long long* counts;
     unsigned long long* tail;  // may be null
     uint32_t* range_keys;      // the caller's range[2], holding (min key, max key) until hist_finish_kernel; may be null
-    int32_t npieces;
-    HistPiece piece[kHistMaxPieces];
+    RingPieces pieces;
 };
-
-// u32 keys that order like the floats they come from (NaN never gets here)
-__device__ __forceinline__ uint32_t key_of_float(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float float_of_key(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
-// lower-bound search; every probe lies in [0, n) whatever the order of `s` (outline_kernel's)
-__device__ __forceinline__ bool hist_in_set(const uint32_t* __restrict__ s, uint32_t n, uint32_t v) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (s[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < n && s[lo] == v;
-}
 
 template <typename T> struct HistElem;
 template <> struct HistElem<uint8_t> {
@@ -152,20 +121,13 @@ __global__ __launch_bounds__(kHistThreads) void hist_kernel(const HistArgs a) {
     if (tid == 0) { wg_min = 0xFFFFFFFFu; wg_max = 0u; }
     __syncthreads();
 
-    // the piece this workgroup belongs to (wave-uniform)
-    int pi = 0;
-    while (pi + 1 < a.npieces && blockIdx.x >= a.piece[pi + 1].block0) ++pi;
-    const HistPiece& P = a.piece[pi];
-    const uint32_t r0 = (blockIdx.x - P.block0) * P.rows_per_wg;
-    const uint32_t r1 = (uint32_t)min((uint64_t)P.rows, (uint64_t)r0 + P.rows_per_wg);
-    const uint32_t lpr = 1u << P.lpr_log2, rows_per_iter = kHistThreads >> P.lpr_log2;
-    const uint32_t lane_row = tid >> P.lpr_log2, lane_slot = tid & (lpr - 1u);
+    RING_WALK(kHistThreads, a.pieces, blockIdx.x, tid);
     const uint32_t nx = P.n[0];
     const T* const ring = static_cast<const T*>(a.density);
 
     // without label rings every label is 0: the filter passes everything or nothing
     bool filter = FILT, nothing = false;
-    if (FILT && !a.labels) { filter = false; nothing = !hist_in_set(a.sel, a.nsel, 0u); }
+    if (FILT && !a.labels) { filter = false; nothing = !ring_in_set(a.sel, a.nsel, 0u); }
 
     uint32_t kmin = 0xFFFFFFFFu, kmax = 0u;             // keys of the lane's min / max (integer rings: the raw values)
     bool any = false;
@@ -176,7 +138,7 @@ __global__ __launch_bounds__(kHistThreads) void hist_kernel(const HistArgs a) {
         const bool row_ok = rb + lane_row < r1;
         const uint32_t row = (uint32_t)(rb + lane_row);
         const uint32_t ry = row_ok ? row % P.n[1] : 0u, rz = row_ok ? row / P.n[1] : 0u;
-        const size_t e0 = ((size_t)(P.s[2] + rz) * (size_t)a.ring[1] + (size_t)(P.s[1] + ry)) * (size_t)a.ring[0] + (size_t)P.s[0];
+        const size_t e0 = RING_ROW_OFFSET(P, a.ring, ry, rz);
         const T* const rowp = ring + e0;
         const uint32_t head = (uint32_t)((reinterpret_cast<uintptr_t>(rowp) & 15u) / sizeof(T));   // elements before the row in its first slot
         for (uint32_t sb = 0; sb < P.spr; sb += lpr) {
@@ -209,7 +171,7 @@ __global__ __launch_bounds__(kHistThreads) void hist_kernel(const HistArgs a) {
                     if (vm & (1u << j)) {
                         const uint32_t lab = lrow[first + j];
                         if (!have_last || lab != last_label) {
-                            last_pass = hist_in_set(a.sel, a.nsel, lab); last_label = lab; have_last = true;
+                            last_pass = ring_in_set(a.sel, a.nsel, lab); last_label = lab; have_last = true;
                         }
                         if (!last_pass) vm &= ~(1u << j);
                     }
@@ -219,7 +181,7 @@ __global__ __launch_bounds__(kHistThreads) void hist_kernel(const HistArgs a) {
             const bool solid = full && vm == kAll && E::one_value(q);
             const uint32_t b0 = hist_bin(E::value(rawv[0]), a.lo, a.hi, a.inv, K);
             if (solid && b0 != (uint32_t)K + 2u) {
-                const uint32_t key = sizeof(T) == 4 ? key_of_float(E::value(rawv[0])) : rawv[0];
+                const uint32_t key = sizeof(T) == 4 ? ring_key_of_float(E::value(rawv[0])) : rawv[0];
                 kmin = min(kmin, key); kmax = max(kmax, key); any = true;
             }
             hist_wave_add(bins, b0, solid, (uint32_t)V);
@@ -241,7 +203,7 @@ __global__ __launch_bounds__(kHistThreads) void hist_kernel(const HistArgs a) {
                     const float v = E::value(rawv[j]);
                     const uint32_t b = hist_bin(v, a.lo, a.hi, a.inv, K);
                     if (ok && b != (uint32_t)K + 2u) {
-                        const uint32_t key = sizeof(T) == 4 ? key_of_float(v) : rawv[j];
+                        const uint32_t key = sizeof(T) == 4 ? ring_key_of_float(v) : rawv[j];
                         kmin = min(kmin, key); kmax = max(kmax, key); any = true;
                     }
                     if (merge) hist_wave_add(bins, b, ok, 1u);
@@ -254,7 +216,7 @@ __global__ __launch_bounds__(kHistThreads) void hist_kernel(const HistArgs a) {
     // min / max: per wave, then per workgroup through LDS, then one pair of global u32 atomics
     if (a.range_keys) {
         if (sizeof(T) != 4 && any) {                                   // integer rings tracked raw values: exact in f32
-            kmin = key_of_float((float)kmin); kmax = key_of_float((float)kmax);
+            kmin = ring_key_of_float((float)kmin); kmax = ring_key_of_float((float)kmax);
         }
         if (!any) { kmin = 0xFFFFFFFFu; kmax = 0u; }
 #pragma unroll
@@ -301,7 +263,7 @@ __global__ __launch_bounds__(256) void hist_finish_kernel(const unsigned long lo
         const uint32_t kmin = range_keys[0], kmax = range_keys[1];
         float* const r = reinterpret_cast<float*>(range_keys);
         if (kmin > kmax) { r[0] = __builtin_inff(); r[1] = -__builtin_inff(); }     // nothing considered, or only NaN
-        else { r[0] = float_of_key(kmin); r[1] = float_of_key(kmax); }
+        else { r[0] = ring_float_of_key(kmin); r[1] = ring_float_of_key(kmax); }
     }
 }
 
@@ -332,65 +294,15 @@ hipError_t svr_launch_histogram(const svr_ctx* c, int lod, const int64_t lo[3], 
         a.lo = flo; a.hi = fhi; a.inv = inv; a.K = K;
         a.sel = sel; a.nsel = nsel;
         a.counts = counts; a.tail = tail; a.range_keys = keys;
-        const size_t es = svr_dtype_size(c->density_storage);
-        const uint32_t per_slot = (uint32_t)(16 / es);
-        // the pieces: per axis the run up to the ring's end, then the run that wrapped to its start
-        uint32_t s[3][2], m[3][2]; int cnt[3];
-        size_t total = 1;
-        for (int ax = 0; ax < 3; ++ax) {
-            const uint32_t R = (uint32_t)L.ring[ax];
-            a.ring[ax] = R;
-            const uint32_t s0 = (uint32_t)(lo[ax] % (int64_t)R), len = (uint32_t)n[ax];     // len <= the window <= R
-            const uint32_t first = len < R - s0 ? len : R - s0;
-            s[ax][0] = s0; m[ax][0] = first; cnt[ax] = 1;
-            if (first < len) { s[ax][1] = 0u; m[ax][1] = len - first; cnt[ax] = 2; }
-            total *= (size_t)len;
-        }
+        for (int ax = 0; ax < 3; ++ax) a.ring[ax] = (uint32_t)L.ring[ax];
         // a workgroup's share: kHistWgPerCu workgroups per CU of the device over the whole box, and at least
         // kHistMinShare bytes of voxels, which keeps the flush (one global atomic per non-zero bin) a small part of its work
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
-        size_t bytes_per_wg = total * es / ((size_t)cus * kHistWgPerCu);
-        if (bytes_per_wg < kHistMinShare) bytes_per_wg = kHistMinShare;
-        uint32_t blocks = 0;
-        a.npieces = 0;
-        for (int iz = 0; iz < cnt[2]; ++iz)
-            for (int iy = 0; iy < cnt[1]; ++iy)
-                for (int ix = 0; ix < cnt[0]; ++ix) {
-                    HistPiece& P = a.piece[a.npieces++];
-                    P.s[0] = s[0][ix]; P.s[1] = s[1][iy]; P.s[2] = s[2][iz];
-                    P.n[0] = m[0][ix]; P.n[1] = m[1][iy]; P.n[2] = m[2][iz];
-                    const uint64_t rows = (uint64_t)P.n[1] * P.n[2];
-                    if (rows > 0xFFFFFFFFull) return hipErrorInvalidValue;      // not with int32 ring extents below 2^16 x 2^16 rows
-                    P.rows = (uint32_t)rows;
-                    const size_t row_bytes = (size_t)P.n[0] * es;
-                    uint64_t rpw = (bytes_per_wg + row_bytes - 1) / row_bytes;
-                    const uint64_t cap = 0xFFFFFFFFull / P.n[0];                 // rows_per_wg * n[0] < 2^32: u32 LDS counters
-                    if (rpw > cap) rpw = cap;
-                    if (rpw > rows) rpw = rows;
-                    if (rpw < 1) rpw = 1;
-                    P.rows_per_wg = (uint32_t)rpw;
-                    // slots per row: one more than the row's own where a row may start inside a slot
-                    const bool aligned = (reinterpret_cast<uintptr_t>(L.density) + (size_t)P.s[0] * es) % 16 == 0 &&
-                                         ((size_t)a.ring[0] * es) % 16 == 0;
-                    P.spr = (P.n[0] + per_slot - 1u) / per_slot + (aligned ? 0u : 1u);
-                    // lanes per row: the power of two that covers the slots, or for longer rows the one (at least 8
-                    // lanes: whole 128-byte lines) whose multiple wastes the fewest lanes
-                    uint32_t lg = 0;
-                    while (lg < 3u && (1u << lg) < P.spr) ++lg;
-                    if (P.spr > 8u) {
-                        uint32_t best = 0xFFFFFFFFu;
-                        for (uint32_t g = 3u; g <= 8u; ++g) {
-                            const uint32_t padded = ((P.spr + (1u << g) - 1u) >> g) << g;
-                            if (padded <= best) { best = padded; lg = g; }
-                        }
-                    }
-                    P.lpr_log2 = lg;
-                    P.block0 = blocks;
-                    const uint64_t nb = (rows + rpw - 1) / rpw;
-                    if (nb + blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-                    blocks += (uint32_t)nb;
-                }
+        const uint32_t es = (uint32_t)svr_dtype_size(c->density_storage);
+        const RingPass pass = {es, 16u / es, reinterpret_cast<uintptr_t>(L.density), ring_workgroups(c->device, kHistWgPerCu), kHistMinShare};
+        RingPlan plan;
+        if (!ring_plan(a.ring, L.state.offset, lo, n, pass, plan)) return hipErrorInvalidValue;
+        a.pieces = plan.pieces;
+        const uint32_t blocks = plan.blocks;
         const bool filt = nsel > 0;
         if (c->density_storage == SVR_U8)       hist_launch_typed<uint8_t>(a, filt, blocks, stream);
         else if (c->density_storage == SVR_U16) hist_launch_typed<uint16_t>(a, filt, blocks, stream);

@@ -1,11 +1,11 @@
 // Per-object measurements of the resident rings (svr_objects, include/svr.h): one streaming pass over a box of one
 // LOD's window that fills an open-addressed table of records, one per label.  gfx950.
 //
-// Decomposition.  svr_launch_histogram's: the host cuts box and window at the ring's wrap seams into at most 2 x 2 x 2
-// dense pieces (ring_pieces.h); a workgroup of 256 threads takes a run of whole rows of one piece; element offsets are
-// 64-bit.  A lane owns one slot of 4 consecutive voxels, aligned to 16 bytes of the LABEL ring: a slot wholly inside
-// the row is one 16-byte label load and one 4 / 8 / 16-byte density load, the slots at the row's head and tail read
-// their own elements one by one.  2^k lanes share a row, as in the histogram.
+// Decomposition.  The histogram's, stated once in ring_pieces.h: the host cuts box and window at the ring's wrap seams
+// into at most 2 x 2 x 2 dense pieces; a workgroup of 256 threads takes a run of whole rows of one piece; element
+// offsets are 64-bit.  A lane owns one slot of 4 consecutive voxels, aligned to 16 bytes of the LABEL ring: a slot
+// wholly inside the row is one 16-byte label load and one 4 / 8 / 16-byte density load, the slots at the row's head
+// and tail read their own elements one by one.  2^k lanes share a row, as in the histogram.
 //
 // Merging before any atomic.  A lane's 4 voxels collapse into runs of equal labels (geometry of a run is arithmetic:
 // its x span gives count, sum, min and max; y and z are the row's).  A lane whose slot is one label ("solid") joins
@@ -21,6 +21,9 @@
 // minima travel as complemented keys under atomicMax, so an untouched record stays all-zero and needs no clean-up.
 // obj_finish_kernel decodes the keys of the occupied records, counts them and writes the header's offsets.
 // No float atomics except the f64 value_sum of float32 rings; vmin / vmax are u32 keys (ring_pieces.h).
+#include <string.h>
+
+#include "svr_internal.h"
 #include "ring_pieces.h"
 
 static_assert(sizeof(svr_object_record) == 96, "svr_object_record is 96 bytes");
@@ -28,23 +31,16 @@ static_assert(sizeof(svr_object_record) == 96, "svr_object_record is 96 bytes");
 namespace {
 
 constexpr int kObjThreads = 256;
-constexpr int kObjMaxPieces = 8;
 constexpr uint32_t kLdsSlots = 512;          // 40 KB of LDS per workgroup: three workgroups per CU
 constexpr uint32_t kLdsProbes = 8;
-constexpr size_t kObjWgPerCu = 3;
-constexpr size_t kObjMinShare = 65536;       // bytes read per workgroup at least: the flush costs ~15 global atomics per label
+constexpr uint64_t kObjWgPerCu = 3;
+constexpr uint64_t kObjMinShare = 65536;      // bytes read per workgroup at least: the flush costs ~15 global atomics per label
 constexpr unsigned long long kUsed = 1ull << 32;
 
-struct ObjPiece {
-    uint32_t s[3];             // first ring slot (x, y, z)
-    uint32_t n[3];             // extent; s + n <= ring on every axis
-    uint32_t rel[3];           // logical coordinate of the first voxel, relative to the window offset
-    uint32_t rows;             // n[1] * n[2]
-    uint32_t rows_per_wg;
-    uint32_t block0;           // first workgroup of this piece
-    uint32_t lpr_log2;         // log2 of the lanes that share a row
-    uint32_t spr;              // 4-voxel slots a row can touch
-};
+// a piece with the logical coordinate of its first voxel, relative to the window offset, where the kernels' arguments
+// have always had it: between extent and rows
+struct ObjRel { uint32_t rel[3]; };
+struct ObjPiece : RingBox, ObjRel, RingShare {};
 
 struct ObjArgs {
     const void* density;
@@ -58,7 +54,7 @@ struct ObjArgs {
     uint32_t capacity;
     unsigned long long* header;
     int32_t npieces;
-    ObjPiece piece[kObjMaxPieces];
+    ObjPiece piece[kRingMaxPieces];    // slots of 4 voxels
 };
 
 // what a record holds during the pass.  Same layout as svr_object_record; lo / hi / vmin / vmax are keys that only grow
@@ -222,14 +218,8 @@ __global__ __launch_bounds__(kObjThreads) void obj_kernel(const ObjArgs a) {
     }
     __syncthreads();
 
-    // the piece this workgroup belongs to (wave-uniform)
-    int pi = 0;
-    while (pi + 1 < a.npieces && blockIdx.x >= a.piece[pi + 1].block0) ++pi;
-    const ObjPiece& P = a.piece[pi];
-    const uint32_t r0 = (blockIdx.x - P.block0) * P.rows_per_wg;
-    const uint32_t r1 = (uint32_t)min((uint64_t)P.rows, (uint64_t)r0 + P.rows_per_wg);
-    const uint32_t lpr = 1u << P.lpr_log2, rows_per_iter = kObjThreads >> P.lpr_log2;
-    const uint32_t lane_row = tid >> P.lpr_log2, lane_slot = tid & (lpr - 1u);
+    RING_WALK(kObjThreads, a, blockIdx.x, tid);
+    const uint32_t* const rel = P.rel;
     const uint32_t lane = __lane_id();
     const uint32_t nx = P.n[0];
     const T* const ring = static_cast<const T*>(a.density);
@@ -247,12 +237,12 @@ __global__ __launch_bounds__(kObjThreads) void obj_kernel(const ObjArgs a) {
         const bool row_ok = rb + lane_row < r1;
         const uint32_t row = (uint32_t)(rb + lane_row);
         const uint32_t ry = row_ok ? row % P.n[1] : 0u, rz = row_ok ? row / P.n[1] : 0u;
-        const size_t e0 = ((size_t)(P.s[2] + rz) * (size_t)a.ring[1] + (size_t)(P.s[1] + ry)) * (size_t)a.ring[0] + (size_t)P.s[0];
+        const size_t e0 = RING_ROW_OFFSET(P, a.ring, ry, rz);
         const T* const rowp = ring + e0;
         const uint32_t* const lrow = a.labels ? a.labels + e0 : nullptr;
         // elements before the row in its first slot: slots are aligned to 16 bytes of the label ring
         const uint32_t head = a.labels ? (uint32_t)((reinterpret_cast<uintptr_t>(lrow) & 15u) / 4u) : (uint32_t)(e0 & 3u);
-        const uint32_t yrel = P.rel[1] + ry, zrel = P.rel[2] + rz;
+        const uint32_t yrel = rel[1] + ry, zrel = rel[2] + rz;
         for (uint32_t sb = 0; sb < P.spr; sb += lpr) {
             const uint32_t slot = sb + lane_slot;
             // the slot holds row elements [first, first + 4), of which [0, nx) exist
@@ -393,7 +383,7 @@ __global__ __launch_bounds__(kObjThreads) void obj_kernel(const ObjArgs a) {
                         r.vsum = F32 ? (unsigned long long)__double_as_longlong(dsum) : (unsigned long long)isum;
                     }
                     // geometry: x from first + s over n voxels, relative to the window offset
-                    const uint32_t xrel = P.rel[0] + (uint32_t)(first + (int64_t)s);
+                    const uint32_t xrel = rel[0] + (uint32_t)(first + (int64_t)s);
                     r.n = n;
                     r.s[0] = (unsigned long long)n * xrel + ((unsigned long long)n * (n - 1u)) / 2ull;
                     r.s[1] = (unsigned long long)n * yrel;
@@ -487,58 +477,19 @@ hipError_t svr_launch_objects(const svr_ctx* c, int lod, const int64_t lo[3], co
         a.density = L.density; a.labels = L.labels;
         a.sel = sel; a.nsel = nsel; a.ignore_zero = ignore_zero;
         a.records = out.records; a.capacity = capacity; a.header = header;
-        const size_t es = svr_dtype_size(c->density_storage);
-        uint32_t s[3][2], m[3][2]; int cnt[3];
-        const size_t total = ring_cut_at_seams(L, lo, n, s, m, cnt);
         for (int ax = 0; ax < 3; ++ax) { a.ring[ax] = (uint32_t)L.ring[ax]; a.off[ax] = L.state.offset[ax]; }
-        // a workgroup's share of the bytes read (density + 4 of label per voxel)
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
-        size_t bytes_per_wg = total * (es + 4) / ((size_t)cus * kObjWgPerCu);
-        if (bytes_per_wg < kObjMinShare) bytes_per_wg = kObjMinShare;
-        uint32_t blocks = 0;
-        a.npieces = 0;
-        for (int iz = 0; iz < cnt[2]; ++iz)
-            for (int iy = 0; iy < cnt[1]; ++iy)
-                for (int ix = 0; ix < cnt[0]; ++ix) {
-                    ObjPiece& P = a.piece[a.npieces++];
-                    const int idx[3] = {ix, iy, iz};
-                    for (int ax = 0; ax < 3; ++ax) {
-                        P.s[ax] = s[ax][idx[ax]]; P.n[ax] = m[ax][idx[ax]];
-                        P.rel[ax] = (uint32_t)(lo[ax] - (int64_t)L.state.offset[ax]) + (idx[ax] ? m[ax][0] : 0u);
-                    }
-                    const uint64_t rows = (uint64_t)P.n[1] * P.n[2];
-                    if (rows > 0xFFFFFFFFull) return hipErrorInvalidValue;      // not with int32 ring extents below 2^16 x 2^16 rows
-                    P.rows = (uint32_t)rows;
-                    const size_t row_bytes = (size_t)P.n[0] * (es + 4);
-                    uint64_t rpw = (bytes_per_wg + row_bytes - 1) / row_bytes;
-                    const uint64_t cap = 0xFFFFFFFFull / P.n[0];                 // rows_per_wg * n[0] < 2^32: u32 counters
-                    if (rpw > cap) rpw = cap;
-                    if (rpw > rows) rpw = rows;
-                    if (rpw < 1) rpw = 1;
-                    P.rows_per_wg = (uint32_t)rpw;
-                    // slots per row: one more than the row's own where a row may start inside a slot
-                    const bool aligned = L.labels
-                        ? (reinterpret_cast<uintptr_t>(L.labels) + (size_t)P.s[0] * 4) % 16 == 0 && ((size_t)a.ring[0] * 4) % 16 == 0
-                        : P.s[0] % 4 == 0 && a.ring[0] % 4 == 0;
-                    P.spr = (P.n[0] + 3u) / 4u + (aligned ? 0u : 1u);
-                    // lanes per row: the power of two that covers the slots, or for longer rows the one (at least 8
-                    // lanes) whose multiple wastes the fewest lanes
-                    uint32_t lg = 0;
-                    while (lg < 3u && (1u << lg) < P.spr) ++lg;
-                    if (P.spr > 8u) {
-                        uint32_t best = 0xFFFFFFFFu;
-                        for (uint32_t g = 3u; g <= 8u; ++g) {
-                            const uint32_t padded = ((P.spr + (1u << g) - 1u) >> g) << g;
-                            if (padded <= best) { best = padded; lg = g; }
-                        }
-                    }
-                    P.lpr_log2 = lg;
-                    P.block0 = blocks;
-                    const uint64_t nb = (rows + rpw - 1) / rpw;
-                    if (nb + blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-                    blocks += (uint32_t)nb;
-                }
+        // a workgroup's share of the bytes read (density + 4 of label per voxel); slots are 16 bytes of the label ring
+        const uint32_t es = (uint32_t)svr_dtype_size(c->density_storage);
+        const RingPass pass = {es + 4u, 4u, reinterpret_cast<uintptr_t>(L.labels), ring_workgroups(c->device, kObjWgPerCu), kObjMinShare};
+        RingPlan plan;
+        if (!ring_plan(a.ring, a.off, lo, n, pass, plan)) return hipErrorInvalidValue;
+        a.npieces = plan.pieces.npieces;
+        for (int p = 0; p < a.npieces; ++p) {
+            static_cast<RingBox&>(a.piece[p]) = plan.pieces.piece[p];
+            static_cast<RingShare&>(a.piece[p]) = plan.pieces.piece[p];
+            memcpy(a.piece[p].rel, plan.rel[p], sizeof(plan.rel[p]));
+        }
+        const uint32_t blocks = plan.blocks;
         const bool filt = nsel > 0;
         if (c->density_storage == SVR_U8)       obj_launch_typed<uint8_t>(a, filt, blocks, stream);
         else if (c->density_storage == SVR_U16) obj_launch_typed<uint16_t>(a, filt, blocks, stream);

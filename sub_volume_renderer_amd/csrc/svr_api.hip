@@ -1297,27 +1297,40 @@ int svr_slab(svr_ctx* c, const svr_slab_params* sp, const svr_frame* fr, const s
     return SVR_DRAW_ORDERED(c, stream, svr_launch_slab(c, *sp, dw, f, *out, twin_mode, interpolation_of(c), s));
 }
 
+// What svr_histogram and svr_objects check before and after their own checks (who: the entry point's name, the prefix
+// of its error texts): the lod; then a box's shape, the id list, and lo, n: the intersection of box and window in the
+// LOD's logical voxels.  In 64 bits (box_off + box_shape may pass 2^31); a window of None has shape 0 and holds
+// nothing, so an n may be <= 0.
+static int box_lod(const char* who, const svr_ctx* c, int lod) {
+    SVR_REQUIRE(lod >= 0 && lod < c->num_lods, std::string(who) + ": lod out of range");
+    return SVR_OK;
+}
+static int box_window(const char* who, const svr_ctx* c, int lod, int use_box, const int32_t box_off[3], const int32_t box_shape[3],
+                      const uint32_t* selected, uint32_t selected_count, int64_t lo[3], int64_t n[3]) {
+    if (use_box)
+        for (int a = 0; a < 3; ++a) SVR_REQUIRE(box_shape[a] >= 0, std::string(who) + ": negative box_shape");
+    SVR_REQUIRE(selected_count == 0 || selected, std::string(who) + ": selected_count > 0 with a NULL selected pointer");
+    const svr_lod_state& st = c->lod[lod].state;
+    for (int a = 0; a < 3; ++a) {
+        int64_t b = st.offset[a], e = (int64_t)st.offset[a] + st.shape[a];
+        if (use_box) {
+            b = std::max<int64_t>(b, box_off[a]);
+            e = std::min<int64_t>(e, (int64_t)box_off[a] + box_shape[a]);
+        }
+        lo[a] = b; n[a] = e - b;
+    }
+    return SVR_OK;
+}
+
 int svr_histogram(svr_ctx* c, const svr_histogram_params* hp, const svr_histogram_outputs* out, void* stream) {
     SVR_REQUIRE(c && hp && out && out->counts, "svr_histogram: null argument");
-    SVR_REQUIRE(hp->lod >= 0 && hp->lod < c->num_lods, "svr_histogram: lod out of range");
+    { const int rc = box_lod("svr_histogram", c, hp->lod); if (rc) return rc; }
     SVR_REQUIRE(hp->bins >= 1 && hp->bins <= SVR_HIST_MAX_BINS, "svr_histogram: bins must be in 1 .. 4096");
     SVR_REQUIRE(isfinite(hp->lo) && isfinite(hp->hi) && hp->lo < hp->hi, "svr_histogram: lo and hi must be finite, lo < hi");
     const float inv = (float)hp->bins / (hp->hi - hp->lo);
     SVR_REQUIRE(isfinite(inv), "svr_histogram: bins / (hi - lo) is not finite in f32");
-    if (hp->use_box)
-        for (int a = 0; a < 3; ++a) SVR_REQUIRE(hp->box_shape[a] >= 0, "svr_histogram: negative box_shape");
-    SVR_REQUIRE(hp->selected_count == 0 || hp->selected, "svr_histogram: selected_count > 0 with a NULL selected pointer");
-    // the intersection of box and window, in 64 bits (box_off + box_shape may pass 2^31); a window of None has shape 0 and holds nothing
-    const svr_lod_state& st = c->lod[hp->lod].state;
     int64_t lo[3], n[3];
-    for (int a = 0; a < 3; ++a) {
-        int64_t b = st.offset[a], e = (int64_t)st.offset[a] + st.shape[a];
-        if (hp->use_box) {
-            b = std::max<int64_t>(b, hp->box_off[a]);
-            e = std::min<int64_t>(e, (int64_t)hp->box_off[a] + hp->box_shape[a]);
-        }
-        lo[a] = b; n[a] = e - b;
-    }
+    { const int rc = box_window("svr_histogram", c, hp->lod, hp->use_box, hp->box_off, hp->box_shape, hp->selected, hp->selected_count, lo, n); if (rc) return rc; }
     const int lod = hp->lod, K = hp->bins;
     const float flo = hp->lo, fhi = hp->hi;
     const uint32_t* sel = hp->selected; const uint32_t nsel = hp->selected_count;
@@ -1326,22 +1339,10 @@ int svr_histogram(svr_ctx* c, const svr_histogram_params* hp, const svr_histogra
 
 int svr_objects(svr_ctx* c, const svr_objects_params* op, const svr_objects_outputs* out, void* stream) {
     SVR_REQUIRE(c && op && out && out->records && out->header, "svr_objects: null argument");
-    SVR_REQUIRE(op->lod >= 0 && op->lod < c->num_lods, "svr_objects: lod out of range");
+    { const int rc = box_lod("svr_objects", c, op->lod); if (rc) return rc; }
     SVR_REQUIRE(op->capacity >= 1 && op->capacity <= SVR_OBJECTS_MAX_CAPACITY, "svr_objects: capacity must be in 1 .. 2^26");
-    if (op->use_box)
-        for (int a = 0; a < 3; ++a) SVR_REQUIRE(op->box_shape[a] >= 0, "svr_objects: negative box_shape");
-    SVR_REQUIRE(op->selected_count == 0 || op->selected, "svr_objects: selected_count > 0 with a NULL selected pointer");
-    // the intersection of box and window, as svr_histogram takes it
-    const svr_lod_state& st = c->lod[op->lod].state;
     int64_t lo[3], n[3];
-    for (int a = 0; a < 3; ++a) {
-        int64_t b = st.offset[a], e = (int64_t)st.offset[a] + st.shape[a];
-        if (op->use_box) {
-            b = std::max<int64_t>(b, op->box_off[a]);
-            e = std::min<int64_t>(e, (int64_t)op->box_off[a] + op->box_shape[a]);
-        }
-        lo[a] = b; n[a] = e - b;
-    }
+    { const int rc = box_window("svr_objects", c, op->lod, op->use_box, op->box_off, op->box_shape, op->selected, op->selected_count, lo, n); if (rc) return rc; }
     const int lod = op->lod, ignore_zero = op->ignore_zero;
     const uint32_t* sel = op->selected; const uint32_t nsel = op->selected_count, capacity = op->capacity;
     return SVR_DRAW_ORDERED(c, stream, svr_launch_objects(c, lod, lo, n, sel, nsel, ignore_zero, capacity, *out, s));

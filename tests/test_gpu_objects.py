@@ -219,6 +219,44 @@ def test_boxes(kind):
     same(c_objects(vol, 1, 1024, box=box, ignore_zero=True), twin_of(kind, 1, box=box, ignore_zero=True), 1024, (kind, "lod 1"))
 
 
+def c_histogram_considered(vol, lod, box=None, labels=None):
+    """tail[3] of one svr_histogram call: every voxel it considered, whatever its value."""
+    dev = torch.device("cuda", vol._rings.device)
+    counts, tail = torch.full((1,), -7, dtype=torch.int64, device=dev), torch.full((4,), -7, dtype=torch.int64, device=dev)
+    hp = N.HistogramParams(lod=lod, lo=0.0, hi=256.0, bins=1)
+    if box is not None:
+        hp.use_box = 1
+        hp.box_off[:], hp.box_shape[:] = box
+    sel = None
+    if labels is not None:
+        sel = torch.from_numpy(np.unique(np.asarray(labels, np.uint32)).view(np.int32)).to(dev)
+        hp.selected, hp.selected_count = sel.data_ptr(), sel.numel()
+    ho = N.HistogramOutputs(counts.data_ptr(), tail.data_ptr(), None)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    N.check(N.lib().svr_histogram(vol.prepare(), C.byref(hp), C.byref(ho), C.c_void_p(stream)), "svr_histogram")
+    torch.cuda.synchronize()
+    return int(tail[3])
+
+
+@pytest.mark.parametrize("kind", ["u8", "f32"])
+def test_histogram_and_objects_consider_the_same_voxels(kind):
+    """Both passes walk box and window through the same plan (csrc/ring_pieces.h), the histogram in slots of 16 or 4
+    voxels aligned to the density ring, the objects pass in slots of 4 aligned to the label ring: the voxels they
+    consider are the same, with ignore_zero the dropped label-0 voxels included.  Integers, so ``==``."""
+    vol, _ = scene_of(kind)
+    ids = sorted(twin_of(kind, 0)["objects"])
+    some = [0, ids[len(ids) // 2], 0xFFFFFFFF, ids[len(ids) // 2] + 1]
+    for name, box in BOXES:
+        for labels in (None, some):
+            considered = c_histogram_considered(vol, 0, box, labels)
+            _, header = c_objects(vol, 0, 2048, box=box, labels=labels)
+            assert considered == int(header[1]), (kind, name, labels)
+            _, header = c_objects(vol, 0, 2048, box=box, labels=labels, ignore_zero=True)
+            assert considered == int(header[1]) + int(header[3]), (kind, name, labels)
+            if labels is None and name == "window":
+                assert considered == WINDOW0 and int(header[3]) > 0
+
+
 def test_selected():
     vol, rings = scene_of("u8")
     ids = sorted(twin_of("u8", 0)["objects"])
