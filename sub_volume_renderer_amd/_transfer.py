@@ -21,7 +21,7 @@ def _srgb_to_linear(c: np.ndarray) -> np.ndarray:
 
 
 def nominal_step(volume_dimensions) -> np.float32:
-    """The march's sample spacing in voxels, as ``svr_api.hip`` computes it in f32 (fs_main.wgsl:20):
+    """The march's sample spacing in voxels, as ``svr_render.hip`` computes it in f32 (fs_main.wgsl:20):
     ``min(max(sqrt(max(size)) / 20, 0.1), 0.8)``."""
     mx = max(np.float32(v) for v in volume_dimensions)
     return np.float32(min(max(np.sqrt(np.float32(mx)) / np.float32(20.0), np.float32(0.1)), np.float32(0.8)))

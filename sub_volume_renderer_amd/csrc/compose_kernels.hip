@@ -6,7 +6,7 @@
 // (parity unpinned).  Pure HBM streaming: 21 B read + 4 B written per pixel, one thread per pixel.
 #include <algorithm>
 
-#include "svr_internal.h"
+#include "svr_host.h"
 
 namespace {
 

@@ -11,6 +11,7 @@
 // Arithmetic contract: strict IEEE f32 without contraction (-ffp-contract=off), operation order as written in svr.h.
 // Ray set-up, LOD test and the small helpers are ray_common.h's; tests/test_gpu_composite.py holds this kernel to
 // tests/composite_twin.py.
+#include "svr_host.h"
 #include "ray_common.h"
 #include "linear_sample.h"
 
@@ -257,7 +258,7 @@ __global__ __launch_bounds__(256) void composite_kernel(const CompParams P) {
 
 }  // namespace
 
-// Declared in svr_api.hip, which validates the arguments, orders the launch against the uploads and marks it as a
+// svr_composite has validated the arguments; it orders the launch against the uploads and marks it as a
 // render.  table: the device copy of the transfer function (K entries of RGBA).  interp: SVR_INTERP_*.  cut_planes:
 // cut_count x abcd of svr_set_cut_planes (host), cut_mode: SVR_CUT_*; any plane selects the CUT instantiations, which
 // doubles the kernels of this file (8 LOD counts x 3 element sizes x TINT x LIN x CUT = 192).

@@ -20,7 +20,7 @@
 //      eight on the first lane's bin, tested on one element per slot) skips the merging: on noise it only costs.
 // A constant ring thus costs one LDS atomic per wave and 1 KiB read.  Counts are integers: the result does not
 // depend on arrival order.  No float atomics anywhere: min / max travel as u32 keys that order like the floats.
-#include "svr_internal.h"
+#include "svr_host.h"
 #include "ring_pieces.h"
 
 namespace {

@@ -23,7 +23,7 @@
 // No float atomics except the f64 value_sum of float32 rings; vmin / vmax are u32 keys (ring_pieces.h).
 #include <string.h>
 
-#include "svr_internal.h"
+#include "svr_host.h"
 #include "ring_pieces.h"
 
 static_assert(sizeof(svr_object_record) == 96, "svr_object_record is 96 bytes");

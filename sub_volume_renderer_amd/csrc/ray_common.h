@@ -176,7 +176,7 @@ __device__ __forceinline__ bool setup_ray(const Params& P, int i, int j, Ray& R)
 
 // ---- cut planes (svr_set_cut_planes, include/svr.h) -------------------------------------------------------------------
 
-// The context's planes as the caller gave them (host state, kept by svr_api.hip).
+// The context's planes as the caller gave them (host state: CutState of svr_host.h).
 struct CutPlanes {
     uint32_t count;
     int32_t  mode;                                 // SVR_CUT_ANY / SVR_CUT_ALL

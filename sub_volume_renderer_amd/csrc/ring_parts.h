@@ -1,6 +1,6 @@
 // How the march reaches one LOD's density ring: through one buffer resource, or, for a ring of 4 GiB or more, through
 // up to 8 resources of `zsplit` whole ring z planes each (LodParams::nparts / zsplit / part_bytes / rbytes_last in
-// svr_internal.h).  Plain host C++ on plain integers, so that a test can compile it without HIP: svr_api.hip decides the
+// svr_internal.h).  Plain host C++ on plain integers, so that a test can compile it without HIP: svr_render.hip decides the
 // split here and nowhere else.
 #pragma once
 

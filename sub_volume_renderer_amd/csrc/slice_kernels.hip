@@ -5,6 +5,7 @@
 // Arithmetic contract: strict IEEE f32 without contraction (-ffp-contract=off), operation order as written in svr.h.
 // LOD test and the small helpers are ray_common.h's; tests/test_gpu_slice.py holds this kernel and the march to the same
 // numpy restatement.
+#include "svr_host.h"
 #include "ray_common.h"
 #include "linear_sample.h"
 
@@ -374,8 +375,8 @@ float row_lines(int esh, const float e[3], float cap = 64.0f) {
 
 }  // namespace
 
-// Declared in svr_api.hip (which validates the arguments, orders the launch against the uploads and marks it as a
-// render).  twin_mode: 0 rows only, 2 the micro-block copy wherever there is one, 1 per LOD the fewer lines (the
+// svr_slice has validated the arguments; it orders the launch against the uploads and marks it as a
+// render.  twin_mode: 0 rows only, 2 the micro-block copy wherever there is one, 1 per LOD the fewer lines (the
 // estimate is the nearest sample's under either interpolation: a cell adds one voxel per axis to the footprint).
 // interp: SVR_INTERP_*.
 hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const svr_frame& fr, const svr_slice_outputs& out,
@@ -401,7 +402,7 @@ hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const s
     });
 }
 
-// Declared in svr_api.hip, like svr_launch_slice; svr_slab has validated the arguments and computed dw.
+// Like svr_launch_slice; svr_slab has validated the arguments and computed dw.
 // Micro-block copy routing per LOD over the whole slab (twin_mode 1).  A wave's N gathers of 64 lanes cost, per layout,
 //   the lines each gather walks (the slice's estimate of the tile on one plane: a gather touching 64 lines takes the
 //   texture unit 64 passes even when they are cached), summed over the N samples, plus

@@ -1,0 +1,76 @@
+// What the host units of the C ABI (svr_api.hip, svr_upload.hip, svr_render.hip, svr_modes.hip) share with one another
+// and with the kernel units whose launchers they call.  Kept apart from svr_internal.h, whose bytes are part of the
+// kernel-source stamp bench.py checks its traffic profile against.
+#pragma once
+
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "svr_internal.h"
+
+#define SVR_REQUIRE(cond, msg)                    \
+    do {                                          \
+        if (!(cond)) {                            \
+            svr_set_error(msg);                   \
+            return SVR_ERR_INVALID;               \
+        }                                         \
+    } while (0)
+
+// launchers of the kernel units, which include this header too --------------------------------------------------------
+// compose_kernels.hip
+hipError_t svr_launch_outline(const float* rgba, const float* depth, const uint32_t* label, const uint8_t* flags, int w,
+                              int h, const svr_outline_params& q, const float* colors, uint32_t ncolors,
+                              const uint32_t* sel, uint32_t nsel, float* out, uint8_t* mask, hipStream_t stream);
+// slice_kernels.hip.  twin_mode: 0 rows only, 1 per LOD the layout with fewer lines per wave, 2 the copy.
+hipError_t svr_launch_slice(const svr_ctx* c, const svr_slice_plane& pl, const svr_frame& fr, const svr_slice_outputs& out,
+                            int twin_mode, int interp, hipStream_t stream);
+// slice_kernels.hip.  dw: the data-space sample step, computed and checked by svr_slab.
+hipError_t svr_launch_slab(const svr_ctx* c, const svr_slab_params& sp, const float dw[3], const svr_frame& fr,
+                           const svr_slice_outputs& out, int twin_mode, int interp, hipStream_t stream);
+// composite_kernels.hip.  table: the device copy of the transfer function, K entries of RGBA.
+hipError_t svr_launch_composite(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr,
+                                const svr_composite_params& cp, const svr_outputs& out, const float* table, int K,
+                                int interp, const float* cut_planes, uint32_t cut_count, int cut_mode,
+                                hipStream_t stream);
+// iso_kernels.hip.  cut_planes: cut_count x abcd of svr_set_cut_planes (host), cut_mode: SVR_CUT_*.
+hipError_t svr_launch_iso(const svr_ctx* c, const svr_camera& cam, const svr_frame& fr, const svr_iso_params& ip,
+                          const svr_outputs& out, int interp, const float* cut_planes, uint32_t cut_count, int cut_mode,
+                          hipStream_t stream);
+// histogram_kernels.hip.  lo, n: box and window intersected, in the LOD's logical voxels (an n <= 0: nothing
+// to count); inv = (float)K / (hi - lo); everything checked by svr_histogram.
+hipError_t svr_launch_histogram(const svr_ctx* c, int lod, const int64_t lo[3], const int64_t n[3], float flo, float fhi,
+                                float inv, int K, const uint32_t* sel, uint32_t nsel, const svr_histogram_outputs& out,
+                                hipStream_t stream);
+// object_kernels.hip.  lo, n as above; everything checked by svr_objects.
+hipError_t svr_launch_objects(const svr_ctx* c, int lod, const int64_t lo[3], const int64_t n[3], const uint32_t* sel, uint32_t nsel,
+                              int ignore_zero, uint32_t capacity, const svr_objects_outputs& out, hipStream_t stream);
+
+// the context as svr_create really allocates it ------------------------------------------------------------------------
+// The state of svr_set_transfer_function, svr_set_interpolation and svr_set_cut_planes (svr_modes.hip).  Like the colour
+// table of svr_set_material, every new transfer function goes into a fresh device buffer; the replaced ones are freed
+// once the device has drained (or with the context).  A context starts with no table (tf_dev null),
+// SVR_INTERP_NEAREST and no planes.
+struct CutState {
+    uint32_t count;
+    int mode;
+    float planes[SVR_MAX_CUT_PLANES][4];
+};
+struct svr_ctx_ext : svr_ctx {
+    std::mutex modes_mu;                   // setters write under it; a draw copies what it needs under it and launches outside
+    float* tf_dev = nullptr;
+    int tf_K = 0;
+    std::vector<float*> tf_retired;
+    int interp = SVR_INTERP_NEAREST;
+    CutState cut = {};
+};
+// (every svr_ctx* of the ABI comes from svr_create)
+inline svr_ctx_ext* svr_ext(svr_ctx* c) { return static_cast<svr_ctx_ext*>(c); }
+
+// helpers of more than one unit (svr_api.hip) ---------------------------------------------------------------------------
+// off, shape inside LOD lod's ring?  who: the entry point's name, the prefix of the error texts.
+int check_region(svr_ctx* c, int lod, const int32_t off[3], const int32_t shape[3], const char* who);
+// Before an upload's first enqueue: order the upload stream behind every render still in flight ...
+int uploads_after_render(svr_ctx* c);
+// ... which every draw that reads the rings registers, right behind its launch on stream s.
+int mark_render(svr_ctx* c, hipStream_t s);

@@ -3,8 +3,8 @@ steps, label and pick bit for bit, rgba and depth within 1e-4 — u8 / u16 / flo
 and 3 LODs (every count 1 .. 8: tests/test_gpu_lod_counts.py), no / "auto" / "all" micro-block copies, perspective and orthographic cameras, a rotated and scaled world,
 clipping planes ANY and ALL, cutoffs 1.0 / 0.99 / 0.5 with and without the label tint, and a fly-through that wraps
 the rings.  Also: tiles and stripes, out= in place, outline / compose on a composite, a float ring beyond 4 GiB, the
-table sent only when it changes, every refusal with nothing launched, and LMIP / MIP / weighted-average frames that a
-composite render leaves bit-identical."""
+table sent only when it changes, every refusal with nothing launched, LMIP / MIP / weighted-average frames that a
+composite render leaves bit-identical, and two contexts that keep their tables, sampling and cut planes apart."""
 import ctypes as C
 
 import numpy as np
@@ -352,3 +352,86 @@ def test_refusals_launch_nothing():
     assert not bool((out.flags == 7).any()) and int((out.flags == HIT).sum()) > 100
     assert set(out.flags.unique().tolist()) <= {DISCARD, MISS, HIT}
     vol.close()
+
+
+def test_two_contexts_keep_their_mode_state_apart():
+    """Table, sampling and cut planes belong to the context.  The package sends sampling and planes before every draw,
+    which would hide a mix-up, so each context gets its state once (its first render) and is then drawn through the ABI
+    with no setter in between, in the order A, B, A.  A context created after one was destroyed starts empty."""
+    from slice_twin import twin_of_spec
+    from sub_volume_renderer_amd import SubVolume
+    from test_gpu_slice import check as check_slice
+
+    W, H = 40, 30
+    lib = N.lib()
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def small_scene():                                    # 32^3 u8, one LOD
+        spec = testing.synthetic_spec(32, W, H)
+        spec.pairs, spec.chunk_shapes, spec.ring_shapes = spec.pairs[:1], spec.chunk_shapes[:1], spec.ring_shapes[:1]
+        scene = testing.build(spec)
+        assert scene.volume._rings.density_storage == "uint8" and len(scene.volume._rings.ring_shapes) == 1
+        return spec, scene.volume, scene.camera
+
+    def raw_composite(vol, cam):
+        out = RenderResult(torch.full((H, W, 4), 7.0, device=dev), torch.full((H, W), 7.0, device=dev),
+                           torch.full((H, W), 7, dtype=torch.int32, device=dev), torch.full((H, W), 7, dtype=torch.uint8, device=dev),
+                           torch.full((H, W), 7, dtype=torch.int32, device=dev), torch.full((H, W), 7, dtype=torch.int64, device=dev))
+        ob = N.Outputs()
+        for name in ("rgba", "depth", "label", "flags", "steps", "pick"):
+            setattr(ob, name, getattr(out, name).data_ptr())
+        ob.pick_id = vol.id & 0xFFFFFFFF
+        cb, fb = vol._camera_block_uncached(cam), vol.frame_block(W, H, None)
+        cp = N.CompositeParams(vol.material.alpha_cutoff, 1 if vol.material.color_by_label else 0)
+        rc = lib.svr_composite(vol._rings.handle, C.byref(cb), C.byref(fb), C.byref(cp), C.byref(ob), None)
+        torch.cuda.synchronize()
+        return rc, out
+
+    def ref_of(spec, vol, cam):
+        m, orac = vol.material, lmip.oracle_volume(spec)
+        return composite_twin(lmip.rings_of(orac), matrices_of(vol, cam), orac.volume_dimensions_shader,
+                              material_of(spec.material), m.transfer_function.device_table(vol._volume_dimensions), W, H,
+                              m.alpha_cutoff, m.color_by_label, pick_id=vol.id, cut_planes=m.cut_planes, cut_mode=m.cut_mode,
+                              linear=(m.interpolation == "linear"))
+
+    c = (15.5, 15.5, 15.5)
+    half = ([(0.8, -0.36, -0.48, 0.8 * c[0] - 0.36 * c[1] - 0.48 * c[2])], "ANY")
+    wedge = ([(1.0, 0.0, 0.0, c[0]), (0.0, -1.0, 0.0, -c[1]), (0.0, 0.0, -1.0, -c[2])], "ALL")
+    made = {}
+    for name, tf, cutoff, tint, interpolation, (planes, mode) in (("A", MID, 0.99, True, "nearest", half),
+                                                                 ("B", OPAQUE, 0.5, False, "linear", wedge)):
+        spec, vol, cam = small_scene()
+        composite_on(vol, tf, cutoff, tint)
+        vol.material.interpolation, vol.material.cut_planes, vol.material.cut_mode = interpolation, planes, mode
+        ref = ref_of(spec, vol, cam)
+        check(vol.render(cam, W, H, count_steps=True, pick=True), ref, (name, "first render"))
+        made[name] = (vol, cam, ref)
+    assert not np.array_equal(made["A"][2]["rgba"], made["B"][2]["rgba"])
+    assert all(int((ref["flags"] == HIT).sum()) > 100 for _, _, ref in made.values())
+    for name in "ABA":
+        vol, cam, ref = made[name]
+        rc, out = raw_composite(vol, cam)
+        assert rc == 0, lib.svr_last_error()
+        check(out, ref, (name, "through the ABI"))
+    # B goes, C comes (quite possibly at B's address): no table, nearest sampling
+    made["B"][0].close()
+    spec, vol, cam = small_scene()
+    vol.prepare()
+    rc, out = raw_composite(vol, cam)
+    assert rc == -1 and "svr_composite: svr_set_transfer_function has not been called" in lib.svr_last_error().decode()
+    assert bool((out.flags == 7).all())
+    origin, u, v = SubVolume.axis_slice_plane("z", c, 1.0)
+    res, pl, fb = vol._slice_outputs(H, W), vol._plane_struct(origin, u, v), vol.frame_block(W, H, None)
+    assert lib.svr_slice(vol._rings.handle, C.byref(pl), C.byref(fb), C.byref(vol._plane_ob(res)),
+                         C.c_void_p(vol._plane_stream(None))) == 0, lib.svr_last_error()
+    torch.cuda.synchronize()
+    near = twin_of_spec(spec, origin, u, v, W, H, linear=False)
+    check_slice(res, near, "slice on the new context")
+    assert int((near["flags"] == HIT).sum()) > 100
+    assert not np.array_equal(near["value"], twin_of_spec(spec, origin, u, v, W, H, linear=True)["value"])
+    # A is untouched by all that
+    rc, out = raw_composite(*made["A"][:2])
+    assert rc == 0
+    check(out, made["A"][2], ("A", "after B went"))
+    vol.close()
+    made["A"][0].close()

@@ -205,7 +205,11 @@ def test_the_host_derives_the_split_in_one_place():
 
     import __graft_entry__ as g
 
-    api = open(os.path.join(CSRC, "svr_api.hip")).read()
-    assert '#include "ring_parts.h"' in api and "ring_parts(" in api
-    assert "- 128) / plane" not in api and "zsplit &=" not in api
+    units = {name: open(os.path.join(CSRC, name)).read() for name in g.HIP_SOURCES if name.startswith("svr_")}
+    assert set(units) == {"svr_api.hip", "svr_upload.hip", "svr_render.hip", "svr_modes.hip"}     # the host units
+    render = units["svr_render.hip"]
+    assert '#include "ring_parts.h"' in render and "ring_parts(" in render
+    for name, text in units.items():
+        assert "- 128) / plane" not in text and "zsplit &=" not in text, name
+        assert name == "svr_render.hip" or "ring_parts" not in text, name
     assert "ring_parts.h" in inspect.getsource(g.build_hip)

@@ -27,7 +27,7 @@ for spec in sys.argv[1:]:
         subprocess.run(["hipcc", *cflags, *extra, "-c", os.path.join(g.CSRC, src), "-o", obj], check=True)
         return obj
 
-    # every translation unit is rebuilt with the flags (-DSVR_EXPERIMENTS reaches svr_api.hip and ring_kernels.hip too)
+    # every translation unit is rebuilt with the flags (-DSVR_EXPERIMENTS reaches the host units, svr_*.hip, and ring_kernels.hip too)
     units = [(s, os.path.join(objdir, s.replace(".hip", ".o")), []) for s in g.HIP_SOURCES]
     units += [("march_kernel.hip", os.path.join(objdir, f"march_nl{k}.o"), [f"-DSVR_NL={k}"]) for k in range(1, 9)]
     with ThreadPoolExecutor(8) as pool:
