@@ -780,6 +780,16 @@ int  svr_sync_uploads(svr_ctx* ctx);         /* upload stream idle */
 int  svr_lod_device_ptrs(svr_ctx* ctx, int lod, void** density, void** labels);
 /* the micro-block copy of the LOD's density ring (svr_lod_desc::blocked_twin), or NULL: tests compare it with the ring */
 int  svr_lod_twin_ptr(svr_ctx* ctx, int lod, void** twin);
+/* The macro-cell maxima of the LOD's density ring, which decide where the LMIP march and the iso kernel skip empty
+ * space: two DEVICE tables of cdim[2] x cdim[1] x cdim[0] elements of the ring's type (u8 / u16 / f32), x fastest,
+ * over cells of S^3 ring slots, S = 1 << *cshift (8 at LOD 0, 4 at the coarser LODs).  Once the upload stream is idle:
+ *   raw[cz][cy][cx] = fmax over the S^3 slots of the cell of |ring|, starting from 0 (a NaN never wins)
+ *   blk[cz][cy][cx] = max of raw[(cz+dz) % cdim[2]][(cy+dy) % cdim[1]][(cx+dx) % cdim[0]], d* in {0, 1}
+ * EXACTLY, over the ring as it lies in memory: a slot counts whether or not the published ROI maps it, stale slots of
+ * chunks that left the window too.  Holds after any sequence of svr_upload_region, svr_upload_region_device and
+ * svr_clear_lod (which zeroes both).  The kernels read blk.  A LOD whose ring extents are not all multiples of 8 has
+ * no tables: *raw = *blk = NULL (cdim and *cshift are still written).  Tests compare the tables with the ring. */
+int  svr_lod_cell_ptrs(svr_ctx* ctx, int lod, void** raw, void** blk, int32_t cdim[3], int32_t* cshift);
 
 /* diagnostics: batch census accumulated by instrumented renders (outputs.steps != NULL):
  * [0] general batches, [1] direct fast batches, [2] brick batches, [3] brick slabs, [4] runs,

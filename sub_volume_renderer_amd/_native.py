@@ -296,6 +296,8 @@ SIGNATURES = {
     "svr_debug_timers": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
     "svr_lod_device_ptrs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "svr_lod_twin_ptr": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "svr_lod_cell_ptrs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _I3,
+                                    C.POINTER(C.c_int32)]),
     "svr_time_render": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Frame),
                                   C.POINTER(Outputs), C.c_int, C.POINTER(C.c_float)]),
 }

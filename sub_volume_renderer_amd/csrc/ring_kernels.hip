@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "svr_internal.h"
+#include "cell_range.h"
 
 size_t svr_dtype_size(int dtype) {
     switch (dtype) {
@@ -170,8 +171,6 @@ template <> __device__ __forceinline__ float cell_abs<float>(float v) { return f
 template <typename T> __device__ __forceinline__ T cell_max(T a, T b) { return a > b ? a : b; }
 template <> __device__ __forceinline__ float cell_max<float>(float a, float b) { return fmaxf(a, b); }   // NaN never wins
 
-__device__ __forceinline__ int torus(int c, int n) { c %= n; return c < 0 ? c + n : c; }
-
 // One thread per cell, S * S rows of S slots each; neighbouring threads take neighbouring cells along x, so a
 // wave's loads of one row index cover 64 * S contiguous slots of a ring row: coalesced, every byte read once.
 template <typename T, int S>
@@ -179,9 +178,9 @@ __global__ __launch_bounds__(256) void cell_raw_kernel(const CellArgs a) {
     const int cell = (int)(blockIdx.x * 256u + threadIdx.x);
     const int total = a.cn[0] * a.cn[1] * a.cn[2];
     if (cell >= total) return;
-    const int cx = torus(a.c0[0] + cell % a.cn[0], a.cdim[0]);
-    const int cy = torus(a.c0[1] + (cell / a.cn[0]) % a.cn[1], a.cdim[1]);
-    const int cz = torus(a.c0[2] + cell / (a.cn[0] * a.cn[1]), a.cdim[2]);
+    const int cx = cell_torus(a.c0[0] + cell % a.cn[0], a.cdim[0]);
+    const int cy = cell_torus(a.c0[1] + (cell / a.cn[0]) % a.cn[1], a.cdim[1]);
+    const int cz = cell_torus(a.c0[2] + cell / (a.cn[0] * a.cn[1]), a.cdim[2]);
     typedef T row_t __attribute__((ext_vector_type(S)));            // one row of the cell: S * sizeof(T) bytes, aligned
     T m = 0;
     for (int z = 0; z < S; ++z) {
@@ -203,15 +202,15 @@ __global__ __launch_bounds__(256) void cell_block_kernel(const CellArgs a) {
     const int cell = (int)(blockIdx.x * 256u + threadIdx.x);
     const int total = a.cn[0] * a.cn[1] * a.cn[2];
     if (cell >= total) return;
-    const int cx = torus(a.c0[0] + cell % a.cn[0], a.cdim[0]);
-    const int cy = torus(a.c0[1] + (cell / a.cn[0]) % a.cn[1], a.cdim[1]);
-    const int cz = torus(a.c0[2] + cell / (a.cn[0] * a.cn[1]), a.cdim[2]);
+    const int cx = cell_torus(a.c0[0] + cell % a.cn[0], a.cdim[0]);
+    const int cy = cell_torus(a.c0[1] + (cell / a.cn[0]) % a.cn[1], a.cdim[1]);
+    const int cz = cell_torus(a.c0[2] + cell / (a.cn[0] * a.cn[1]), a.cdim[2]);
     const T* raw = static_cast<const T*>(a.raw);
     T m = raw[((size_t)cz * a.cdim[1] + cy) * a.cdim[0] + cx];
     for (int dz = 0; dz <= 1; ++dz)
         for (int dy = 0; dy <= 1; ++dy)
             for (int dx = 0; dx <= 1; ++dx) {
-                const int x = torus(cx + dx, a.cdim[0]), y = torus(cy + dy, a.cdim[1]), z = torus(cz + dz, a.cdim[2]);
+                const int x = cell_torus(cx + dx, a.cdim[0]), y = cell_torus(cy + dy, a.cdim[1]), z = cell_torus(cz + dz, a.cdim[2]);
                 m = cell_max(m, raw[((size_t)z * a.cdim[1] + y) * a.cdim[0] + x]);
             }
     static_cast<T*>(a.blk)[((size_t)cz * a.cdim[1] + cy) * a.cdim[0] + cx] = m;
@@ -371,13 +370,12 @@ hipError_t svr_launch_cell_update(const void* ring, int storage, const int32_t r
     if (!raw || !blk || shape[0] <= 0 || shape[1] <= 0 || shape[2] <= 0) return hipSuccess;
     CellArgs a;
     a.ring = ring; a.raw = raw; a.blk = blk; a.cshift = cshift;
+    const CellRanges r = cell_ranges_of(off, shape, cdim, cshift);      // cell_range.h
     for (int i = 0; i < 3; ++i) {
         a.ring_dims[i] = ring_dims[i]; a.cdim[i] = cdim[i];
-        a.c0[i] = off[i] >> cshift;
-        a.cn[i] = ((off[i] + shape[i] - 1) >> cshift) - a.c0[i] + 1;
+        a.c0[i] = r.raw_c0[i]; a.cn[i] = r.raw_cn[i];
     }
-    const int total = a.cn[0] * a.cn[1] * a.cn[2];
-    const dim3 g1((unsigned)((total + 255) / 256)), block(256);
+    const dim3 g1(r.raw_blocks), block(256);
 #define SVR_CELL_RAW(T)                                                                            \
     do {                                                                                           \
         if (cshift == 3) hipLaunchKernelGGL((cell_raw_kernel<T, 8>), g1, block, 0, stream, a);      \
@@ -389,12 +387,8 @@ hipError_t svr_launch_cell_update(const void* ring, int storage, const int32_t r
 #undef SVR_CELL_RAW
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    for (int i = 0; i < 3; ++i) {                  // the blocks that contain a refreshed cell start one cell earlier
-        a.c0[i] -= 1;
-        a.cn[i] = a.cn[i] + 1 > a.cdim[i] ? a.cdim[i] : a.cn[i] + 1;
-    }
-    const int total2 = a.cn[0] * a.cn[1] * a.cn[2];
-    const dim3 g2((unsigned)((total2 + 255) / 256));
+    for (int i = 0; i < 3; ++i) { a.c0[i] = r.blk_c0[i]; a.cn[i] = r.blk_cn[i]; }      // the blocks that contain a refreshed cell
+    const dim3 g2(r.blk_blocks);
     if (storage == SVR_U8)       hipLaunchKernelGGL((cell_block_kernel<uint8_t>), g2, block, 0, stream, a);
     else if (storage == SVR_U16) hipLaunchKernelGGL((cell_block_kernel<uint16_t>), g2, block, 0, stream, a);
     else                         hipLaunchKernelGGL((cell_block_kernel<float>), g2, block, 0, stream, a);

@@ -427,6 +427,16 @@ int svr_lod_twin_ptr(svr_ctx* c, int lod, void** twin) {
     return SVR_OK;
 }
 
+int svr_lod_cell_ptrs(svr_ctx* c, int lod, void** raw, void** blk, int32_t cdim[3], int32_t* cshift) {
+    SVR_REQUIRE(c && raw && blk && cdim && cshift, "svr_lod_cell_ptrs: null argument");
+    SVR_REQUIRE(lod >= 0 && lod < c->num_lods, "svr_lod_cell_ptrs: lod out of range");
+    const LodStorage& L = c->lod[lod];
+    *raw = L.cells_raw; *blk = L.cells_dil;         // both null for a LOD without a grid
+    for (int a = 0; a < 3; ++a) cdim[a] = L.cdim[a];
+    *cshift = L.cshift;
+    return SVR_OK;
+}
+
 int svr_lod_device_ptrs(svr_ctx* c, int lod, void** density, void** labels) {
     SVR_REQUIRE(c, "svr_lod_device_ptrs: null ctx");
     SVR_REQUIRE(lod >= 0 && lod < c->num_lods, "svr_lod_device_ptrs: lod out of range");

@@ -8,9 +8,14 @@
 #include "svr_host.h"
 #include "pack_rows.h"
 
+// How a region is cut into staged blocks (tests/test_gpu_macro_cells.py reads these three to prove which path a shape takes)
+static const size_t kStagingSlotBytes = (size_t)48 << 20;     // per slot; 3 slots -> 144 MiB pinned
+static const size_t kMinBlockBytes = (size_t)4 << 20;         // the smallest staging block
+static const size_t kBlocksPerRegion = 8;                     // a block is about this fraction of the region
+
 static int ensure_staging(svr_ctx* c) {
     if (c->slot_bytes) return SVR_OK;
-    const size_t bytes = (size_t)48 << 20;   // per slot; 3 slots -> 144 MiB pinned
+    const size_t bytes = kStagingSlotBytes;
     for (auto& s : c->slot) {
         if (hipHostMalloc(&s.host, bytes, hipHostMallocDefault) != hipSuccess ||
             hipMalloc(&s.dev, bytes) != hipSuccess ||
@@ -80,7 +85,7 @@ int svr_upload_region(svr_ctx* c, int lod, const int32_t dst_off[3], const int32
     // Blocks of about an eighth of the region (4 MiB .. one slot): the pack of block k+1 runs while block k is on
     // the bus and block k-1 is being scattered, so a region of one or two slots' worth still overlaps the three.
     const size_t region_bytes = row_bytes * (size_t)shape[1] * (size_t)shape[2];
-    size_t block_bytes = std::min(c->slot_bytes - 32, std::max<size_t>((size_t)4 << 20, region_bytes / 8));
+    size_t block_bytes = std::min(c->slot_bytes - 32, std::max<size_t>(kMinBlockBytes, region_bytes / kBlocksPerRegion));
     if (const int mib = svr_exp_env_int("SVR_UPLOAD_BLOCK_MIB", 0)) block_bytes = std::min(c->slot_bytes - 32, std::max<size_t>(1, (size_t)mib) << 20);
     const int64_t rows_max = std::max<int64_t>(1, (int64_t)(block_bytes / row_bytes));
     const int64_t plane_rows = shape[1];

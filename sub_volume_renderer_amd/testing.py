@@ -322,3 +322,64 @@ def read_micro_block_copy(rings, lod: int):
         __cuda_array_interface__ = {"shape": (n * np.dtype(dt).itemsize,), "typestr": "|u1", "data": (twin.value, False), "version": 2}
 
     return torch.as_tensor(_Raw(), device="cuda").cpu().numpy().view(dt).copy()
+
+
+# ---------------------------------------------------------------------------
+# macro-cell maxima of a density ring (empty-space skipping; svr_lod_cell_ptrs in include/svr.h)
+# ---------------------------------------------------------------------------
+def macro_cells_of(ring: np.ndarray, cshift: int):
+    """What the two macro-cell tables of a density ring [z][y][x] must hold, as ``(raw, blk)`` shaped [cz][cy][cx] in
+    the ring's dtype: raw = the largest |value| of each cell of S^3 slots (S = 1 << cshift), an fmax from 0, so a NaN
+    never wins; blk = the maximum of the 2 x 2 x 2 raw cells that start at a cell, on the torus."""
+    s = 1 << cshift
+    rz, ry, rx = ring.shape
+    assert rz % s == 0 and ry % s == 0 and rx % s == 0, (ring.shape, s)
+    a = np.abs(ring) if ring.dtype.kind == "f" else ring
+    cells = a.reshape(rz // s, s, ry // s, s, rx // s, s)
+    raw = np.fmax.reduce(np.fmax.reduce(np.fmax.reduce(cells, axis=5, initial=0), axis=3, initial=0), axis=1, initial=0)
+    raw = raw.astype(ring.dtype)
+    blk = raw.copy()
+    for dz in (0, 1):
+        for dy in (0, 1):
+            for dx in (0, 1):
+                blk = np.fmax(blk, np.roll(raw, (-dz, -dy, -dx), axis=(0, 1, 2)))
+    return raw, blk
+
+
+def macro_cell_bytes(rings, lod: int):
+    """The two live macro-cell tables of LOD `lod` as flat torch byte tensors ``(raw, blk)`` that alias the device memory
+    (no copy: writing to them changes what the kernels read), with their shape (cz, cy, cx), numpy element type and
+    cshift; or None for a LOD without a grid."""
+    import ctypes as C
+
+    import torch
+
+    from . import _native as N
+
+    raw, blk, cdim, cshift = C.c_void_p(), C.c_void_p(), N._I3(), C.c_int32()
+    N.check(N.lib().svr_lod_cell_ptrs(rings.handle, lod, C.byref(raw), C.byref(blk), cdim, C.byref(cshift)), "svr_lod_cell_ptrs")
+    assert bool(raw.value) == bool(blk.value)
+    if not raw.value:
+        return None
+    N.check(N.lib().svr_sync(rings.handle), "svr_sync")
+    dt = np.dtype({"uint8": np.uint8, "uint16": np.uint16}.get(rings.density_storage, np.float32))
+    shape = (int(cdim[2]), int(cdim[1]), int(cdim[0]))
+    nbytes = int(np.prod(shape)) * dt.itemsize
+
+    def wrap(ptr):
+        class _Raw:
+            __cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+
+        return torch.as_tensor(_Raw(), device="cuda")
+
+    return wrap(raw.value), wrap(blk.value), shape, dt, int(cshift.value)
+
+
+def read_macro_cells(rings, lod: int):
+    """Host copies ``(raw, blk)`` of the macro-cell tables of LOD `lod` as they lie in HBM once both streams are idle,
+    shaped [cz][cy][cx] in the ring's element type; or None for a LOD without a grid."""
+    t = macro_cell_bytes(rings, lod)
+    if t is None:
+        return None
+    raw, blk, shape, dt, _ = t
+    return tuple(x.cpu().numpy().view(dt).reshape(shape).copy() for x in (raw, blk))
