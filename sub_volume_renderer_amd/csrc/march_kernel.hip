@@ -793,13 +793,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
 #else
     constexpr int dbg_nowait = 0, brick_pow2 = 0;                         // the shipped kernel carries neither
 #endif
-    bool found = false, finished = (dbg_nowait & 2) != 0;      // instruction-count experiments: prologue + epilogue only
+    // Which lanes have found their first hit / have left the loop: wave-uniform lane masks, combined with scalar & and |
+    // ("Batch control").  A ballot's operand is always a bare compare; as per-lane bools that are merged
+    // across branches the compiler re-made the masks from 0 / 1 registers before every ballot.  Only assigned under
+    // wave-uniform control flow.
+    typedef unsigned long long mask_t;
+    mask_t found_m = 0ull, fin_m = (dbg_nowait & 2) != 0 ? ~0ull : 0ull;   // instruction-count experiments: prologue + epilogue only
+    // the lanes that still have a sample at iteration i (wave-uniform i) and have not left the loop
+    auto live_at = [&](int i) -> mask_t { return __builtin_amdgcn_ballot_w64(i < nsteps) & ~fin_m; };
+    // the first pair of iterations of a batch runs on from the batch before (exact, see the brick loop) where the kernel
+    // has the two registers for it: byte and u16 rings' LMIP kernels; the others rebuild it from n
+    constexpr bool kCarryIter = !WAVG && ESH != 2;
+    constexpr bool kLaneBools = WAVG || ESH == 2;
+    constexpr bool kScalarCount = !kLaneBools;
+    // the live lanes of batch k8 / U of a loop that started at iteration n0: the loop's scalar counter against what was left
+    // of each ray there (rem = nsteps - n0), so that the counter never moves to the vector side (kScalarCount; the others
+    // compare the iteration itself, as they did)
+    auto live_in = [&](int nb, int rem, int k8) -> mask_t {
+        return (kScalarCount ? __builtin_amdgcn_ballot_w64(k8 < rem) : __builtin_amdgcn_ballot_w64(nb < nsteps)) & ~fin_m;
+    };
     float local_max = 0.f, samp = 0.f;
     int hit_i = 0, since = 0;
     uint32_t steps = 0;
 
     // LMIP state machine over one batch of U samples starting at iteration nb (raycast.wgsl:35-61).
-    // `live`: this lane executes the batch; `tail`: some of its samples may lie beyond nsteps.
     // Skipped entirely while no lane can change state (nothing found yet, nothing >= threshold).
     typedef typename Texel<ESH>::type texel_t;
     // "(f32)m >= threshold" on the raw texel: integer texels compare as integers against ceil(threshold)
@@ -811,63 +828,133 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
     // contribution so far, samp the weighted sum, den the sum of weights; the lane is finished at its first weightless sample
     // (its own instantiations, WAVG: the LMIP kernels do not carry a single instruction of it)
     float den = 0.f;
-    auto lmip_batch = [&](const texel_t (&sv)[U], int nb, bool live, bool tail) {
-        if constexpr (WAVG) {
-            const float steplen = sqrtf((Rtx * Rtx + Rty * Rty) + Rtz * Rtz);
-            const float k = fresh_params(P)->weight_falloff;
+    // `live_m`: the lanes that execute the batch (live_at(nb)).  Whether some of them end inside the batch (a tail: their
+    // samples beyond nsteps are masked) is looked at only where the batch has something to do.
+    auto lmip_batch = [&](const texel_t (&sv)[U], int nb, mask_t live_m) {
+        if constexpr (kLaneBools) {
+            auto body = [&](auto tail_c) {
+                constexpr bool tail = decltype(tail_c)::value;
+                const bool live = __builtin_amdgcn_inverse_ballot_w64(live_m);
+                bool found = __builtin_amdgcn_inverse_ballot_w64(found_m), finished = __builtin_amdgcn_inverse_ballot_w64(fin_m);
+                if constexpr (WAVG) {
+                    const float steplen = sqrtf((Rtx * Rtx + Rty * Rty) + Rtz * Rtz);
+                    const float k = fresh_params(P)->weight_falloff;
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const bool act = live && !finished && (!tail || (nb + u) < nsteps);
-                const float tw = 1.0f - k * ((float)(nb + u) * steplen);
-                const bool go = act && tw > 0.0f;
-                finished = finished || (act && !go);
-                if (COUNT) steps += go ? 1u : 0u;
-                const float val = texel_value(sv[u]);
-                const float w = tw * tw;
-                const float contribution = w * fabsf(val);
-                const float num1 = samp + w * val, den1 = den + w;
-                samp = go ? num1 : samp;
-                den = go ? den1 : den;
-                const bool take = go && contribution > local_max;
-                local_max = take ? contribution : local_max;
-                hit_i = take ? (nb + u) : hit_i;
-            }
+                    for (int u = 0; u < U; ++u) {
+                        const bool act = live && !finished && (!tail || (nb + u) < nsteps);
+                        const float tw = 1.0f - k * ((float)(nb + u) * steplen);
+                        const bool go = act && tw > 0.0f;
+                        finished = finished || (act && !go);
+                        if (COUNT) steps += go ? 1u : 0u;
+                        const float val = texel_value(sv[u]);
+                        const float w = tw * tw;
+                        const float contribution = w * fabsf(val);
+                        const float num1 = samp + w * val, den1 = den + w;
+                        samp = go ? num1 : samp;
+                        den = go ? den1 : den;
+                        const bool take = go && contribution > local_max;
+                        local_max = take ? contribution : local_max;
+                        hit_i = take ? (nb + u) : hit_i;
+                    }
+                    fin_m = __builtin_amdgcn_ballot_w64(finished);
+                    return;
+                }
+                texel_t m;
+                if constexpr (ESH != 2) m = 0u; else m = -1.0f;
+                const texel_t neutral = m;
+#pragma unroll
+                for (int u = 0; u < U; ++u) m = texel_max(m, (tail && (nb + u) >= nsteps) ? neutral : texel_abs(sv[u]));
+                bool need;
+                if (mip_like) need = live && (found ? texel_value(m) > local_max : m >= thr_raw);
+                else need = live && (found || m >= thr_raw);
+                if (__builtin_amdgcn_ballot_w64(need) != 0) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const bool act = live && !finished && (!tail || (nb + u) < nsteps);
+                        const float val = texel_value(sv[u]);
+                        const float inten = fabsf(val);
+                        if (COUNT) steps += act ? 1u : 0u;
+                        const bool was_found = found;
+                        const bool first_hit = act && !was_found && inten >= P.lmip_threshold;     // :37
+                        const bool tracking = act && was_found;
+                        since += tracking ? 1 : 0;                                                 // :47
+                        const bool take = first_hit || (tracking && inten > local_max);            // :50
+                        local_max = take ? inten : local_max;
+                        samp = take ? val : samp;
+                        hit_i = take ? (nb + u) : hit_i;
+                        found = found || first_hit;
+                        const bool brk = tracking && (since >= P.lmip_max_samples || inten < local_max * P.lmip_fall_off);  // :58
+                        finished = finished || brk;
+                    }
+                    found_m = __builtin_amdgcn_ballot_w64(found);
+                    fin_m = __builtin_amdgcn_ballot_w64(finished);
+                } else if (COUNT) {
+                    steps += live ? (uint32_t)(tail ? (min(nb + U, nsteps) - nb) : U) : 0u;
+                }
+            };
+            if ((live_m & __builtin_amdgcn_ballot_w64(nb + U > nsteps)) != 0) body(std::true_type{});
+            else body(std::false_type{});
             return;
         }
-        // u8: 0 is neutral (a live lane always has one real sample); f32: -1 < every |s|
+        // The largest value of the batch, samples beyond a ray's end included (they are fetched from harmless addresses):
+        // it is at least the largest of the real ones, so a batch this test lets pass has nothing to do either way.
+        // u8: 0 is neutral; f32: -1 < every |s|
         texel_t m;
         if constexpr (ESH != 2) m = 0u; else m = -1.0f;
         const texel_t neutral = m;
 #pragma unroll
-        for (int u = 0; u < U; ++u) m = texel_max(m, (tail && (nb + u) >= nsteps) ? neutral : texel_abs(sv[u]));
-        // a lane that follows a maximum needs the batch too — unless the machine can never stop (MIP: no fall-off, no
-        // sample limit; host: skip_flags bit 1) and nothing in the batch beats its maximum (raycast.wgsl:50 is a strict >)
-        // (the same decision written branch-free, both conditions evaluated first, measured 1.5 % slower: the compiler
-        // then keeps the lane masks as 0 / 1 in VGPRs)
-        bool need;
-        if (mip_like) need = live && (found ? texel_value(m) > local_max : m >= thr_raw);
-        else need = live && (found || m >= thr_raw);
-        if (__builtin_amdgcn_ballot_w64(need) != 0) {
+        for (int u = 0; u < U; ++u) m = texel_max(m, texel_abs(sv[u]));
+        // one compare, one branch: a lane that has found something, or whose batch reaches the threshold
+        if (((__builtin_amdgcn_ballot_w64(m >= thr_raw) | found_m) & live_m) != 0) {
+            // the LMIP state machine, lane masks in scalar registers (raycast.wgsl:35-61)
+            auto machine = [&](auto tail_c) {
+                constexpr bool tail = decltype(tail_c)::value;
+                // (the lanes that still have sample u: one compare each, its mask serves the maximum and the machine)
+                mask_t in_m[U];
+                if (tail) {
+                    m = neutral;
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const bool act = live && !finished && (!tail || (nb + u) < nsteps);
-                const float val = texel_value(sv[u]);
-                const float inten = fabsf(val);
-                if (COUNT) steps += act ? 1u : 0u;
-                const bool was_found = found;
-                const bool first_hit = act && !was_found && inten >= P.lmip_threshold;     // :37
-                const bool tracking = act && was_found;
-                since += tracking ? 1 : 0;                                                 // :47
-                const bool take = first_hit || (tracking && inten > local_max);            // :50
-                local_max = take ? inten : local_max;
-                samp = take ? val : samp;
-                hit_i = take ? (nb + u) : hit_i;
-                found = found || first_hit;
-                const bool brk = tracking && (since >= P.lmip_max_samples || inten < local_max * P.lmip_fall_off);  // :58
-                finished = finished || brk;
-            }
+                    for (int u = 0; u < U; ++u) {
+                        in_m[u] = __builtin_amdgcn_ballot_w64((nb + u) < nsteps);
+                        m = texel_max(m, __builtin_amdgcn_inverse_ballot_w64(in_m[u]) ? texel_abs(sv[u]) : neutral);
+                    }
+                }
+                // a lane that follows a maximum needs the batch too — unless the machine can never stop (MIP: no fall-off,
+                // no sample limit; host: skip_flags bit 1) and nothing in the batch beats its maximum (raycast.wgsl:50 is
+                // a strict >)
+                mask_t need_m = found_m;
+                if (tail || mip_like) {
+                    if (mip_like) need_m &= __builtin_amdgcn_ballot_w64(texel_value(m) > local_max);
+                    need_m |= __builtin_amdgcn_ballot_w64(m >= thr_raw) & ~found_m;
+                    if ((need_m & live_m) == 0) return false;
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    mask_t act_m = live_m & ~fin_m;
+                    if (tail) act_m &= in_m[u];
+                    const float val = texel_value(sv[u]);
+                    const float inten = fabsf(val);
+                    if (COUNT) steps += __builtin_amdgcn_inverse_ballot_w64(act_m) ? 1u : 0u;
+                    const mask_t first_m = act_m & ~found_m & __builtin_amdgcn_ballot_w64(inten >= P.lmip_threshold);   // :37
+                    const mask_t track_m = act_m & found_m;
+                    since += __builtin_amdgcn_inverse_ballot_w64(track_m) ? 1 : 0;             // :47
+                    const bool take = __builtin_amdgcn_inverse_ballot_w64(
+                        first_m | (track_m & __builtin_amdgcn_ballot_w64(inten > local_max)));  // :50
+                    local_max = take ? inten : local_max;
+                    samp = take ? val : samp;
+                    hit_i = take ? (nb + u) : hit_i;
+                    found_m |= first_m;
+                    fin_m |= track_m & (__builtin_amdgcn_ballot_w64(since >= P.lmip_max_samples) |
+                                        __builtin_amdgcn_ballot_w64(inten < local_max * P.lmip_fall_off));   // :58
+                }
+                return true;
+            };
+            bool ran;
+            if ((live_m & __builtin_amdgcn_ballot_w64(nb + U > nsteps)) != 0) ran = machine(std::true_type{});
+            else ran = machine(std::false_type{});
+            if (COUNT && !ran) steps += __builtin_amdgcn_inverse_ballot_w64(live_m) ? (uint32_t)(min(nb + U, nsteps) - nb) : 0u;
         } else if (COUNT) {
-            steps += live ? (uint32_t)(tail ? (min(nb + U, nsteps) - nb) : U) : 0u;
+            steps += __builtin_amdgcn_inverse_ballot_w64(live_m) ? (uint32_t)(min(nb + U, nsteps) - nb) : 0u;
         }
     };
 
@@ -910,14 +997,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
     int n = 0;                                       // wave-uniform: every ray starts at iteration 0
     lap(0);
     while (true) {
-        const bool alive = !finished && n < nsteps;
-        const unsigned long long alive_mask = __builtin_amdgcn_ballot_w64(alive);
+        const mask_t alive_mask = live_at(n);
         if (alive_mask == 0) break;
+        const bool alive = __builtin_amdgcn_inverse_ballot_w64(alive_mask);
 
         // ---- span refresh for the lanes whose span has ended
-        if (__builtin_amdgcn_ballot_w64(alive && n >= E) != 0) {
+        const mask_t refresh_m = alive_mask & __builtin_amdgcn_ballot_w64(n >= E);
+        if (refresh_m != 0) {
             const kparams_t Pr = fresh_params(P);
-            if (alive && n >= E) {
+            if (__builtin_amdgcn_inverse_ballot_w64(refresh_m)) {
                 code = NL; E = nsteps; Kc = 0xFFFFFFFFu;
                 bool settled = false;
 #pragma unroll
@@ -1024,7 +1112,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
                     s[u] = acc;
                 }
             }
-            lmip_batch(s, n, alive, true);
+            lmip_batch(s, n, alive_mask);
             n += U;
             lap(2);
             continue;
@@ -1035,13 +1123,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
             texel_t s[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) s[u] = 0;
-            for (; run > 0; --run) {
+            // (the test for a live lane stands before the batch: it is the batch's own live mask)
+            for (mask_t lv_m = alive_mask; run > 0 && lv_m != 0; --run, lv_m = live_at(n)) {
                 if (COUNT) ++c_zero;
-                const bool lv = alive && !finished && n < nsteps;
-                if (__builtin_amdgcn_ballot_w64(lv && n + U > nsteps) != 0) lmip_batch(s, n, lv, true);
-                else lmip_batch(s, n, lv, false);
+                lmip_batch(s, n, lv_m);
                 n += U;
-                if (__builtin_amdgcn_ballot_w64(alive && !finished && n < nsteps) == 0) break;
             }
             continue;
         }
@@ -1084,8 +1170,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
                     const float reach = (float)(8 * sb);
                     const uint32_t cs = (uint32_t)Ps->lod[first].cshift;
                     const float vx = SCALED ? Rtx : Rtx * ssx, vy = SCALED ? Rty : Rty * ssy, vz = SCALED ? Rtz : Rtz * ssz;
-                    const bool slow = fmaxf(fmaxf(fabsf(vx), fabsf(vy)), fabsf(vz)) * reach <=
-                                      (float)(1u << cs) - 0.5f;
+                    const mask_t slow_m = __builtin_amdgcn_ballot_w64(fmaxf(fmaxf(fabsf(vx), fabsf(vy)), fabsf(vz)) * reach <=
+                                                                      (float)(1u << cs) - 0.5f);
                     __amdgpu_buffer_rsrc_t crsrc = __builtin_amdgcn_make_buffer_rsrc(
                         const_cast<void*>(Ps->cells_all), 0, (int)Ps->cells_all_bytes, 0x00020000);
                     const uint32_t cbase = Ps->lod[first].cell_base;
@@ -1101,7 +1187,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
                         c0z = ((uint32_t)(int)coord_one<SCALED>(i0, Rsz, Rtz, ssz) + (uint32_t)L.addw[2]) >> cs;
                     }
                     while (run >= 4 * sb) {
-                        const bool live = alive && !finished && n < nsteps;
+                        const mask_t live_m = live_at(n);
                         // unwrapped cell coordinates ((index + addw) >> cs, in [0, 2 * cells)) of the samples at the 5
                         // stretch borders: iterations n, n + 8B, n + 16B, n + 24B and n + 32B — the first border of the
                         // next test, which inherits it — or, when this run ends with the group, its LAST iteration,
@@ -1132,18 +1218,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
                         // a lane that tracks a maximum, moves too fast for the test, or passes a block that may hold a
                         // significant value vetoes the skip
                         // (MIP: a lane that follows a maximum only vetoes for a block that may beat it)
-                        const bool occupied = live && !found && (!slow || m >= thr_raw);
-                        const bool following = live && found && (!mip_like || !slow || texel_value(m) > local_max);
-                        const unsigned long long occ_mask = __builtin_amdgcn_ballot_w64(occupied);
-                        if (occ_mask != 0 || __builtin_amdgcn_ballot_w64(following) != 0) {
+                        const mask_t occ_mask = live_m & ~found_m & (~slow_m | __builtin_amdgcn_ballot_w64(m >= thr_raw));
+                        mask_t fol_mask = live_m & found_m;
+                        if (mip_like && fol_mask != 0) fol_mask &= ~slow_m | __builtin_amdgcn_ballot_w64(texel_value(m) > local_max);
+                        if ((occ_mask | fol_mask) != 0) {
                             vetoed = true;
                             tracking_only = occ_mask == 0;         // every vetoing lane is already following a maximum
                             break;
                         }
-                        if (COUNT) { steps += live ? (uint32_t)(min(n + 32 * sb, nsteps) - n) : 0u; c_skip += 4 * sb; }
+                        if (COUNT) { steps += __builtin_amdgcn_inverse_ballot_w64(live_m) ? (uint32_t)(min(n + 32 * sb, nsteps) - n) : 0u; c_skip += 4 * sb; }
                         n += 32 * sb;
                         run -= 4 * sb;
-                        if (__builtin_amdgcn_ballot_w64(alive && !finished && n < nsteps) == 0) { run = 0; break; }
+                        if (live_at(n) == 0) { run = 0; break; }
                     }
                     if (vetoed) {
                         // march one test's worth (a whole brick slab where bricks are staged), then test again
@@ -1168,7 +1254,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
                 // length; at its first box that does not fit the LDS region it drops to the plain length)
                 while (brick_mode && L.slab > 0 && !use_twin && run >= (L.slab << (brick_mode - 1)) / U) {
                     const int slab = L.slab << (brick_mode - 1);
-                    const bool live = alive && !finished && n < nsteps;
+                    const bool live = __builtin_amdgcn_inverse_ballot_w64(live_at(n));
                     // first and last existing sample of the slab, both at once with the packed chain
                     const float2_t it = { (float)n, (float)min(n + slab - 1, nsteps - 1) };
                     const float2_t ex = coord_pair<SCALED>(it, Rsx, Rtx, ssx);
@@ -1261,10 +1347,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
                     lap(4);
                     // one dot2 on the packed (y, z): y * rowpitch + z * planepitch + (x + bk)
                     const uint32_t kyz = (uint32_t)(gp << 4) | ((uint32_t)(pz << 4) << 16);
-                    const bool slab_tail = __builtin_amdgcn_ballot_w64(live && n + slab > nsteps) != 0;   // some ray ends inside this slab
-                    for (int k = 0; k < slab / U; ++k) {
+                    // (iter runs on from batch to batch: the chain's own four adds leave it at the next batch's first pair,
+                    //  exact below 2^24 like the converts they replace)
+                    float2_t iter = { (float)n, (float)n + 1.0f };
+                    // the batch counter k8 is the loop's only scalar state; the lanes compare it with what is left of their ray
+                    const int n0 = n, rem = kScalarCount ? nsteps - n0 : 0;
+                    for (int k8 = 0; k8 < slab; k8 += U) {
                         texel_t s[U];
-                        float2_t iter = { (float)n, (float)n + 1.0f };
+                        const int nb = kScalarCount ? n0 + k8 : n;
+                        if constexpr (!kCarryIter) iter = float2_t{ (float)nb, (float)nb + 1.0f };
 #pragma unroll
                         for (int u = 0; u < U; u += 2) {
                             const Idx2p v = voxel_pair_packed<SCALED>(Rsx, Rsy, Rsz, Rtx, Rty, Rtz, iter, ssx, ssy, ssz);
@@ -1279,16 +1370,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
                         // (one statement for the whole batch: one wait for the 8 reads instead of 8)
                         if constexpr (ESH != 2 && U == 8)
                             asm("" : "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3]), "+v"(s[4]), "+v"(s[5]), "+v"(s[6]), "+v"(s[7]));
-                        {
-                            const bool lv = alive && !finished && n < nsteps;
-                            // keep the no-tail case a compile-time constant (its per-sample tests fold away); a ray can only
-                            // end inside this slab if slab_tail says so (one test per slab instead of one per batch)
-                            if (slab_tail && __builtin_amdgcn_ballot_w64(lv && n + U > nsteps) != 0) lmip_batch(s, n, lv, true);
-                            else lmip_batch(s, n, lv, false);
-                        }
-                        n += U;
+                        lmip_batch(s, nb, live_in(nb, rem, k8));
+                        if constexpr (!kScalarCount) n += U;
                         if (COUNT) ++c_brick;
                     }
+                    if constexpr (kScalarCount) n = n0 + slab;
                     run -= slab / U;
                     lap(5);
                     asm volatile("" ::: "memory");      // the next slab's loads must not overtake these LDS reads
@@ -1304,13 +1390,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
             auto direct_batches = [&](auto from_twin) {
             constexpr int TWF = decltype(from_twin)::value;
             constexpr bool TW = TWF != 0;
-            for (; run > 0; --run) {
-                const bool live = alive && !finished && n < nsteps;
-                if (__builtin_amdgcn_ballot_w64(live) == 0) break;
+            float2_t iter = { (float)n, (float)n + 1.0f };        // (runs on from batch to batch, as in the brick loop)
+            const int n0 = n, rem = kScalarCount ? nsteps - n0 : 0;
+            int k8 = 0;                                           // (scalar, as in the brick loop)
+            for (; run > 0; --run, k8 += U) {
+                const int nb = kScalarCount ? n0 + k8 : n;
+                const mask_t live_m = live_in(nb, rem, k8);
+                if (live_m == 0) break;
+                const bool live = __builtin_amdgcn_inverse_ballot_w64(live_m);
                 if (COUNT) { ++c_direct; if (TW) t_acc[15] += 1ull; }          // ([15]: a count, not cycles — svr_debug_timers)
                 texel_t s[U];
                 uint32_t off[U];
-                float2_t iter = { (float)n, (float)n + 1.0f };
+                if constexpr (!kCarryIter) iter = float2_t{ (float)nb, (float)nb + 1.0f };
                 if constexpr (TWF == 2) {
 #pragma unroll
                     for (int u = 0; u < U; u += 2) {
@@ -1351,17 +1442,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
                         for (uint32_t k = 1; k < L.nparts; ++k) q += icz >= zth + (int)((k - 1u) * L.zsplit) ? 1u : 0u;
                         return q;
                     };
-                    const float2_t ends = { (float)n, (float)min(n + U - 1, nsteps - 1) };     // (samples beyond the ray's end are never looked at)
+                    const float2_t ends = { (float)nb, (float)min(nb + U - 1, nsteps - 1) };     // (samples beyond the ray's end are never looked at)
                     const float2_t ez2 = coord_pair<SCALED>(ends, Rsz, Rtz, ssz);
                     const uint32_t pa = part_of((int)ez2.x), pb = part_of((int)ez2.y);
-                    const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)pa, (int)__builtin_ctzll(__builtin_amdgcn_ballot_w64(live)));
+                    const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)pa, (int)__builtin_ctzll(live_m));
                     if (__builtin_amdgcn_ballot_w64(live && (pa != p0 || pb != p0)) == 0) {
                         const __amdgpu_buffer_rsrc_t rp = part_rsrc(L, p0, TW ? twin_base : L.rbase);
                         const uint32_t sub = p0 * L.part_bytes;
 #pragma unroll
                         for (int u = 0; u < U; ++u) s[u] = fetch_density<ESH>(rp, live ? off[u] - sub : 0xFFFFFFFFu);
                     } else {
-                    float2_t it2 = { (float)n, (float)n + 1.0f };
+                    float2_t it2 = { (float)nb, (float)nb + 1.0f };
 #pragma unroll
                     for (int u = 0; u < U; u += 2) {
                         const float2_t cz = coord_pair<SCALED>(it2, Rsz, Rtz, ssz);      // the z index of the pair again (this path is rare)
@@ -1373,7 +1464,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
                             for (uint32_t k = 1; k < L.nparts; ++k) part += icz >= zth + (int)((k - 1u) * L.zsplit) ? 1u : 0u;
                             const uint32_t rel = off[u + h] - part * L.part_bytes;
                             texel_t a = 0;
-                            for (unsigned long long todo = __builtin_amdgcn_ballot_w64(live); todo != 0ull;) {
+                            for (unsigned long long todo = live_m; todo != 0ull;) {
                                 const uint32_t p = (uint32_t)__builtin_amdgcn_readlane((int)part, (int)__builtin_ctzll(todo));
                                 const bool mine = live && part == p;
                                 const texel_t t = fetch_density<ESH>(part_rsrc(L, p, TW ? twin_base : L.rbase), mine ? rel : 0xFFFFFFFFu);
@@ -1389,10 +1480,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
 #pragma unroll
                     for (int u = 0; u < U; ++u) s[u] = fetch_density<ESH>(TW ? rsrc_twin : rsrc, off[u]);
                 }
-                if (__builtin_amdgcn_ballot_w64(live && n + U > nsteps) != 0) lmip_batch(s, n, live, true);
-                else lmip_batch(s, n, live, false);
-                n += U;
+                lmip_batch(s, nb, live_m);
+                if constexpr (!kScalarCount) n += U;
             }
+            if constexpr (kScalarCount) n = n0 + k8;
             };
             if (use_twin || (many_lines && L.twin == 2u && (brick_mode == 0 || L.slab <= 0))) {
                 const kparams_t Pt = fresh_params(P);
@@ -1406,7 +1497,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
             } else {
                 direct_batches(std::integral_constant<int, 0>{});
             }
-            } while (held > 0 && __builtin_amdgcn_ballot_w64(alive && !finished && n < nsteps) != 0);
+            } while (held > 0 && live_at(n) != 0);
             if constexpr (SCALED) {
                 // back to the ray of the reference (1 / ss = 2^-m, read from the host: the product is the original value)
                 const kparams_t Pu = fresh_params(P);
@@ -1424,7 +1515,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCALED && !
         atomicAdd(P.dbg + 6, 1u);                  atomicAdd(P.dbg + 7, (uint32_t)c_skip);
     }
     Hit h;
-    h.found = found; h.sample = samp; h.steps = steps;
+    h.found = __builtin_amdgcn_inverse_ballot_w64(found_m); h.sample = samp; h.steps = steps;
     if constexpr (WAVG) { h.found = local_max > 0.0f; h.sample = h.found ? samp / den : 0.0f; }
     const float hit_f = (float)hit_i;
     h.offset = { hit_f * Rtx, hit_f * Rty, hit_f * Rtz };                    // raycast.wgsl:30
