@@ -773,6 +773,81 @@ typedef struct svr_objects_outputs {    /* DEVICE pointers, both required */
 } svr_objects_outputs;
 int  svr_objects(svr_ctx* ctx, const svr_objects_params* params, const svr_objects_outputs* out, void* stream);
 
+/* ---- surface meshes of the resident rings: a picked object, or a level set, as vertices and triangles.  (No
+ * counterpart in the reference; what an exporter, a surface-area or volume measurement, or a mesh renderer beside the
+ * volume needs.)  An addition within ABI version 9: one new symbol and two new structs, nothing older changes.  The
+ * mesh is extracted in HBM; nothing is copied to the host.
+ * Defined HERE (numpy restatement: tests/mesh_twin.py).  The method is naive surface nets: one vertex per mixed cell,
+ * one quad per crossing lattice edge; there is no case table.
+ *   coordinates LOD-`lod` logical voxels in shader order (x, y, z); integer c is the CENTRE of voxel c (the convention
+ *               of the Python side's lod_center_to_data).
+ *   box B       [lo, lo + n): the intersection of box and window exactly as in svr_histogram (use_box, box_off,
+ *               box_shape).  A window of None and a box that misses the window give an empty mesh.
+ *   inside(p)   p is in B, and
+ *                 SVR_MESH_LABELS  the label texel of p is one of selected[0 .. selected_count) (sorted ascending,
+ *                                  selected_count >= 1); without label rings every label reads as 0;
+ *                 SVR_MESH_LEVEL   v >= level, v being the density element converted to f32 exactly as svr_histogram
+ *                                  converts it.  A NaN is outside.  `level` is in the ring's own units, like iso_value.
+ *               Every voxel outside B is outside, so surfaces are closed, with flat caps half a voxel beyond B's faces.
+ *               The texel is ring slot (x % ring_x, y % ring_y, z % ring_z) of the row-major ring (the micro-block
+ *               copy is never read).
+ *   cells       cell c has the 8 corners c + d, d in {0, 1}^3; c ranges over [lo - 1, lo + n - 1] on every axis:
+ *               (n_x + 1)(n_y + 1)(n_z + 1) cells.  A cell is ACTIVE when its corners are neither all inside nor all
+ *               outside.  An edge CROSSES when inside() differs at its two ends.
+ *   vertex      of an active cell c: (float)(c - window offset) + q per axis (one f32 add), where q is the f32 sum,
+ *               added one by one in a fixed order, of the crossing points of the cell's crossing edges, divided by
+ *               (float)k, k being their number.  The order: the 4 x-edges, the 4 y-edges, the 4 z-edges; within an
+ *               axis by the corner offsets on the two other axes, the higher of those axes being the major key
+ *               (x-edges: (dy, dz) = (0,0), (1,0), (0,1), (1,1)).  A crossing point has t on the edge's own axis and
+ *               the edge's corner offsets (0 or 1) on the others.  t = 0.5, except in SVR_MESH_LEVEL when both ends
+ *               lie in B and both values are finite: then, with v0 the value at the lower end, r = (level - v0) /
+ *               (v1 - v0) in f32, t = r clamped to [0, 1], and t = 0.5 when r is not finite.  No fused operations.
+ *   vertices    in ascending order of the cell (z, then y, then x).
+ *   quads       edge (p, a) runs from voxel p to p + e_a, p in the cell range, a in {x, y, z}.  When it crosses, with
+ *               (b, c) the axes that follow a cyclically (x: (y, z), y: (z, x), z: (x, y)), the four cells around it
+ *               are k0 = p - e_b - e_c, k1 = p - e_c, k2 = p, k3 = p - e_b; all four are active and in the cell range
+ *               (an end outside B is outside, so no edge crosses on the low border of the range).  The quad is
+ *               (k0, k1, k2, k3) when inside(p), whose normal +a points out of the object, else (k0, k3, k2, k1); it
+ *               gives the triangles (q0, q1, q2) and (q0, q2, q3), vertex indices as int32.
+ *               Quads in ascending order of p (z, then y, then x), then axis x, y, z; a quad's two triangles adjacent.
+ *   header      8 x uint64_t:
+ *                 [0] vertices V        [1] triangles T
+ *                 [2] vertices written  [3] triangles written
+ *                 [4..6] the window offset (x, y, z) of the LOD the call used, as int64 bit patterns
+ *                 [7] the number of inside voxels
+ *               If V > vertex_capacity or T > triangle_capacity NEITHER array is written and [2] = [3] = 0; else
+ *               [2] = V, [3] = T.  Capacities of 0 with NULL arrays are the count-only call.  The header is overwritten
+ *               by every call.
+ * The output is fully specified, order included: two calls on the same rings give identical bytes.  Ordered like
+ * svr_objects: it waits for published uploads, and later uploads are ordered behind it.  Enqueued on `stream`;
+ * asynchronous.  The call works in scratch memory owned by the context (about 1 byte per cell, grown on demand,
+ * SVR_ERR_NOMEM when it cannot be, released by svr_destroy); a call is ordered behind the previous svr_mesh of the same
+ * context, whatever its stream.  The material, the variant, the interpolation and the cut planes are not read.
+ * SVR_ERR_INVALID, with nothing enqueued and the outputs untouched, for: a NULL ctx, params, outputs or header; lod out of
+ * range; an unknown mode; SVR_MESH_LABELS with selected_count == 0 or selected == NULL; a NaN level (SVR_MESH_LEVEL); a
+ * negative box_shape component (with use_box != 0); more than SVR_MESH_MAX_CELLS cells; a NULL array with a non-zero
+ * capacity. */
+#define SVR_MESH_LABELS 0
+#define SVR_MESH_LEVEL  1
+#define SVR_MESH_MAX_CELLS (1u << 28)
+typedef struct svr_mesh_params {
+    int32_t lod;
+    int32_t use_box;                    /* 0: the LOD's whole resident window */
+    int32_t box_off[3], box_shape[3];   /* LOD-l logical voxels, shader order: svr_histogram_params' */
+    int32_t mode;                       /* SVR_MESH_LABELS or SVR_MESH_LEVEL */
+    float   level;                      /* SVR_MESH_LEVEL: inside is v >= level; not NaN */
+    const uint32_t* selected;           /* SVR_MESH_LABELS: DEVICE, sorted ascending */
+    uint32_t selected_count;            /* SVR_MESH_LABELS: >= 1 */
+} svr_mesh_params;
+typedef struct svr_mesh_outputs {       /* DEVICE pointers; header required */
+    float*    vertices;                 /* 3 * vertex_capacity: x, y, z relative to header[4..6] */
+    int32_t*  triangles;                /* 3 * triangle_capacity */
+    uint64_t* header;                   /* 8 */
+    uint64_t  vertex_capacity;          /* 0: vertices may be NULL */
+    uint64_t  triangle_capacity;        /* 0: triangles may be NULL */
+} svr_mesh_outputs;
+int  svr_mesh(svr_ctx* ctx, const svr_mesh_params* params, const svr_mesh_outputs* out, void* stream);
+
 /* ---- sync */
 int  svr_sync(svr_ctx* ctx);                 /* both streams idle */
 int  svr_sync_uploads(svr_ctx* ctx);         /* upload stream idle */

@@ -15,6 +15,7 @@ from ._transfer import TransferFunction
 from ._transform import AffineTransform, OrthographicCamera, PerspectiveCamera
 from ._wobject import FrameRegion, HistogramResult, IsoResult, ObjectTable, RenderResult, SliceResult, SubVolume
 from ._wrapping_buffer import WrappingBuffer, subtract_rois
+from .mesh import SurfaceMesh
 
 __all__ = [
     "SubVolume",
@@ -33,6 +34,7 @@ __all__ = [
     "IsoResult",
     "HistogramResult",
     "ObjectTable",
+    "SurfaceMesh",
     "subtract_rois",
     # display-side output of a render (pygfx's job in the reference)
     "compose",

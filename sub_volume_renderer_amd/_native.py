@@ -229,6 +229,32 @@ class ObjectsOutputs(C.Structure):
 OBJECTS_MAX_CAPACITY = 1 << 26                      # SVR_OBJECTS_MAX_CAPACITY
 OBJECT_RECORD_BYTES = 96                            # sizeof(svr_object_record)
 
+class MeshParams(C.Structure):
+    _fields_ = [
+        ("lod", C.c_int32),
+        ("use_box", C.c_int32),
+        ("box_off", C.c_int32 * 3),
+        ("box_shape", C.c_int32 * 3),
+        ("mode", C.c_int32),
+        ("level", C.c_float),
+        ("selected", C.c_void_p),
+        ("selected_count", C.c_uint32),
+    ]
+
+
+class MeshOutputs(C.Structure):
+    _fields_ = [
+        ("vertices", C.c_void_p),
+        ("triangles", C.c_void_p),
+        ("header", C.c_void_p),
+        ("vertex_capacity", C.c_uint64),
+        ("triangle_capacity", C.c_uint64),
+    ]
+
+
+MESH_LABELS, MESH_LEVEL = 0, 1                      # SVR_MESH_*
+MESH_MAX_CELLS = 1 << 28                            # SVR_MESH_MAX_CELLS
+
 INTERPOLATIONS = {"nearest": 0, "linear": 1}      # SVR_INTERP_*
 CUT_MODES = {"ANY": 0, "ALL": 1}                  # SVR_CUT_*
 MAX_CUT_PLANES = 8                                # SVR_MAX_CUT_PLANES
@@ -290,6 +316,7 @@ SIGNATURES = {
     "svr_set_cut_planes": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int]),
     "svr_histogram": (C.c_int, [C.c_void_p, C.POINTER(HistogramParams), C.POINTER(HistogramOutputs), C.c_void_p]),
     "svr_objects": (C.c_int, [C.c_void_p, C.POINTER(ObjectsParams), C.POINTER(ObjectsOutputs), C.c_void_p]),
+    "svr_mesh": (C.c_int, [C.c_void_p, C.POINTER(MeshParams), C.POINTER(MeshOutputs), C.c_void_p]),
     "svr_sync": (C.c_int, [C.c_void_p]),
     "svr_sync_uploads": (C.c_int, [C.c_void_p]),
     "svr_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),

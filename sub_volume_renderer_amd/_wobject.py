@@ -1202,5 +1202,18 @@ class SubVolume(_HasWorld):
                            min=vmm[:, 0].contiguous(), max=vmm[:, 1].contiguous(), considered=head[1], background=head[3], lod=lod,
                            scale_factor=scale, volume=self)
 
+    # -- that object, or that level, as a surface ------------------------------------
+    def mesh(self, labels=None, level=None, lod: int = 0, box=None, stream=None):
+        """The surface of a picked object or of a level set of what LOD ``lod`` holds in HBM, extracted on the device
+        (definition: ``svr_mesh`` in include/svr.h; naive surface nets) -> :class:`~.mesh.SurfaceMesh`.  Exactly one of
+        ``labels`` (the voxels whose label is one of these ids are inside; a volume without segmentation reads label 0
+        everywhere) and ``level`` (the voxels whose value is >= ``level`` are inside; the ring's own units, like the iso
+        value) must be given, else ``ValueError``.  ``box`` means what it means in :meth:`histogram`; everything
+        outside box and window is outside, so the surface is closed, with flat caps where the box cuts the object.  The
+        call SYNCHRONISES twice: it counts first, allocates exactly, then emits.  An empty mesh is a valid result."""
+        from .mesh import mesh
+
+        return mesh(self, labels=labels, level=level, lod=lod, box=box, stream=stream)
+
     def synchronize(self):
         N.check(N.lib().svr_sync(self._rings.handle), "svr_sync")

@@ -45,6 +45,11 @@ hipError_t svr_launch_histogram(const svr_ctx* c, int lod, const int64_t lo[3], 
 // object_kernels.hip.  lo, n as above; everything checked by svr_objects.
 hipError_t svr_launch_objects(const svr_ctx* c, int lod, const int64_t lo[3], const int64_t n[3], const uint32_t* sel, uint32_t nsel,
                               int ignore_zero, uint32_t capacity, const svr_objects_outputs& out, hipStream_t stream);
+// mesh_kernels.hip.  lo: the first voxel of box and window intersected; plan: mesh_plan (mesh_plan.h) of its extent, null
+// for an empty box; scratch: plan->bytes of the context's mesh scratch; everything checked by svr_mesh.
+struct MeshPlan;
+hipError_t svr_launch_mesh(const svr_ctx* c, int lod, const int64_t lo[3], const MeshPlan* plan, int mode, float level,
+                           const uint32_t* sel, uint32_t nsel, void* scratch, const svr_mesh_outputs& out, hipStream_t stream);
 
 // the context as svr_create really allocates it ------------------------------------------------------------------------
 // The state of svr_set_transfer_function, svr_set_interpolation and svr_set_cut_planes (svr_modes.hip).  Like the colour
@@ -63,6 +68,13 @@ struct svr_ctx_ext : svr_ctx {
     std::vector<float*> tf_retired;
     int interp = SVR_INTERP_NEAREST;
     CutState cut = {};
+    // svr_mesh (svr_modes.hip): the scratch its kernels work in, grown on demand and shared by every call, so a call is
+    // ordered behind the previous one (mesh_done, recorded behind every call's last kernel) whatever its stream
+    std::mutex mesh_mu;                    // one svr_mesh at a time sizes the scratch and enqueues
+    void* mesh_scratch = nullptr;
+    size_t mesh_scratch_bytes = 0;
+    hipEvent_t mesh_done = nullptr;
+    bool mesh_pending = false;             // mesh_done has been recorded
 };
 // (every svr_ctx* of the ABI comes from svr_create)
 inline svr_ctx_ext* svr_ext(svr_ctx* c) { return static_cast<svr_ctx_ext*>(c); }

@@ -1,11 +1,13 @@
 // The render modes and passes of the C ABI (include/svr.h) beside the march: slices, slabs, composite and iso renders,
-// histograms and object tables, and the three setters of the state they share (svr_ctx_ext, svr_host.h).  Each entry
-// point checks its arguments and hands the launch of its kernel unit to draw_ordered.
+// histograms, object tables and surface meshes, and the three setters of the state they share (svr_ctx_ext,
+// svr_host.h).  Each entry point checks its arguments and hands the launch of its kernel unit to draw_ordered; svr_mesh
+// besides keeps the scratch memory its kernels work in.
 #include <math.h>
 
 #include <algorithm>
 
 #include "svr_host.h"
+#include "mesh_plan.h"
 
 // What svr_slice, svr_slab, svr_composite and svr_iso check first, in this order (who: the entry point's name, the
 // prefix of its error texts; args_ok: its own null test), and the frame with band_h defaulted to one band.
@@ -139,6 +141,55 @@ int svr_objects(svr_ctx* c, const svr_objects_params* op, const svr_objects_outp
     const int lod = op->lod, ignore_zero = op->ignore_zero;
     const uint32_t* sel = op->selected; const uint32_t nsel = op->selected_count, capacity = op->capacity;
     return SVR_DRAW_ORDERED(c, stream, svr_launch_objects(c, lod, lo, n, sel, nsel, ignore_zero, capacity, *out, s));
+}
+
+int svr_mesh(svr_ctx* c, const svr_mesh_params* mp, const svr_mesh_outputs* out, void* stream) {
+    SVR_REQUIRE(c && mp && out && out->header, "svr_mesh: null argument");
+    { const int rc = box_lod("svr_mesh", c, mp->lod); if (rc) return rc; }
+    SVR_REQUIRE(mp->mode == SVR_MESH_LABELS || mp->mode == SVR_MESH_LEVEL, "svr_mesh: unknown mode");
+    const bool labels = mp->mode == SVR_MESH_LABELS;
+    if (labels) SVR_REQUIRE(mp->selected_count >= 1 && mp->selected, "svr_mesh: SVR_MESH_LABELS needs at least one selected id");
+    else        SVR_REQUIRE(mp->level == mp->level, "svr_mesh: level must not be NaN");
+    SVR_REQUIRE(out->vertices || out->vertex_capacity == 0, "svr_mesh: NULL vertices with a non-zero vertex_capacity");
+    SVR_REQUIRE(out->triangles || out->triangle_capacity == 0, "svr_mesh: NULL triangles with a non-zero triangle_capacity");
+    int64_t lo[3], n[3];
+    { const int rc = box_window("svr_mesh", c, mp->lod, mp->use_box, mp->box_off, mp->box_shape, nullptr, 0, lo, n); if (rc) return rc; }
+    MeshPlan plan;
+    bool too_many = false;
+    const bool any = mesh_plan(n, n[0] > 0 ? mesh_head(lo[0], (uint32_t)c->lod[mp->lod].ring[0]) : 0u, plan, &too_many);
+    SVR_REQUIRE(!too_many, "svr_mesh: more than SVR_MESH_MAX_CELLS cells");
+
+    svr_ctx_ext* x = svr_ext(c);
+    std::lock_guard<std::mutex> lock(x->mesh_mu);
+    {
+        DeviceGuard guard(c->device);
+        if (!x->mesh_done) SVR_HIP_TRY(hipEventCreateWithFlags(&x->mesh_done, hipEventDisableTiming));
+        if (any && plan.bytes > x->mesh_scratch_bytes) {
+            // the call that may still be working in the old scratch ends first
+            if (x->mesh_pending) SVR_HIP_TRY(hipEventSynchronize(x->mesh_done));
+            if (x->mesh_scratch) (void)hipFree(x->mesh_scratch);
+            x->mesh_scratch = nullptr; x->mesh_scratch_bytes = 0;
+            if (hipMalloc(&x->mesh_scratch, (size_t)plan.bytes) != hipSuccess) {
+                x->mesh_scratch = nullptr;
+                (void)hipGetLastError();
+                svr_set_error("svr_mesh: out of device memory for the scratch of " + std::to_string(plan.bytes) + " bytes");
+                return SVR_ERR_NOMEM;
+            }
+            x->mesh_scratch_bytes = (size_t)plan.bytes;
+        }
+    }
+    const int lod = mp->lod, mode = mp->mode;
+    const float level = mp->level;
+    const uint32_t* sel = labels ? mp->selected : nullptr; const uint32_t nsel = labels ? mp->selected_count : 0u;
+    return draw_ordered(c, stream, "svr_launch_mesh", [&](hipStream_t s) {
+        hipError_t e = x->mesh_pending ? hipStreamWaitEvent(s, x->mesh_done, 0) : hipSuccess;
+        if (e != hipSuccess) return e;
+        e = svr_launch_mesh(c, lod, lo, any ? &plan : nullptr, mode, level, sel, nsel, x->mesh_scratch, *out, s);
+        // recorded behind whatever was enqueued, a failed chain's kernels too: the next call waits for them
+        const hipError_t r = hipEventRecord(x->mesh_done, s);
+        if (r == hipSuccess) x->mesh_pending = true;
+        return e != hipSuccess ? e : r;
+    });
 }
 
 int svr_set_transfer_function(svr_ctx* c, const float* rgba, int32_t K) {
