@@ -321,7 +321,13 @@ int  svr_gather_tiles(svr_ctx* ctx, int nplanes, const void* const* local, void*
 /* ---- LOD pyramid builder (device pointers): one 2x2x2 pooling step with the rules of the reference's
  * offline builders — mode 0 = mean (scripts/create_mouse_multiscale.py:23-54; SVR_U8: floor(sum/8),
  * SVR_F32: pairwise sum * 0.125), mode 1 = max (SVR_U32 labels, scripts/create_platynereis_multiscale.py:86-134).
- * src_dims (x, y, z) must be even; dst has half the extent per axis.  Enqueued on `stream`. */
+ * src_dims (x, y, z) must be even; dst has half the extent per axis.  Enqueued on `stream`.
+ * Alignment: the SVR_F32 / SVR_U32 kernels read pairs along x with 8-byte loads, so `src` must be 8-byte aligned for
+ * them (every row then is, the x extent being even); `dst` must be 4-byte aligned for them.  SVR_U8 takes any
+ * address (rows that are not 8-byte aligned are read byte by byte).  A misaligned pointer is refused with
+ * SVR_ERR_INVALID before anything is launched.
+ * SVR_F32 is IEEE f32 in the written order, ((a000+a001)+(a010+a011)) + ((a100+a101)+(a110+a111)) with x fastest,
+ * times 0.125f: NaN and +-inf propagate, a sum that overflows stays inf, subnormals are kept. */
 int  svr_pool2x(int device, const void* src, void* dst, const int32_t src_dims[3], int dtype, int mode, void* stream);
 
 /* ---- display side: blend one render "over" a vertical-gradient background (top row =
@@ -329,7 +335,16 @@ int  svr_pool2x(int device, const void* src, void* dst, const int32_t src_dims[3
  * 8 bits per channel.  Restates what pygfx does after the fragment shader (blending src_alpha /
  * one_minus_src_alpha, depth_compare "<", sRGB canvas); the reference's own tests draw over
  * gfx.Background(None, BackgroundMaterial(bottom, top)) (tests/conftest.py:17-22).  DEVICE pointers;
- * depth / flags / inout_depth may be NULL (NULL flags: every pixel is a fragment).  Parity unpinned. */
+ * depth / flags / inout_depth may be NULL (NULL flags: every pixel is a fragment).  Parity unpinned.
+ * Arithmetic is IEEE f32 in the written order, nothing contracted: t = (y + 0.5f) / height,
+ * c = bg_top * (1 - t) + bg_bottom * t, over a fragment c.rgb = s.rgb * a + c.rgb * (1 - a) and
+ * c.a = a + c.a * (1 - a), the OETF on c' = fminf(fmaxf(c, 0), 1) (12.92 c' up to 0.0031308f, else
+ * 1.055 powf(c', 1 / 2.4f) - 0.055), and each channel stored as (uint8)(fminf(fmaxf(v, 0), 1) * 255 + 0.5f).
+ * fmaxf / fminf return their other operand for a NaN, so a NaN channel quantises to 0 (and inf to 255, -inf to 0).
+ * A NaN depth, or a NaN in inout_depth, fails "<": the fragment is not drawn and inout_depth keeps its bits.
+ * Only powf may differ from a correctly rounded restatement.
+ * rgba must be 16-byte aligned and out_rgba8 4-byte aligned (refused with SVR_ERR_INVALID otherwise);
+ * width or height 0 is accepted and writes nothing. */
 typedef struct svr_compose_params {
     float   bg_bottom[4];
     float   bg_top[4];

@@ -14,14 +14,26 @@ import numpy as np
 f32 = np.float32
 
 
+def clamp01(c):
+    """fminf(fmaxf(c, 0), 1) of include/svr.h: fmax / fmin return the other operand for a NaN, so NaN -> 0
+    (np.clip would pass the NaN on to an undefined integer cast)."""
+    return np.fmin(np.fmax(np.asarray(c, f32), f32(0)), f32(1)).astype(f32)
+
+
 def srgb_encode(c):
-    c = np.clip(c, f32(0), f32(1)).astype(f32)
+    c = clamp01(c)
     hi = f32(1.055) * np.power(c, f32(1.0 / 2.4), dtype=f32) - f32(0.055)
     return np.where(c <= f32(0.0031308), f32(12.92) * c, hi).astype(f32)
 
 
 def compose(rgba, depth=None, flags=None, bg_bottom=(0, 0, 0, 1), bg_top=(0, 0, 0, 1), zbuf=None, srgb=True):
-    """Returns (uint8 [h, w, 4], zbuf or None)."""
+    """Returns (uint8 [h, w, 4], zbuf or None).  NaN follows include/svr.h: a NaN channel quantises to 0, a NaN depth
+    (or zbuf) fails "<" and the fragment is not drawn."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        return _compose(rgba, depth, flags, bg_bottom, bg_top, zbuf, srgb)
+
+
+def _compose(rgba, depth, flags, bg_bottom, bg_top, zbuf, srgb):
     rgba = np.asarray(rgba, f32)
     h, w = rgba.shape[:2]
     t = ((np.arange(h, dtype=f32) + f32(0.5)) / f32(h))[:, None, None]
@@ -38,5 +50,5 @@ def compose(rgba, depth=None, flags=None, bg_bottom=(0, 0, 0, 1), bg_top=(0, 0, 
         zbuf = np.where(draw, np.asarray(depth, f32), zbuf).astype(f32)
     if srgb:
         c[..., :3] = srgb_encode(c[..., :3])
-    q = (np.clip(c, f32(0), f32(1)) * f32(255.0) + f32(0.5)).astype(np.uint8)
+    q = (clamp01(c) * f32(255.0) + f32(0.5)).astype(np.uint8)
     return q, zbuf

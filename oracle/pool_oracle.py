@@ -19,9 +19,10 @@ def mean_u8(a):
 
 def mean_f32(a):
     b = _blocks(a.astype(np.float32))
-    s0 = (b[:, 0, :, 0, :, 0] + b[:, 0, :, 0, :, 1]) + (b[:, 0, :, 1, :, 0] + b[:, 0, :, 1, :, 1])
-    s1 = (b[:, 1, :, 0, :, 0] + b[:, 1, :, 0, :, 1]) + (b[:, 1, :, 1, :, 0] + b[:, 1, :, 1, :, 1])
-    return ((s0 + s1) * np.float32(0.125)).astype(np.float32)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):     # NaN, inf and subnormals are data here (IEEE f32)
+        s0 = (b[:, 0, :, 0, :, 0] + b[:, 0, :, 0, :, 1]) + (b[:, 0, :, 1, :, 0] + b[:, 0, :, 1, :, 1])
+        s1 = (b[:, 1, :, 0, :, 0] + b[:, 1, :, 0, :, 1]) + (b[:, 1, :, 1, :, 0] + b[:, 1, :, 1, :, 1])
+        return ((s0 + s1) * np.float32(0.125)).astype(np.float32)
 
 
 def max_u32(a):

@@ -20,6 +20,16 @@ def compose(volume, result, *, background=((0.0, 0.0, 0.0, 1.0), (0.0, 0.0, 0.0,
     import torch
 
     h, w = result.rgba.shape[:2]
+    # the kernel indexes every plane as y * w + x: a cropped or strided view would compose other pixels
+    for name, plane, shape, dtype in (("rgba", result.rgba, (h, w, 4), torch.float32),
+                                      ("depth", result.depth, (h, w), torch.float32),
+                                      ("flags", result.flags, (h, w), torch.uint8)):
+        if plane is None:
+            continue
+        if tuple(plane.shape) != shape or plane.dtype != dtype or not plane.is_contiguous():
+            raise ValueError(f"result.{name} must be a contiguous {str(dtype).replace('torch.', '')} tensor {list(shape)}")
+    if result.rgba.data_ptr() % 16:
+        raise ValueError("result.rgba must be 16-byte aligned (a view that starts inside a pixel is not: clone it)")
     if out is None:
         out = torch.empty((h, w, 4), dtype=torch.uint8, device=result.rgba.device)
     if tuple(out.shape) != (h, w, 4) or out.dtype != torch.uint8 or not out.is_contiguous():

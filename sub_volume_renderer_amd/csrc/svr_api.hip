@@ -348,6 +348,10 @@ int svr_pool2x(int device, const void* src, void* dst, const int32_t src_dims[3]
         SVR_REQUIRE(src_dims[a] >= 2 && (src_dims[a] & 1) == 0, "svr_pool2x: every source extent must be even and >= 2");
     SVR_REQUIRE((dtype == SVR_U8 && mode == 0) || (dtype == SVR_F32 && mode == 0) || (dtype == SVR_U32 && mode == 1),
                 "svr_pool2x: supported: mean of u8 / f32 (mode 0), max of u32 (mode 1)");
+    if (dtype != SVR_U8) {                     // 8-byte loads of x pairs, 4-byte stores; the u8 kernel has a scalar path
+        SVR_REQUIRE((uintptr_t)src % 8 == 0, "svr_pool2x: src must be 8-byte aligned for SVR_F32 / SVR_U32");
+        SVR_REQUIRE((uintptr_t)dst % 4 == 0, "svr_pool2x: dst must be 4-byte aligned for SVR_F32 / SVR_U32");
+    }
     DeviceGuard guard(device);
     SVR_HIP_TRY(svr_launch_pool2x(src, dst, src_dims, dtype, mode, static_cast<hipStream_t>(stream)));
     return SVR_OK;
@@ -358,6 +362,8 @@ int svr_compose(svr_ctx* c, const float* rgba, const float* depth, const uint8_t
     SVR_REQUIRE(c && rgba && params && out_rgba8, "svr_compose: null argument");
     SVR_REQUIRE(width >= 0 && height >= 0, "svr_compose: negative size");
     SVR_REQUIRE(!inout_depth || depth, "svr_compose: a depth test needs the render's depth plane");
+    SVR_REQUIRE((uintptr_t)rgba % 16 == 0, "svr_compose: rgba must be 16-byte aligned");
+    SVR_REQUIRE((uintptr_t)out_rgba8 % 4 == 0, "svr_compose: out_rgba8 must be 4-byte aligned");
     DeviceGuard guard(c->device);
     SVR_HIP_TRY(svr_launch_compose(rgba, depth, flags, width, height, *params, out_rgba8, inout_depth,
                                    static_cast<hipStream_t>(stream)));

@@ -14,7 +14,9 @@ from . import _native as N
 
 def pool2x(t, mode: str):
     """One 2x2x2 pooling step of a contiguous 3-D CUDA tensor: ``mode='mean'`` (uint8: floor of the
-    mean; float32) or ``mode='max'`` (int32 holding uint32 label bit patterns, or uint8)."""
+    mean; float32) or ``mode='max'`` (int32 holding uint32 label bit patterns, nothing else).  The float32 / int32
+    kernels read 8 bytes at a time: a contiguous view that is only 4-byte aligned (an odd element offset into a
+    larger buffer) is copied to an aligned tensor first; uint8 is read where it lies, at any address."""
     import torch
 
     if not (t.is_cuda and t.dim() == 3 and t.is_contiguous()):
@@ -25,6 +27,8 @@ def pool2x(t, mode: str):
             ("max", torch.int32): (2, 1)}.get((mode, t.dtype))
     if code is None:
         raise TypeError(f"unsupported combination mode={mode!r} dtype={t.dtype}")
+    if t.element_size() == 4 and t.data_ptr() % 8:
+        t = t.clone(memory_format=torch.contiguous_format)           # fresh allocations are aligned far beyond 8 bytes
     out = torch.empty(tuple(s // 2 for s in t.shape), dtype=t.dtype, device=t.device)
     dims = N.i3(tuple(t.shape)[::-1])
     N.check(N.lib().svr_pool2x(t.device.index, C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr()), dims,

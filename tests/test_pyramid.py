@@ -27,6 +27,110 @@ def test_pool_oracle_matches_reference_numpy_expression():
     np.testing.assert_array_equal(pool_oracle.max_u32(l0), l1)
 
 
+def bits(a):
+    """float32 / int32 as uint32 bit patterns: -0 differs from +0 and a NaN equals the same NaN."""
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def row_of_blocks(blocks, dtype):
+    """2 x 2 x 2 blocks [z][y][x] laid side by side along x: a (2, 2, 2 n) volume whose pooled row is one value each."""
+    return np.ascontiguousarray(np.concatenate([np.asarray(b, dtype).reshape(2, 2, 2) for b in blocks], axis=2))
+
+
+def f32_value_cases():
+    """[(name, block as 8 values in memory order z, y, x, expected float32)], the expected values derived by hand from
+    ((b000 + b001) + (b010 + b011)) + ((b100 + b101) + (b110 + b111)), then * 0.125f, in IEEE f32."""
+    nan, inf = np.float32(np.nan), np.float32(np.inf)
+    tiny = np.float32(2.0 ** -149)                         # the smallest subnormal
+    half_min = np.float32(2.0 ** -127)                     # a subnormal with one bit, half the smallest normal
+    big = np.float32(3e38)
+    cases = [(f"nan_at_{k}", [nan if i == k else 1.0 for i in range(8)], nan) for k in range(8)]
+    cases += [
+        ("inf_alone", [1, inf, 1, 1, 1, 1, 1, 1], inf),
+        ("minus_inf_alone", [1, 1, 1, 1, 1, 1, -inf, 1], -inf),
+        ("inf_with_minus_inf", [inf, 1, 1, 1, 1, 1, 1, -inf], nan),
+        ("minus_zero_alone", [-0.0] * 8, np.float32(-0.0)),                        # -0 + -0 = -0, * 0.125 = -0
+        ("minus_zero_with_zero", [-0.0] * 5 + [0.0] + [-0.0] * 2, np.float32(0.0)),    # -0 + +0 = +0 (round to nearest)
+        ("eight_smallest_subnormals", [tiny] * 8, tiny),                           # 8 * 2^-149 / 8, all exact
+        ("one_smallest_subnormal", [0, 0, 0, tiny, 0, 0, 0, 0], np.float32(0.0)),   # 2^-152 < half of 2^-149: +0
+        ("subnormal_result", [half_min] * 8, half_min),                            # the sum 2^-124 is normal, the mean is not
+        ("sum_overflows", [big] * 8, inf),                                         # 3e38 + 3e38 > FLT_MAX before * 0.125f
+        ("pairs_overflow_apart", [big, big, -big, -big, 1, 1, 1, 1], nan),         # (+inf) + (-inf); other orders give 0.5
+        # 1e8 + 1 = 1e8 (ulp 8), so each plane is 1e8 + (-1e8) = 0 and the mean is 0;
+        # pairing across y, (b000 + b010) + (b001 + b011), would give 0 + 2 per plane, mean 0.5
+        ("mixed_magnitudes", [1e8, 1, -1e8, 1, 1, 1e8, 1, -1e8], np.float32(0.0)),
+        # (1e8 + 1) + (1 + 1) = 1e8 + 2 = 1e8 and (-1e8 + 1) + (1 + 1) = -1e8: mean 0; adding the two planes
+        # first, (b000 + b100) + (b001 + b101) ..., would give (0 + 2) + (2 + 2), mean 0.75
+        ("planes_cancel", [1e8, 1, 1, 1, -1e8, 1, 1, 1], np.float32(0.0)),
+    ]
+    return [(n, np.asarray(b, np.float32), np.float32(e)) for n, b, e in cases]
+
+
+def u8_value_cases():
+    """[(name, 8 bytes, expected)]: floor(sum / 8)."""
+    cases = [("all_255", [255] * 8, 255)]                                           # sum 2040, the largest
+    for k in range(8):
+        cases.append((f"eight_at_{k}", [8 if i == k else 0 for i in range(8)], 1))
+        cases.append((f"seven_at_{k}", [7 if i == k else 0 for i in range(8)], 0))
+    for r in range(8):                                                              # 800 + r: floor, never round
+        cases.append((f"sum_mod_8_is_{r}", [100] * 7 + [100 + r], 100))
+    cases.append(("rounds_down_at_7", [255] * 7 + [254], 254))                      # 2039 / 8 = 254.875
+    return [(n, np.asarray(b, np.uint8), e) for n, b, e in cases]
+
+
+def u32_value_cases():
+    cases = [("top_bit_beats_int_max", [0x7FFFFFFF, 0x80000000, 0, 0, 0, 0, 0, 0], 0x80000000),
+             ("top_bit_last", [0x7FFFFFFF] * 7 + [0x80000000], 0x80000000),
+             ("all_ones", [0, 0, 0, 0, 0, 0xFFFFFFFF, 0, 0], 0xFFFFFFFF),
+             ("all_ones_beside_int_max", [0xFFFFFFFF, 0x7FFFFFFF] * 4, 0xFFFFFFFF),
+             ("all_zero", [0] * 8, 0)]
+    return [(n, np.asarray(b, np.uint32), e) for n, b, e in cases]
+
+
+def test_pool_oracle_value_cases_against_hand_derived_answers():
+    names, blocks, want = zip(*f32_value_cases())
+    got = pool_oracle.mean_f32(row_of_blocks(blocks, np.float32))
+    assert got.shape == (1, 1, len(names)) and got.dtype == np.float32
+    for n, g, w in zip(names, bits(got)[0, 0], bits(np.asarray(want, np.float32))):
+        if n.startswith("nan") or n in ("inf_with_minus_inf", "pairs_overflow_apart"):
+            assert np.isnan(np.uint32(g).view(np.float32)), n                      # any NaN
+        else:
+            assert g == w, (n, hex(g), hex(w))
+    # the orders the contract excludes do give other bits on the cases made for them
+    b = dict((n, blk.reshape(2, 2, 2)) for n, blk, _ in f32_value_cases())
+    m = b["mixed_magnitudes"]
+    across_y = ((m[0, 0, 0] + m[0, 1, 0]) + (m[0, 0, 1] + m[0, 1, 1])) + ((m[1, 0, 0] + m[1, 1, 0]) + (m[1, 0, 1] + m[1, 1, 1]))
+    assert across_y * np.float32(0.125) == np.float32(0.5)
+    p = b["planes_cancel"]
+    z_first = ((p[0, 0, 0] + p[1, 0, 0]) + (p[0, 0, 1] + p[1, 0, 1])) + ((p[0, 1, 0] + p[1, 1, 0]) + (p[0, 1, 1] + p[1, 1, 1]))
+    assert z_first * np.float32(0.125) == np.float32(0.75)
+    names, blocks, want = zip(*u8_value_cases())
+    np.testing.assert_array_equal(pool_oracle.mean_u8(row_of_blocks(blocks, np.uint8))[0, 0], np.asarray(want, np.uint8))
+    names, blocks, want = zip(*u32_value_cases())
+    np.testing.assert_array_equal(pool_oracle.max_u32(row_of_blocks(blocks, np.uint32))[0, 0], np.asarray(want, np.uint32))
+
+
+def oracle_pyramid(a, levels, mode):
+    """The whole array pooled level by level on the CPU: what a store must hold however it was cut into slabs."""
+    rule = {("mean", np.dtype(np.uint8)): pool_oracle.mean_u8, ("mean", np.dtype(np.float32)): pool_oracle.mean_f32,
+            ("max", np.dtype(np.uint32)): pool_oracle.max_u32}[(mode, a.dtype)]
+    out = [a]
+    for _ in range(1, levels):
+        out.append(rule(out[-1]))
+    return out
+
+
+def test_pooling_commutes_with_cutting_into_slabs():
+    """The premise of write_multiscale_store: pooling a slab of 2^k-aligned planes equals the slab of the pooled array."""
+    rng = np.random.default_rng(8)
+    a = (rng.random((96, 12, 20)) * 300 - 20).astype(np.float32)
+    whole = oracle_pyramid(a, 3, "mean")
+    for z0, z1 in ((0, 64), (64, 96)):
+        part = oracle_pyramid(a[z0:z1], 3, "mean")
+        for k in range(3):
+            np.testing.assert_array_equal(bits(part[k]), bits(whole[k][z0 >> k:z1 >> k]))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [(8, 12, 20), (64, 64, 64), (2, 2, 2), (6, 10, 30)])
 def test_pool2x_bit_exact(shape):
@@ -84,7 +188,13 @@ def test_pool_kernels_stream_at_a_sane_fraction_of_hbm_rate(capsys):
         with capsys.disabled():
             print(f"\npool2x {mode} {dtype}: {ms:.3f} ms, {gbs:.0f} GB/s ({gbs / 8000:.2f} of HBM peak)")
         assert gbs > 800.0, (mode, gbs)
-        del t
+        # and what it streams is right: 2^27 outputs, many passes of the capped grid, against torch's own reductions
+        # on the device (the fills are below 2^31, so the signed amax is the unsigned maximum)
+        got = pool2x(t, mode)
+        b = t.reshape(n // 2, 2, n // 2, 2, n // 2, 2)
+        want = (b.sum(dim=(1, 3, 5), dtype=torch.int32) // 8).to(torch.uint8) if mode == "mean" else b.amax(dim=(1, 3, 5))
+        assert got.shape == want.shape and got.dtype == want.dtype and torch.equal(got, want), (mode, dtype)
+        del t, b, got, want
 
 
 @pytest.mark.gpu
