@@ -211,7 +211,18 @@ int  svr_set_material(svr_ctx* ctx, const svr_material* m);
  * to u32 with wrap-around).  The copy is staged through pinned memory and
  * enqueued on the context's upload stream; the call returns once the source
  * has been consumed (source may be freed), not when the device copy is done.
- * Either source may be NULL to leave that texture untouched. */
+ * Either source may be NULL to leave that texture untouched.
+ * A stride may be negative (a flipped axis: the pointer is still element (0,0,0), the last one of that axis in memory)
+ * or zero (one element, row or plane broadcast along that axis); every pointer is a multiple of its element size.
+ * The casts, bit for bit (tests/ring_transfer_cases.py, tests/test_gpu_ring_transfer.py): integers to f32 round to
+ * nearest, ties to even (u64 2^24 + 1 -> 2^24, 2^64 - 1 -> 2^64); f64 to f32 the same, beyond the f32 range +-inf,
+ * below it subnormals and +-0; the NaN payload of an f64 source is not preserved.
+ * Integer labels wrap modulo 2^32 (i8 -128 -> 4294967168, i64 2^32 + 5 -> 5).  Float label sources are defined on
+ * [0, 2^32), truncating toward zero (4294967295.9 -> 4294967295); outside it and for NaN the label is undefined.
+ * SVR_ERR_RANGE for a region outside the ring; SVR_ERR_INVALID, with nothing enqueued, for a NULL ctx / offset /
+ * shape, a lod out of range, an unknown dtype code, NULL strides beside a source, labels into a context without label
+ * rings, a source of another dtype into SVR_U8 / SVR_U16 rings, and (host sources) one row of the region, density plus
+ * labels in their source types, wider than a staging slot less 32 bytes. */
 int  svr_upload_region(svr_ctx* ctx, int lod,
                        const int32_t dst_off[3], const int32_t shape[3],
                        const void* density, int density_dtype, const int64_t density_strides[3],
@@ -250,7 +261,9 @@ int  svr_ticket_pending(svr_ctx* ctx, uint64_t ticket, int* pending);
 
 /* ---- readback of a ring region into packed host arrays (shader-order
  * shape, x fastest): the texture.data numpy mirror the reference's tests read
- * (tests/wrapping_buffer/test_load_logical_roi.py:5-76).  Synchronous. */
+ * (tests/wrapping_buffer/test_load_logical_roi.py:5-76).  Synchronous.
+ * SVR_U8 / SVR_U16 rings read back as f32 (exact).  Either output may be NULL (it is not written); both NULL, or an
+ * extent of 0, reads nothing.  A context without label rings reads every label as 0.  Refusals as for the uploads. */
 int  svr_read_region(svr_ctx* ctx, int lod, const int32_t off[3], const int32_t shape[3],
                      float* density_out, uint32_t* labels_out);
 /* zero both textures of one LOD (fresh WrappingBuffer state) */
@@ -372,9 +385,12 @@ int  svr_compose(svr_ctx* ctx, const float* rgba, const float* depth, const uint
  *                             out.rgb = b.rgb * (1 - a) + c * a,  out.a = b.a * (1 - a) + a;
  *                    otherwise out = b.
  *     edge_mask(p) 1 where edge(p), else 0 (u8).
+ * depth_tolerance -0.0 is not < 0: the depth test is ON, with tolerance 0 (+inf: on, and no step exceeds it; NaN:
+ * refused).  A NaN depth, of p or of q, is no step.  A flag byte other than SVR_PIX_HIT (0, 1, or any other value) is
+ * a non-hit.  L(p) % color_count is unsigned.
  * DEVICE pointers; depth may be NULL when depth_tolerance < 0, edge_mask may be NULL.  rgba, out_rgba and colors are
- * 16-byte aligned.  `selected` is sorted ascending (an unsorted set gives wrong highlighting but never reads outside
- * it).  out_rgba may be rgba itself (in place): a pixel's output depends on its own rgba alone.  A plane rendered with
+ * 16-byte aligned (else SVR_ERR_INVALID, with nothing launched).  `selected` is sorted ascending (an unsorted set
+ * gives wrong highlighting but never reads outside it).  out_rgba may be rgba itself (in place): a pixel's output depends on its own rgba alone.  A plane rendered with
  * a region (svr_frame) is outlined as an image of its own: pixels outside it are not neighbours.  Enqueued on
  * `stream`. */
 typedef struct svr_outline_params {

@@ -238,3 +238,162 @@ def test_null_context_is_refused_with_a_message():
     with pytest.raises(ValueError, match="svr_outline"):
         _native.check(lib.svr_outline(None, None, None, None, None, 8, 8, ctypes.byref(q), None, 0, None, 0, None,
                                       None, None), "svr_outline")
+
+
+# ---- the restatement at its edges (tests/outline_cases.py): answers that do not come from it --------------------------
+import outline_cases as OC  # noqa: E402
+
+
+@pytest.mark.parametrize("kind", list(OC.LONE_KINDS))
+def test_lone_pixel_marks_its_chebyshev_ball(kind):
+    """One odd pixel in a uniform frame, at the centre, the image corners and either side of the tile seams: the edge
+    mask is the ball of radius r round it clipped to the image, with the pixel itself when it is a hit (labels 0 and
+    0xFFFFFFFF included) and without it when its flag byte is anything else (0, 1, 3, 255)."""
+    n = 0
+    for case in OC.lone_pixel_cases([kind]):
+        out, mask = OC.reference(case)
+        np.testing.assert_array_equal(mask, case.mask, err_msg=case.name)
+        assert int(case.mask.sum()) >= 3                                # a corner at r = 1 without its centre
+        miss = case.flags != HIT
+        np.testing.assert_array_equal(out[miss], case.rgba[miss])
+        n += 1
+    assert n == 13 * len(OC.LONE_FRAMES)
+
+
+def test_strict_depth_step_values_are_exact():
+    z0, tau, odd = OC.strict_step_values()
+    assert (z0, tau) == (F32(0.0625), F32(0.125))
+    assert odd["above_by_tau"] == (F32(0.1875), False) and odd["below_by_tau"] == (F32(-0.0625), False)
+    assert float(odd["above_by_next"][0]) == 0.1875 + 2.0 ** -26 and odd["above_by_next"][1]
+    assert float(odd["below_by_next"][0]) == -0.0625 - 2.0 ** -26 and odd["below_by_next"][1]     # one ulp of tau
+
+
+@pytest.mark.parametrize("radius", OC.DEPTH_RADII)
+def test_depth_family_against_scalar_arithmetic(radius):
+    """A step of exactly tau draws nothing and the next f32 draws the ball, above and below the field; +-inf, NaN, signed
+    zeros and a subnormal as field and as odd pixel under tau 0, -0, +inf and 1e-3 (a NaN on either side never
+    differs; -0.0 turns the test on like 0.0); a non-hit's stale depth makes a silhouette and nothing else."""
+    cases = list(OC.depth_cases([radius]))
+    assert len(cases) == 4 + 36 * (2 if radius == 16 else 4) + 2
+    edges = 0
+    for case in cases:
+        _, mask = OC.reference(case)
+        np.testing.assert_array_equal(mask, case.mask, err_msg=case.name)
+        edges += bool(case.mask.any())
+    assert len(cases) // 4 < edges < 3 * len(cases) // 4               # both outcomes are well represented
+    by_name = {c.name.rsplit("-r", 1)[0]: c for c in cases}
+    ball = (2 * radius + 1) ** 2                                        # the odd pixel is further than 16 from every border
+    assert by_name["depth-field+inf-odd+inf-tau-0"].mask.sum() == 0                # inf - inf is NaN: no step
+    assert by_name["depth-field+inf-odd-inf-tau1e-3"].mask.sum() == ball
+    assert by_name["depth-field-0-odd+0-tau-0"].mask.sum() == 0                    # |0 - -0| = 0 is not > -0
+    assert by_name["depth-field+0-oddsubnormal-tau-0"].mask.sum() == ball
+    assert by_name["depth-field+0-oddnan-tau1e-3"].mask.sum() == 0
+    assert by_name["depth-field+0-oddsubnormal-tau-0"].direct and not by_name["depth-field+0-oddnan-tau1e-3"].direct
+    if radius != 16:
+        assert by_name["depth-field+inf-odd-inf-tau+inf"].mask.sum() == 0          # nothing exceeds +inf
+
+
+def test_hand_written_rows():
+    cases = list(OC.hand_cases())
+    assert [c.name for c in cases][:2] == ["hand-1x1-r16", "hand-top-labels-inf-nan"]
+    for case in cases:
+        _, mask = OC.reference(case)
+        np.testing.assert_array_equal(mask, case.mask, err_msg=case.name)
+
+
+def test_label_modulo_is_unsigned():
+    """0xFFFFFFFF % 3 = 0 and 0x80000000 % 3 = 2 (a signed 32-bit modulo gives -1 and -2); % 7: 3 and 2; % 1: 0."""
+    assert [l % 3 for l in OC.MODULO_LABELS[:2]] == [0, 2] and [l % 7 for l in OC.MODULO_LABELS[:2]] == [3, 2]
+    for case in OC.color_cases():
+        if not case.name.startswith("color-modulo"):
+            continue
+        pal = case.kwargs["colors"]
+        out, mask = OC.reference(case)
+        np.testing.assert_array_equal(mask, case.mask)
+        idx = [l % len(pal) for l in OC.MODULO_LABELS]                  # Python ints: no sign to get wrong
+        want = hsv_to_rgb_reference(pal[idx, 0], pal[idx, 1], 1.0)      # opacity 1: the outline colour itself
+        np.testing.assert_array_equal(out[0, :, :3], want)
+        np.testing.assert_array_equal(out[1, :, :3], want)
+        if len(pal) > 1:
+            assert len({tuple(c) for c in want.tolist()}) == len(set(idx))    # the palette entries differ visibly
+
+
+def test_hue_table_reaches_every_branch():
+    """The hue / saturation table of the colour family: NaN only where the hue is NaN and the saturation is not 0;
+    1/6 and its upper neighbour fall in sector 1, its lower neighbour in sector 0; 1.0, 1.25, -0.1 and 1e30 take the
+    last branch."""
+    h = np.array(OC.HUES, F32)
+    fl = np.floor(h * F32(6))
+    assert fl[:5].tolist() == [0.0, 0.0, 1.0, 1.0, 5.0] and fl[5:8].tolist() == [6.0, 7.0, -1.0] and fl[8] > 1e30
+    for s in (0.5, 1.0):
+        rgb = hsv_to_rgb_reference(h, np.full(h.shape, s, F32), 1.0)
+        assert np.isnan(rgb[-1]).any() and not np.isnan(rgb[:-1]).any()
+        assert rgb[1, 0] == 1 and rgb[2, 1] == 1 and rgb[3, 1] == 1                  # (v, t, p) then (q, v, p)
+        np.testing.assert_array_equal(rgb[5:9, 0], np.ones(4, F32))                  # (v, p, q)
+    assert not np.isnan(hsv_to_rgb_reference(h, np.zeros(h.shape, F32), 1.0)).any()
+
+
+def test_opacity_dimming_and_pass_through_of_special_rgba():
+    cases = {c.name: c for c in OC.color_cases()}
+    for by in (0, 1):
+        c = cases[f"color-opacity0-by{by}"]
+        out, mask = OC.reference(c)
+        assert mask.all()
+        np.testing.assert_array_equal(out, c.rgba)                      # b * 1 + c * 0 on finite non-negative values
+        c = cases[f"color-opacity1-by{by}"]
+        out, _ = OC.reference(c)
+        assert np.all(out[..., 3] == 1)
+    c = cases["color-dim0.001-subnormal"]
+    assert np.all(np.abs(c.rgba) < np.finfo(F32).tiny) and np.all(c.rgba != 0)
+    sel = c.label == 2
+    for name in ("color-dim0-subnormal", "color-dim1-subnormal", "color-dim0.001-subnormal"):
+        c = cases[name]
+        out, mask = OC.reference(c)
+        quiet = ~sel & ~mask.astype(bool)
+        assert quiet.any()
+        np.testing.assert_array_equal(out[quiet][:, :3].view(np.uint32),
+                                      (c.rgba[quiet][:, :3] * F32(c.kwargs["dim_unselected"])).view(np.uint32))
+    c = cases["color-special-rgba-a0.5"]
+    out, _ = OC.reference(c)
+    miss = c.flags != HIT
+    assert miss.sum() >= 20 and np.isnan(c.rgba[miss]).any() and np.isinf(c.rgba[miss]).any()
+    np.testing.assert_array_equal(out[miss].view(np.uint32), c.rgba[miss].view(np.uint32))
+
+
+def test_no_blocky_frame_is_vacuous():
+    """For every (family-5 frame, r, depth test on / off) the restatement's mask holds at least 50 edge hits and at least
+    50 hits that are no edge; the frames hold labels 0 and 0xFFFFFFFF as hits and flag bytes 0, 1, 2 and 3."""
+    frames = list(OC.blocky_frames())
+    assert len(frames) == 2 * len(OC.BLOCKY_FRAMES)
+    for name, (rgba, depth, label, flags, tau_on), r, tau in frames:
+        hit = flags == HIT
+        near = window_differs(label, flags, r, depth, tau)
+        assert int((hit & near).sum()) >= 50 and int((hit & ~near).sum()) >= 50, name
+        assert 0.75 < hit.mean() < 0.95 and set(np.unique(flags)) == {0, 1, 2, 3}, name
+        assert (label[hit] == 0).any() and (label[hit] == OC.TOP).any(), name
+        if tau is not None:
+            assert tau > 0 and int((near & ~window_differs(label, flags, r)).sum()) >= 20, name      # the depth test adds edges
+    for name, planes, r, tau in OC.tiny_frames():
+        assert planes[3].shape in {(h, w) for w, h in OC.TINY_FRAMES}
+    sizes = {(c.flags.shape, c.kwargs["radius"]) for c in OC.frame_cases(OC.tiny_frames(), "tiny")[0][4]}
+    assert sizes == {((1, 1), 1)}
+
+
+def test_selection_family_is_sorted_and_reaches_both_ends():
+    cases = list(OC.selection_cases())
+    lens = {len(c.kwargs["selected"]) for c in cases}
+    assert {1, 2, 3, 1000} <= lens and all(c.direct for c in cases)
+    changed = 0
+    for c in cases:
+        sel = c.kwargs["selected"]
+        assert sel.dtype == np.uint32 and np.all(sel[1:] >= sel[:-1])
+        out, mask = OC.reference(c)
+        hit = c.flags == HIT
+        dimmed = hit & ~np.isin(c.label, sel)
+        assert dimmed.any()                                             # no selection holds every label of its frame
+        changed += int(np.isin(c.label[hit], sel).any())
+    mid = [c for c in cases if "-mid-" in c.name]
+    lo, hi = mid[0].label[mid[0].flags == HIT].min(), mid[0].label[mid[0].flags == HIT].max()
+    assert any(c.kwargs["selected"][0] < lo and c.kwargs["selected"][-1] > hi for c in mid)
+    assert any(len(np.unique(c.kwargs["selected"])) < len(c.kwargs["selected"]) for c in cases)
+    assert changed >= len(cases) // 2
