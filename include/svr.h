@@ -127,7 +127,28 @@ typedef struct svr_material {
      *     t_i = max(1 - weight_falloff * d_i, 0),  w_i = t_i * t_i
      *     value = (sum w_i * s_i) / (sum w_i)      over the samples of the ray, in order, f32
      * shown at the sample with the largest w_i * |s_i| (first one wins; it gives depth, label and fog distance);
-     * nothing but zeros along the ray: a miss.  The ray ends at the first sample with t_i == 0. */
+     * nothing but zeros along the ray: a miss.  The ray ends at the first sample with t_i == 0.
+     *
+     * Signed and non-finite samples (float rings hold any f32; oracle/lmip_oracle.c, IEEE comparisons, decides):
+     *   - the intensity of a sample s is |s|: a negative voxel counts by its magnitude and -inf counts as +inf;
+     *     the value shown is s itself, sign included.
+     *   - a NaN sample fails every comparison: it does not reach lmip_threshold (|s| >= threshold is false, also
+     *     for threshold -inf, so under MIP too), it does not raise a running maximum (|s| > max is false) and it
+     *     does not end a run through the fall-off test (|s| < max * lmip_fall_off is false); it still counts
+     *     towards lmip_max_samples.  MIP therefore shows the first occurrence of the largest |s| among the ray's
+     *     non-NaN samples, and a ray with no non-NaN sample is a MISS under LMIP and MIP alike.
+     *   - -0.0 has intensity 0: it starts a run under a threshold <= 0 and is never replaced by +0.0 (strict >).
+     *   - SVR_MODE_WEIGHTED_AVERAGE: num and den are plain f32 sums.  A NaN sample makes num, and so the value,
+     *     NaN; +inf and -inf in one ray make num NaN, one of them alone makes the value that infinity; a sum of
+     *     finite products that overflows is an infinity like any other.  The sample shown is the first with the
+     *     largest w_i * |s_i| among those whose product is not NaN (a NaN product fails >); the ray is a HIT when
+     *     that largest product is > 0, whatever the value.
+     *   - shading takes the winning s through v = (s - clim[0]) / (clim[1] - clim[0]), powf(v, gamma),
+     *     srgb2physical, hsv_to_rgb and the fog mix in that order with no clamp in between, so the colour of a
+     *     negative, infinite or NaN s (or of an s - clim[0] that overflows) is whatever those operations give:
+     *     powf of a negative base with a fractional gamma is NaN, an infinite v gives infinite or NaN channels
+     *     (inf * 0 in hsv_to_rgb).  Label, depth and the pick word come from the sample's position and stay
+     *     finite. */
     int32_t  render_mode;          /* svr_render_mode */
     float    weight_falloff;       /* >= 0; only read in SVR_MODE_WEIGHTED_AVERAGE */
 } svr_material;
@@ -421,7 +442,8 @@ int  svr_outline(svr_ctx* ctx, const float* rgba, const float* depth, const uint
  * classified from dx:
  *     DISCARD  not 0 <= dx_k < size_k on every axis (NaN is outside):  rgba (0,0,0,0), value 0, label 0, lod 255
  *     HIT      the first LOD l whose ROI holds dx (the march's try_sample_scale_i test, sample_vol.wgsl:4-25):
- *                value = that LOD's density texel (f32), label = its label texel (0 without label rings), lod = l,
+ *                value = that LOD's density texel (f32), label = its label texel (0 without label rings), lod = l
+ *                (the texel passes through bit for bit: NaN with its payload, +-inf, -0.0 and subnormals included),
  *                v = (value - clim[0]) / (clim[1] - clim[0]);  v = powf(v, gamma) if gamma != 1;
  *                v = srgb2physical(v) if colorspace_srgb;  rgb = hsv_to_rgb(h, s, v) of colors[label % color_count];
  *                rgba = (rgb, opacity)                             (the march's shading without fog)
@@ -462,8 +484,11 @@ int  svr_slice(svr_ctx* ctx, const svr_slice_plane* plane, const svr_frame* fram
  * resident; the first LOD whose ROI holds it, giving value_k, label_k, lod_k).  Reduced over the HIT samples only:
  *     MAX / MIN  best = the first HIT sample; a later HIT sample replaces it iff value_k > best (MAX) or
  *                value_k < best (MIN).  Ties keep the lowest k; a NaN first HIT stays, a later NaN never wins.
+ *                IEEE comparisons: -0.0 and +0.0 tie (the lower k stays), +inf beats every finite value under MAX
+ *                and -inf under MIN.
  *                value, label, lod and depth are those of the chosen sample.
  *     MEAN       value = (the sum of the HIT values, accumulated in f32 in increasing k) / (float)hits;
+ *                a NaN sample, or +inf and -inf in one column, make it NaN; a sum that overflows stays infinite;
  *                label, lod and depth are those of the sample MAX would choose.
  *     depth      t_k * w_len of the chosen sample: the signed world offset from the centre plane (w_len = |w|, the
  *                f32 of its float64 norm, given by the caller), so svr_outline's depth test applies to slabs.
@@ -501,6 +526,7 @@ int  svr_slab(svr_ctx* ctx, const svr_slab_params* params, const svr_frame* fram
  *            for the step (svr_set_transfer_function):
  *              v   = (s - clim[0]) / (clim[1] - clim[0])
  *              x   = fminf(fmaxf(v * (float)(K-1), 0.0f), (float)(K-1))          (NaN -> 0)
+ *                                                              (fmaxf drops the NaN; +inf -> K-1, -inf and v < 0 -> 0)
  *              j   = min((int)x, K-2);  f = x - (float)j
  *              e_c = T[j].c + f * (T[j+1].c - T[j].c)                              c = r, g, b, a
  *   tint     color_by_label: q = hsv_to_rgb(h, s, 1.0f) of colors[lab % color_count];  e_rgb = e_rgb * q per component
@@ -543,10 +569,14 @@ int  svr_composite(svr_ctx* ctx, const svr_camera* cam, const svr_frame* frame, 
  *            first LOD l whose ROI holds (int)(d * scale_l) gives the value s (the ring's element converted to f32: u8
  *            and u16 exactly, unnormalised like lmip_threshold) and the label (0 without label rings).  A point that
  *            no LOD holds has no value and cannot hit.
- *   coarse   i = 0 .. nsteps-1 in order, iter = (float)i; the candidate is the first i with s >= iso_value.
+ *   coarse   i = 0 .. nsteps-1 in order, iter = (float)i; the candidate is the first i with s >= iso_value.  s is
+ *            signed (not |s|) and the comparison is IEEE: a NaN sample is never a candidate and is passed over, +inf
+ *            reaches every level, -inf only iso_value = -inf (which every sample but a NaN reaches).  Skipping by the
+ *            macro-cell maxima (of |s|, a NaN never wins: an all-NaN cell has maximum 0) changes no plane.
  *   refine   none when i == 0 or refine <= 1: the hit is at iter = (float)i.  Else k = 1 .. refine-1 in order,
  *            iter = (float)(i-1) + (float)k / (float)refine; the first with s >= iso_value is the hit, else iter =
- *            (float)i.  A linear search: sampling is nearest-texel, the field along a ray is a step function and a
+ *            (float)i (a refinement sample that is NaN fails >= like a coarse one).
+ *            A linear search: sampling is nearest-texel, the field along a ray is a step function and a
  *            bisection may miss the first crossing.
  *   gradient at the hit (coordinate c, data point d = c * size, LOD l that gave its value), central differences of one
  *            voxel of that LOD per axis: h_a = 1.0f / scale_l[a];  D(p) = the value the LOD cascade gives for the data
@@ -628,6 +658,10 @@ int  svr_iso(svr_ctx* ctx, const svr_camera* cam, const svr_frame* frame, const 
  *            c0  = c00 + f_y * (c10 - c00);     c1  = c01 + f_y * (c11 - c01)
  *            value = c0 + f_z * (c1 - c0)
  * At a voxel centre every f_a is 0 and the value is the nearest texel bit for bit (finite data).
+ * A corner that is not finite yields whatever these seven expressions yield, weights of 0 included: a NaN corner makes
+ * the value NaN at any weight (0 * NaN).  In a step a + f * (b - a), an infinite b gives that infinity for f > 0 and
+ * NaN at f == 0 (0 * inf); an infinite a gives NaN at every f (b - a is the other infinity: 0 * inf, or inf - inf);
+ * so do two infinities, equal or opposite.  The voxel-centre identity above therefore holds for finite cells only.
  * With SVR_INTERP_LINEAR the sample replaces the nearest texel, and nothing else in each definition changes, in:
  *   svr_slice      the value plane and the shading input.
  *   svr_slab       every sample's value_k; reductions, tie rules and depth are unchanged.

@@ -100,6 +100,10 @@ def _render(rings, M, vdim, mat, W, H, srgb, pick_id=None):
     hit_off = [np.zeros((H, W), f32) for _ in range(3)]
     hit_coord = [np.zeros((H, W), f32) for _ in range(3)]
     steps = np.zeros((H, W), np.uint32)
+    # Diagnostics only, returned apart under "census" and read by no output plane (tests/test_special_values.py counts
+    # what a scene holds with them): the first executed sample is NaN; NaN samples passed before anything was found
+    first_nan = np.zeros((H, W), bool)
+    nan_before = np.zeros((H, W), np.int32)
 
     def texel_index(coord, labels):
         """sample_vol / sample_segmentations_vol (sample_vol.wgsl:51-77) for arrays of coords."""
@@ -149,6 +153,9 @@ def _render(rings, M, vdim, mat, W, H, srgb, pick_id=None):
             contribution = w * np.abs(s)
             better = contribution > best[idx]
             best[idx] = np.where(better, contribution, best[idx])
+            nan_before[idx] += np.isnan(s)
+            if it == 0:
+                first_nan[idx] = np.isnan(s)
             for k_ in range(3):
                 hit_off[k_][idx] = np.where(better, off[k_], hit_off[k_][idx])
                 hit_coord[k_][idx] = np.where(better, coord[k_], hit_coord[k_][idx])
@@ -157,8 +164,9 @@ def _render(rings, M, vdim, mat, W, H, srgb, pick_id=None):
         with np.errstate(invalid="ignore", divide="ignore"):
             samp = np.where(found, num / den, f32(0.0)).astype(f32)
     while mip:
-        # MIP stated directly (not through the LMIP state machine): the largest |sample| of the whole ray,
-        # first occurrence; every fragment "finds" one (its first sample starts the running maximum)
+        # MIP stated directly (not through the LMIP state machine): the first occurrence of the largest |sample|
+        # among the ray's non-NaN samples (include/svr.h: a NaN neither starts nor raises a maximum); a ray with
+        # no such sample finds nothing and is a MISS
         act = frag & (it < nsteps)
         if not act.any():
             break
@@ -168,13 +176,17 @@ def _render(rings, M, vdim, mat, W, H, srgb, pick_id=None):
         s = texel_index(coord, labels=False)
         inten = np.abs(s)
         steps[idx] += 1
-        better = ~found[idx] | (inten > lmax[idx])
+        valid = ~np.isnan(inten)
+        better = valid & (~found[idx] | (inten > lmax[idx]))
         lmax[idx] = np.where(better, inten, lmax[idx])
         samp[idx] = np.where(better, s, samp[idx])
         for k in range(3):
             hit_off[k][idx] = np.where(better, off[k], hit_off[k][idx])
             hit_coord[k][idx] = np.where(better, coord[k], hit_coord[k][idx])
-        found[idx] = True
+        found[idx] |= valid
+        nan_before[idx] += ~valid & ~found[idx]
+        if it == 0:
+            first_nan[idx] = ~valid
         it += 1
     while not (mip or wavg):
         act = ~finished & (it < nsteps)
@@ -201,6 +213,9 @@ def _render(rings, M, vdim, mat, W, H, srgb, pick_id=None):
             hit_coord[k][idx] = np.where(take, coord[k], hit_coord[k][idx])
         found[idx] = was | first_hit
         finished[idx] = brk
+        nan_before[idx] += np.isnan(s) & ~found[idx]
+        if it == 0:
+            first_nan[idx] = np.isnan(s)
         it += 1
 
     flags = np.where(frag, np.where(found, 2, 1), 0).astype(np.uint8)
@@ -245,7 +260,8 @@ def _render(rings, M, vdim, mat, W, H, srgb, pick_id=None):
         fc = [f32(x) for x in mat["fog_color"]]
         rgba[hit] = np.stack([fc[0] * omf + r * fog, fc[1] * omf + g * fog, fc[2] * omf + b * fog,
                               np.full_like(r, f32(mat["opacity"]))], axis=-1)
-    out = dict(rgba=rgba, depth=depth, label=label, flags=flags, steps=steps)
+    out = dict(rgba=rgba, depth=depth, label=label, flags=flags, steps=steps,
+               census=dict(sample=np.where(found, samp, f32(0.0)).astype(f32), first_nan=first_nan, nan_before=nan_before))
     if pick_id is not None:                                           # fs_main.wgsl:89-92, pygfx pick_pack restated
         pick = np.zeros((H, W), np.uint64)
         if len(hit[0]):

@@ -226,20 +226,36 @@ def hold_both_to(ref, volume: SubVolume, camera, width: int, height: int, *, tol
     return rep
 
 
+def class_error(a, b) -> np.ndarray:
+    """|a - b| under the class rule every float comparison of the suite shares: a NaN meets any NaN (whatever its bits)
+    and an infinity the same infinity with error 0; a non-finite value against a finite one, or against the other
+    infinity, is an infinite error.  Two finite values give |a - b| in the arguments' own type, as before."""
+    a, b = np.asarray(a), np.asarray(b)
+    fa, fb = np.isfinite(a), np.isfinite(b)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = np.abs(a - b)
+        same = (np.isnan(a) & np.isnan(b)) | (~fa & ~fb & (a == b))
+    d = np.where(same, 0.0, d)
+    return np.where(~same & ~(fa & fb), np.inf, d)
+
+
+def same_bits_or_nan(a, b) -> np.ndarray:
+    """Per element: equal as bits, or a NaN on both sides (the bit pattern of an arithmetic NaN is not pinned)."""
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.shape == b.shape and a.dtype.kind == b.dtype.kind and a.dtype.itemsize == b.dtype.itemsize, (a.shape, a.dtype, b.shape, b.dtype)
+    if a.dtype.kind != "f":
+        return a == b
+    u = {4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
+    return (a.view(u) == b.view(u)) | (np.isnan(a) & np.isnan(b))
+
+
 def compare(res: RenderResult, ref) -> dict:
     """Compare a device render with an oracle result (numpy arrays with the same
     attribute names).  Integer planes must match exactly; float planes are reported
     as max abs / max relative-or-abs error."""
     rgba = res.rgba.cpu().numpy()
 
-    def err(a, b):
-        """|a - b| where a NaN on both sides counts as equal (pow of a negative base: a clim above the
-        sample with a fractional gamma gives NaN in the shader too) and a NaN on one side as infinite."""
-        na, nb = np.isnan(a), np.isnan(b)
-        with np.errstate(invalid="ignore"):
-            d = np.abs(a - b)
-        d = np.where(na & nb, 0.0, d)
-        return np.where(na ^ nb, np.inf, d)
+    err = class_error
 
     e_rgba = err(rgba, ref.rgba)
     out = {

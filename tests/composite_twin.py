@@ -17,7 +17,8 @@ def composite_twin(rings, matrices, size, material, table, width, height, alpha_
     volume_dimensions in shader order; ``table``: the K x 4 f32 device table; ``linear``: s of every sample is the
     linear sample (labels stay the nearest sample's); ``cut_planes``, ``cut_mode``: as svr_set_cut_planes takes them.
     Returns dict(rgba, depth, label, flags, steps, pick, first, best) for the output pixels of ``region`` (default: the
-    frame); ``first`` and ``best`` are the counters of the depth's and the label's sample (diagnostics).  ``census``:
+    frame); ``first`` and ``best`` are the counters of the depth's and the label's sample, ``saw_nan`` / ``saw_pinf`` / ``saw_below`` the
+    pixels with a contributing sample whose v is NaN / +inf / below 0 (diagnostics).  ``census``:
     also "census", the number of samples each LOD resolved (int64 [len(rings)]); nothing else changes."""
     with np.errstate(all="ignore"):
         return _composite(rings, matrices, size, material, np.asarray(table, f32), width, height, f32(alpha_cutoff),
@@ -39,6 +40,7 @@ def _composite(rings, M, size, mat, T, W, H, cutoff, tint, region, pick_id, cens
     steps = np.zeros(shape, np.uint32)
     alive = frag.copy()
     counts = np.zeros(len(rings), np.int64)
+    saw = {k: np.zeros(shape, bool) for k in ("nan", "pinf", "below")}     # diagnostics: a contributing sample of that class
     it = 0
     while True:
         act = alive & (it < nsteps)
@@ -53,6 +55,9 @@ def _composite(rings, M, size, mat, T, W, H, cutoff, tint, region, pick_id, cens
         idx = tuple(i[res] for i in idx)
         s, lab = s[res], lab[res]
         v = (s - clim0) / (clim1 - clim0)
+        saw["nan"][idx] |= np.isnan(v)
+        saw["pinf"][idx] |= v == np.inf
+        saw["below"][idx] |= v < 0
         xf = np.fmin(np.fmax(v * kmax, f32(0.0)), kmax)     # NaN -> 0
         j = np.minimum(xf.astype(np.int32), K - 2)
         f = xf - j.astype(f32)
@@ -90,7 +95,7 @@ def _composite(rings, M, size, mat, T, W, H, cutoff, tint, region, pick_id, cens
         label[h] = sample(rings, [cb[k] * size[k] for k in range(3)])[1]
         pick[h] = pick_word(cb, pick_id)
     out = dict(rgba=rgba, depth=depth, label=label, flags=flags_of(hit, frag), steps=steps, pick=pick, first=first,
-               best=best)
+               best=best, saw_nan=saw["nan"], saw_pinf=saw["pinf"], saw_below=saw["below"])
     if census:
         out["census"] = counts
     return out

@@ -1,8 +1,12 @@
-"""Shared helpers for the test-suite: fixtures of the reference's ring-buffer tests."""
+"""Shared helpers for the test-suite: fixtures of the reference's ring-buffer tests, and the float comparison rule."""
 import json
 import os
 
 import numpy as np
+
+# the class rule of every float comparison (NaN meets NaN, an infinity the same infinity, anything else non-finite is
+# an infinite error): written once, beside `testing.compare`, which cannot import from tests/
+from sub_volume_renderer_amd.testing import class_error, same_bits_or_nan  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
@@ -25,3 +29,16 @@ def slices(r):
 
 def as_pair(r):
     return (tuple(r[0]), tuple(r[1]))
+
+
+def assert_close(got, ref, tol, what=""):
+    """Every element within `tol` under the class rule; returns the largest error."""
+    err = class_error(got, ref)
+    worst = float(err.max(initial=0.0))
+    assert worst <= tol, (what, worst, int((err > tol).sum()))
+    return worst
+
+
+def assert_same_bits(got, ref, what=""):
+    bad = int((~same_bits_or_nan(got, ref)).sum())
+    assert bad == 0, (what, bad)

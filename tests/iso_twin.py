@@ -23,7 +23,8 @@ def iso_twin(rings, matrices, size, material, width, height, params=None, region
     S(iter) and D(p) are the linear sample (the label and the LOD of the hit stay the nearest sample's);
     ``cut_planes``, ``cut_mode``: as svr_set_cut_planes takes them.  Returns dict(rgba, depth, label, flags, steps,
     pick, normal, iter, cap) for the output pixels of ``region`` (default: the frame); ``iter`` is the refined float
-    counter of the hit (diagnostics), ``cap`` the index of the cutting plane on a cap hit (int32, -1 elsewhere).
+    counter of the hit (diagnostics), ``cap`` the index of the cutting plane on a cap hit (int32, -1 elsewhere),
+    ``nan_before`` the number of NaN samples the coarse search passed, ``gradient_finite`` whether a hit's G is finite.
     ``census``: also "census", the number of samples of the coarse search each LOD resolved (int64 [len(rings)]), and
     "hit_lod", the LOD that holds each hit (int32, -1 on non-hits); nothing else changes."""
     p = dict(DEFAULTS)
@@ -51,6 +52,7 @@ def _iso(rings, M, size, mat, W, H, p, region, pick_id, census, linear, planes, 
     cand = np.full(shape, -1, np.int64)
     searching = frag.copy()
     counts = np.zeros(len(rings), np.int64)
+    nan_before = np.zeros(shape, np.int64)                 # diagnostics: NaN samples of the coarse search before the hit
     it = 0
     while True:
         act = searching & (it < nsteps)
@@ -60,7 +62,8 @@ def _iso(rings, M, size, mat, W, H, p, region, pick_id, census, linear, planes, 
         s, _, lod = sample(rings, data([start[k][idx] + f32(it) * step[k][idx] for k in range(3)]), linear=linear)
         if census:
             counts += np.bincount(lod[lod >= 0], minlength=len(rings))
-        got = (lod >= 0) & (s >= iso) & ~rc.cut(it, idx)
+        got = (lod >= 0) & (s >= iso) & ~rc.cut(it, idx)             # NaN >= iso is false: a NaN sample is passed over
+        nan_before[idx] += np.isnan(s)
         at = tuple(i[got] for i in idx)
         cand[at] = it
         searching[at] = False
@@ -76,7 +79,8 @@ def _iso(rings, M, size, mat, W, H, p, region, pick_id, census, linear, planes, 
     cap = np.full(shape, -1, np.int32)
     hit_lod = np.full(shape, -1, np.int32)
     out = dict(rgba=rgba, depth=depth, label=label, flags=flags_of(hit, frag), steps=steps, pick=pick, normal=normal,
-               iter=iters, cap=cap, census=counts, hit_lod=hit_lod)
+               iter=iters, cap=cap, census=counts, hit_lod=hit_lod, nan_before=nan_before,
+               gradient_finite=np.ones(shape, bool))
     if not hit.any():
         return out
     h = np.nonzero(hit)
@@ -125,6 +129,7 @@ def _iso(rings, M, size, mat, W, H, p, region, pick_id, census, linear, planes, 
     zero = [np.zeros_like(w[0])] * 3
     v = _unit([-w[0], -w[1], -w[2]], zero)
     n = _unit([-G[0], -G[1], -G[2]], v)
+    out["gradient_finite"][h] = np.isfinite(G[0]) & np.isfinite(G[1]) & np.isfinite(G[2])
 
     # ---- caps: a hit whose predecessor was cut takes the cutting plane's normal, turned towards the viewer
     if len(rc):

@@ -268,3 +268,18 @@ def test_header_declares_the_composite_entry_points_within_abi_9():
     assert re.search(r"#define SVR_TF_MAX_ENTRIES 4096\b", header) and _native.TF_MAX_ENTRIES == 4096
     assert {"svr_set_transfer_function", "svr_composite"} <= set(_native.SIGNATURES)
     assert [n for n, _ in _native.CompositeParams._fields_] == ["alpha_cutoff", "color_by_label"]
+
+
+def test_table_entries_of_infinite_negative_and_out_of_range_samples():
+    """x = fminf(fmaxf(v * (K-1), 0), K-1): NaN and everything below clim[0] (-inf included) take entry 0, +inf and
+    everything above clim[1] entry K-1; the order of the two clamps matters only for NaN (fminf first would give K-1)."""
+    T = table((0.0, 0.0, 0.0), [0.0, 0.0, 0.0])
+    T[0], T[-1] = (0.8, 0.1, 0.2, 0.5), (0.0, 0.0, 1.0, 1.0)
+    first, last = f32((0.8, 0.1, 0.2)), f32((0.0, 0.0, 1.0))
+    for value, steps, rgb in ((np.nan, 7, first), (-np.inf, 7, first), (-3e38, 7, first), (-0.0, 7, first),
+                              (np.inf, 1, last), (3e38, 1, last), (1e6, 1, last)):
+        out = run([ring(np.full((N, N, N), value, np.float32))], T, 0.99)
+        assert (out["flags"] == HIT).all() and (out["steps"] == steps).all(), (value, out["steps"][0, 0])
+        np.testing.assert_allclose(out["rgba"][..., :3], np.broadcast_to(rgb, (FRAME, FRAME, 3)), atol=1e-6, err_msg=str(value))
+        assert np.isfinite(out["rgba"]).all() and np.isfinite(out["depth"]).all()
+        assert out["saw_nan"].all() == bool(np.isnan(value)) and out["saw_pinf"].all() == (value == np.inf)

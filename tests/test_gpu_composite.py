@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import assert_close
 from composite_twin import composite_twin, material_of, matrices_of
 from oracle import lmip
 from slice_twin import DISCARD, HIT, MISS
@@ -44,8 +45,7 @@ def check(res, ref, what):
         if k in got:
             assert np.array_equal(got[k], ref[k]), (what, k, int((got[k] != ref[k]).sum()))
     for k in ("rgba", "depth"):
-        err = np.abs(got[k].astype(np.float64) - ref[k])
-        assert not np.isnan(err).any() and float(err.max(initial=0.0)) <= TOL, (what, k, float(np.nanmax(err)))
+        assert_close(got[k].astype(np.float64), ref[k], TOL, (what, k))
 
 
 def composite_on(vol, tf, cutoff, tint):

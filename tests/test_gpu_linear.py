@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import composite_twin
+from helpers import class_error, same_bits_or_nan
 import iso_twin
 from linear_twin import composite_linear, iso_linear, slab_of_spec, slice_of_spec
 from oracle import lmip
@@ -31,17 +32,14 @@ TOL = 1e-4          # the project's tolerance for rgba, depth and normal
 
 def check_planes(got, ref, what, exact, close):
     for k in exact:
-        a = got[k].view(np.uint32) if got[k].dtype == np.float32 else got[k]
-        b = ref[k].view(np.uint32) if ref[k].dtype == np.float32 else ref[k]
-        bad = int((a != b).sum())
-        print(what, k, "mismatching pixels", bad, "of", a.size)
+        bad = int((~same_bits_or_nan(got[k], ref[k])).sum())            # floats as bits, a NaN meeting any NaN
+        print(what, k, "mismatching pixels", bad, "of", got[k].size)
         assert bad == 0, (what, k, bad)
     for k in close:
         a, b = got[k].astype(np.float64), ref[k].astype(np.float64)
-        both_nan = np.isnan(a) & np.isnan(b)
-        err = np.where(both_nan, 0.0, np.abs(a - b))
-        print(what, k, "max abs error", float(np.nanmax(err)) if err.size else 0.0)
-        assert not np.isnan(err).any() and float(err.max(initial=0.0)) <= TOL, (what, k, float(np.nanmax(err)))
+        err = class_error(a, b)
+        print(what, k, "max abs error", float(err.max(initial=0.0)))
+        assert float(err.max(initial=0.0)) <= TOL, (what, k, float(err.max(initial=0.0)))
 
 
 def check_slice(res, ref, what):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import assert_close, assert_same_bits
 from oracle import lmip
 from slab_twin import twin_of_spec
 from slice_twin import DISCARD, HIT
@@ -33,14 +34,8 @@ def host(res):
 def check(res, ref, what):
     got = host(res) if isinstance(res, SliceResult) else res
     for k in PLANES:
-        a = got[k].view(np.uint32) if k in ("value", "depth") else got[k]
-        b = ref[k].view(np.uint32) if k in ("value", "depth") else ref[k]
-        assert np.array_equal(a, b), (what, k, int((a != b).sum()))
-    a, b = got["rgba"], ref["rgba"]
-    both_nan = np.isnan(a) & np.isnan(b)
-    with np.errstate(invalid="ignore"):
-        err = np.where(both_nan, 0.0, np.abs(a - b))
-    assert not np.isnan(err).any() and float(err.max(initial=0.0)) <= RGBA_TOL, (what, float(np.nanmax(err)))
+        assert_same_bits(got[k], ref[k], (what, k))                    # value and depth as bits, a NaN meeting any NaN
+    assert_close(got["rgba"], ref["rgba"], RGBA_TOL, what)
 
 
 def slabs(p, step):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import assert_close, assert_same_bits
 from oracle import lmip
 from slice_twin import DISCARD, HIT, MISS, twin_of_spec
 from sub_volume_renderer_amd import FrameRegion, RenderResult, SliceResult, SubVolume, _native as N, compose, outline, testing
@@ -30,13 +31,8 @@ def host(res):
 def check(res, ref, what):
     got = host(res) if isinstance(res, SliceResult) else res
     for k in PLANES:
-        assert np.array_equal(got[k].view(np.uint32) if k == "value" else got[k],
-                              ref[k].view(np.uint32) if k == "value" else ref[k]), (what, k, int((got[k] != ref[k]).sum()))
-    a, b = got["rgba"], ref["rgba"]
-    both_nan = np.isnan(a) & np.isnan(b)
-    with np.errstate(invalid="ignore"):
-        err = np.where(both_nan, 0.0, np.abs(a - b))
-    assert not np.isnan(err).any() and float(err.max(initial=0.0)) <= RGBA_TOL, (what, float(np.nanmax(err)))
+        assert_same_bits(got[k], ref[k], (what, k))                    # value as bits, a NaN meeting any NaN
+    assert_close(got["rgba"], ref["rgba"], RGBA_TOL, what)
     assert not got["depth"].any(), what
 
 

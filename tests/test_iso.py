@@ -269,3 +269,40 @@ def test_header_declares_svr_iso_within_abi_9():
     assert "svr_iso" in _native.SIGNATURES
     assert int(re.search(r"#define SVR_ISO_MAX_REFINE (\d+)", header).group(1)) == _native.ISO_MAX_REFINE
     assert int(re.search(r"#define SVR_ISO_MAX_SHININESS_LOG2 (\d+)", header).group(1)) == _native.ISO_MAX_SHININESS_LOG2
+
+
+def test_nan_and_infinite_samples_against_negative_zero_and_infinite_levels():
+    """s >= iso_value on the signed sample, IEEE: a NaN sample is passed over at every level (-inf included), +inf
+    reaches every level, -inf only the level -inf; an all-NaN block is a MISS that runs every step."""
+    spec = spec_for("+z")
+    first_x = int(np.ceil(10 * NSTEPS / N))                       # the first sample in voxel 10 along the ray
+    for fill, dense, level, want in (
+            (np.nan, 5.0, -40.0, "late"), (np.nan, 5.0, 0.0, "late"), (np.nan, 5.0, float("-inf"), "late"),
+            (np.nan, -np.inf, float("-inf"), "late"), (np.nan, -np.inf, -1e30, "miss"), (np.nan, np.inf, 3e38, "late"),
+            (-np.inf, np.nan, float("-inf"), "first"), (-50.0, np.nan, -40.0, "miss"), (np.nan, np.nan, float("-inf"), "miss"),
+            (-0.0, 7.0, 0.0, "first")):
+        d = np.full((N, N, N), fill, np.float32)
+        d[10:] = dense                                            # [z, y, x]: the +z rays meet `dense` from voxel 10 on
+        out = run([ring(d)], spec, iso_value=level, refine=0)
+        what = (fill, dense, level)
+        if want == "miss":
+            assert (out["flags"] == MISS).all() and (out["steps"] == NSTEPS).all(), what
+        else:
+            assert (out["flags"] == HIT).all(), what
+            assert (out["steps"] == (1 if want == "first" else first_x + 1)).all(), (what, out["steps"][0, 0], first_x)
+        assert np.isfinite(out["rgba"]).all() and np.isfinite(out["normal"]).all(), what      # n falls back to v
+
+
+def test_a_refinement_sample_that_is_nan_is_passed_over():
+    d = np.zeros((N, N, N), np.float32)
+    d[10:] = 200.0
+    spec = spec_for("+z")
+    plain = run([ring(d)], spec, iso_value=100.0, refine=4)
+    d[10] = np.nan                                                # the layer the refinement would have found first
+    d[9] = 0.0
+    out = run([ring(d)], spec, iso_value=100.0, refine=4)
+    assert (out["flags"] == HIT).all() and (plain["flags"] == HIT).all()
+    # the coarse candidate moves to the first sample in voxel 11 and the sub-samples before it (in the NaN layer) fail
+    first_11 = int(np.ceil(11 * NSTEPS / N))
+    assert (out["steps"] == first_11 + 1).all() and (out["iter"] == np.float32(first_11)).all(), (out["steps"][0, 0], out["iter"][0, 0])
+    assert (plain["iter"] < out["iter"]).all()

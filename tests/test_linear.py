@@ -242,3 +242,29 @@ def test_svr_set_interpolation_is_declared_bound_and_exported():
     # no existing struct gained a field
     assert ctypes.sizeof(_native.SlicePlane) == (16 + 3 * 4) * 4 and ctypes.sizeof(_native.SliceOutputs) == 6 * 8
     assert ctypes.sizeof(_native.CompositeParams) == 8 and ctypes.sizeof(_native.SlabParams) == (16 + 3 * 4) * 4 + 24
+
+
+def test_non_finite_corners_give_what_the_stated_blend_gives():
+    """a + f * (b - a), x first, then y, then z (include/svr.h): a NaN corner at any weight -> NaN; an infinite `b` ->
+    that infinity for f > 0 and NaN at f == 0 (0 * inf); an infinite `a` -> NaN at every f.  Only the corner that is the
+    `b` of all three steps (v111) can therefore pass an infinity on, and only when every f is above 0."""
+    inf, nan, big = np.inf, np.nan, 3e38
+    base = (10, 20, 30)                                        # v000 of the cell, (x, y, z)
+    cases = [  # {corner offset (dx, dy, dz): value}, fractions (fx, fy, fz), expected
+        ({(1, 1, 1): inf}, (0.5, 0.5, 0.5), inf), ({(1, 1, 1): -inf}, (0.25, 0.5, 0.75), -inf),
+        ({(1, 1, 1): inf}, (0.0, 0.5, 0.5), nan), ({(1, 1, 1): inf}, (0.5, 0.5, 0.0), nan),      # weight 0 meets an infinity
+        ({(1, 1, 1): nan}, (0.0, 0.0, 0.0), nan), ({(0, 1, 0): nan}, (0.5, 0.0, 0.5), nan),      # weight 0 meets a NaN
+        ({(0, 0, 0): inf}, (0.5, 0.5, 0.5), nan), ({(0, 0, 0): inf}, (0.0, 0.0, 0.0), nan),      # an infinite `a`
+        ({(1, 0, 0): inf}, (0.5, 0.5, 0.5), nan),                                                # `b` in x, then `a` in y
+        ({(0, 1, 1): inf, (1, 1, 1): -inf}, (0.5, 0.5, 0.5), nan), ({(0, 1, 1): inf, (1, 1, 1): inf}, (0.5, 0.5, 0.5), nan),
+        ({(0, 1, 1): -big, (1, 1, 1): big}, (0.5, 0.5, 0.5), inf),                               # 3e38 - -3e38 overflows
+        ({(0, 0, 0): -0.0, (1, 0, 0): -0.0}, (0.5, 0.0, 0.0), 0.0)]            # -0.0 + 0.5 * (+0.0): the zero's sign goes
+    for corners, f, want in cases:
+        content = np.full((N, N, N), 2.0, f32)
+        for (dx, dy, dz), value in corners.items():
+            content[base[2] + dz, base[1] + dy, base[0] + dx] = value
+        ring = ring_of(content, (0, 0, 0), (N, N, N), (N, N, N))
+        value, _, lod = linear_sample([ring], [np.array([base[k] + f[k] + 0.5], f32) for k in range(3)])
+        got = f32(value[0])
+        assert lod[0] == 0
+        assert (np.isnan(want) and np.isnan(got)) or got.view(np.uint32) == f32(want).view(np.uint32), (corners, f, got)

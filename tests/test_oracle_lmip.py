@@ -432,3 +432,87 @@ def test_orthographic_single_voxel_covers_exactly_the_predicted_pixel():
         want_col, want_row = 15 - off[2], 16 - off[1]
         assert rows.tolist() == [want_row] and cols.tolist() == [want_col], (off, rows, cols)
         assert r.label[want_row, want_col] == 7
+
+
+# ---- signed and non-finite voxels (tests/special_scenes.py; the rules are in include/svr.h at svr_material) ----------
+def _rel(a, b):
+    """The class rule's error (tests/helpers.py) divided by max(1, |b|): the file's absolute 2e-6 for every value up
+    to 1, relative above it.  The special scenes shade +-3e38 to values near 1e36, where one ulp (1e29) of libm's powf
+    is far more than 2e-6 and an absolute bound cannot hold between two correct restatements."""
+    from helpers import class_error
+
+    return class_error(a, b) / np.maximum(1.0, np.abs(np.nan_to_num(b)))
+
+
+@pytest.mark.parametrize("mode", ["lmip+20", "lmip-30", "lmip0", "lmip+inf", "mip", "wavg"])
+@pytest.mark.parametrize("view", ["outside", "inside", "+x", "+y", "+z"])
+def test_restatements_agree_on_signed_and_non_finite_voxels(view, mode):
+    import special_scenes as S
+
+    shading = list(S.SHADING)[(list(S.MARCH).index(mode) + S.VIEWS.index(view)) % len(S.SHADING)]
+    spec = S.march_spec(view, mode, shading)
+    a = lmip.render_spec(spec, nthreads=2, pick_id=77)
+    b = lmip_numpy.render_spec(spec, pick_id=77)
+    for plane in ("flags", "label", "steps", "pick"):
+        np.testing.assert_array_equal(getattr(a, plane), b[plane], err_msg=plane)
+    assert float(_rel(a.rgba, b["rgba"]).max()) <= 2e-6
+    assert float(_rel(a.depth, b["depth"]).max()) <= 2e-6
+    assert (~np.isfinite(a.rgba)).any(-1).sum() > 100               # the comparison met NaN and infinite colours
+
+
+def test_mip_with_nan_voxels_follows_the_header_in_both_restatements():
+    """A 32^3, 3-LOD, 48 x 40 scene with 5 % of the voxels NaN: a NaN sample neither starts nor raises the maximum
+    (MIP is LMIP with threshold -inf: NaN >= -inf is false).  Before the numpy restatement said so it let a ray's first
+    sample start the maximum even when NaN, and the two differed on 34 labels of 1,650 fragments."""
+    rng = np.random.default_rng(5)
+    pairs = []
+    for l in range(3):
+        n = 32 >> l
+        d = rng.normal(0.0, 40.0, (n, n, n)).astype(np.float32)
+        d[rng.random((n, n, n)) < 0.05] = np.nan
+        pairs.append((d, rng.integers(0, 2**32, (n, n, n), dtype=np.uint64).astype(np.uint32)))
+    spec = testing.synthetic_spec(32, 48, 40, pairs=pairs, chunk_shapes=[(8, 8, 8), (4, 4, 4), (2, 2, 2)],
+                                  ring_shapes=[(2, 2, 2), (4, 4, 4), (8, 8, 8)])
+    spec.material.update(render_mode="mip", clim=(-100.0, 100.0))
+    a = lmip.render_spec(spec, nthreads=2)
+    b = lmip_numpy.render_spec(spec)
+    assert (b["census"]["first_nan"] & (b["flags"] == 2)).sum() >= 30         # rays whose first sample is NaN, and that still hit
+    for plane in ("flags", "label", "steps"):
+        np.testing.assert_array_equal(getattr(a, plane), b[plane], err_msg=plane)
+    assert float(_rel(a.rgba, b["rgba"]).max()) <= 2e-6 and not np.isnan(b["census"]["sample"]).any()
+
+
+@pytest.mark.parametrize("view", ["+x", "+y", "+z"])
+def test_axis_views_of_the_special_scene_show_their_voxel_columns(view):
+    """Known answers from the columns alone (special_scenes.column_answers, lmip_walk): MIP is the first argmax of |v|
+    over the non-NaN voxels, LMIP starts at the first voxel with |v| >= threshold and walks on by the fall-off rule
+    restated in scalar Python, all-NaN columns are MISS; label and depth are the winner's."""
+    import ortho_scenes as ortho
+    import special_scenes as S
+
+    for mode in ("mip", "lmip+20", "lmip-30"):
+        spec = S.march_spec(view, mode)
+        orac = lmip.oracle_volume(spec)
+        thr = spec.material["lmip_threshold"]
+        ka = S.column_answers(spec, orac, "mip" if mode == "mip" else "first", thr)
+        J, (iu, iv) = ka["judged"], ka["columns"]
+        assert J.all()
+        lo, hi = S.depth_bounds(spec, np.maximum(ka["index"], 0), ka["axis"])
+        for r in (lmip.render_spec(spec, vol=orac), lmip_numpy.render_spec(spec)):
+            r = r if isinstance(r, dict) else vars(r)
+            np.testing.assert_array_equal(r["flags"], ka["flags"])
+            if mode == "mip":
+                hit = ka["flags"] == 2
+                np.testing.assert_array_equal(r["label"][hit], ka["label"][hit])
+                assert np.all(r["depth"][hit] >= lo[hit] - 1e-6) and np.all(r["depth"][hit] <= hi[hit] + 1e-6)
+                if "census" in r:
+                    np.testing.assert_array_equal(r["census"]["sample"][hit].view(np.uint32), ka["value"][hit].view(np.uint32))
+                continue
+            for j, i in list(zip(*np.nonzero(J)))[::37]:
+                col = ortho.column_of(ka["val_xyz"], ka["axis"], 1.0, iu[j, i], iv[j, i])
+                win, steps = S.lmip_walk(col, thr, 0.5, 10)
+                assert steps == r["steps"][j, i] and (r["flags"][j, i] == 2) == (win >= 0), (view, mode, j, i)
+                if win >= 0:
+                    assert r["label"][j, i] == ortho.column_of(ka["lab_xyz"], ka["axis"], 1.0, iu[j, i], iv[j, i])[win]
+                    wlo, whi = S.depth_bounds(spec, np.array(win), ka["axis"])          # the depth of the winner's voxel
+                    assert wlo - 1e-6 <= r["depth"][j, i] <= whi + 1e-6, (view, mode, j, i)

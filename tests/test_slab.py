@@ -240,3 +240,23 @@ def test_svr_slab_is_declared_bound_and_exported():
     for name, value in (("SVR_SLAB_MAX", 0), ("SVR_SLAB_MIN", 1), ("SVR_SLAB_MEAN", 2), ("SVR_SLAB_MAX_SAMPLES", 4096)):
         assert int(re.search(rf"#define {name}\s+(\d+)", text).group(1)) == value
     assert _native.SLAB_MODES == {"max": 0, "min": 1, "mean": 2} and _native.SLAB_MAX_SAMPLES == 4096
+
+
+def test_infinities_overflow_and_signed_zeros_in_a_column():
+    """Hand-written answers for what a float ring may hold: IEEE comparisons and plain f32 sums (include/svr.h)."""
+    inf, nan, big = np.float32(np.inf), np.float32(np.nan), np.float32(3e38)
+    cases = [  # column, mode, expected value, chosen k (= label)
+        ([1, inf, 7, inf], "max", inf, 1), ([1, inf, 7], "min", 1, 0), ([1, -inf, 7, -inf], "min", -inf, 1),
+        ([-inf, -5, -inf], "max", -5, 1), ([inf, inf], "min", inf, 0),
+        ([1, inf, 7], "mean", inf, 1), ([-inf, 2, 3], "mean", -inf, 2), ([2, inf, -inf, 5], "mean", nan, 1),
+        ([0.0, -0.0, 0.0], "max", 0.0, 0), ([-0.0, 0.0, -0.0], "min", -0.0, 0), ([-0.0, -0.0], "mean", 0.0, 0),          # (the sum starts from +0.0)
+        ([big, big, 1], "mean", inf, 0), ([big, -big, big], "mean", np.float32(big / np.float32(3)), 0),
+        ([big, big, -big, -big], "mean", inf, 0),                                  # inf - 3e38 - 3e38 stays inf
+        ([np.float32(1e-41), 0.0], "max", np.float32(1e-41), 0), ([nan, inf], "max", nan, 0), ([inf, nan], "mean", nan, 0)]
+    for column, mode, value, k in cases:
+        out = run_column(column, mode)
+        got = out["value"][0, 0]
+        assert (out["flags"] == HIT).all()
+        assert np.float32(got).view(np.uint32) == np.float32(value).view(np.uint32) or (np.isnan(value) and np.isnan(got)), \
+            (column, mode, got)
+        assert (out["label"] == k).all(), (column, mode, out["label"][0, 0])

@@ -189,3 +189,19 @@ def test_svr_slice_is_declared_bound_and_exported():
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), "svr_slice")
     assert int(re.search(r"#define SVR_ABI_VERSION (\d+)", text).group(1)) == 9
     assert ctypes.sizeof(_native.SlicePlane) == (16 + 3 * 4) * 4 and ctypes.sizeof(_native.SliceOutputs) == 6 * 8
+
+
+def test_a_slice_passes_every_float_through_bit_for_bit():
+    """value is the texel itself (include/svr.h): NaN with its payload, +-inf, -0.0, a subnormal and +-3e38 arrive as
+    their bits; the rgba of each follows from the stated shading chain."""
+    from slice_twin import material_of, slice_twin
+
+    bits = np.array([0x7FC00000, 0xFFC00001, 0x7F800000, 0xFF800000, 0x80000000, 0x00001BE0, 0x7F61B1E6, 0xFF61B1E6], np.uint32)
+    d = np.resize(bits, (8, 8, 8)).view(np.float32).copy()
+    ring = dict(density=d, labels=np.zeros((8, 8, 8), np.uint32), offset=(0, 0, 0), shape=(8, 8, 8), scale=(1.0, 1.0, 1.0))
+    out = slice_twin([ring], np.eye(4), (8, 8, 8), (3.5, 3.5, 2.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), 8, 8, material_of({}))
+    assert (out["flags"] == HIT).all()
+    np.testing.assert_array_equal(out["value"].view(np.uint32), d[2].view(np.uint32))
+    v = out["value"]
+    assert np.isnan(out["rgba"][np.isnan(v)][:, :3]).all() and (out["rgba"][..., 3] == 1.0).all()
+    assert np.isinf(out["rgba"][v == np.inf][:, :3]).any(-1).all()
