@@ -103,6 +103,20 @@ class Outputs(C.Structure):
         ("pick_id", C.c_uint32),
     ]
 
+    @classmethod
+    def of(cls, res, *, steps=False, pick=False, pick_id=0):
+        """The struct over the planes of a render result: ``rgba``, and ``depth`` / ``label`` / ``flags`` where the
+        result holds them; ``steps`` and ``pick`` only when asked for and present (NULL otherwise)."""
+        ob = cls()
+        ob.rgba = res.rgba.data_ptr()
+        for name in ("depth", "label", "flags"):
+            t = getattr(res, name)
+            setattr(ob, name, t.data_ptr() if t is not None else None)
+        ob.steps = res.steps.data_ptr() if (steps and res.steps is not None) else None
+        ob.pick = res.pick.data_ptr() if (pick and res.pick is not None) else None   # the `write_pick` shader variant
+        ob.pick_id = pick_id
+        return ob
+
 
 class ComposeParams(C.Structure):
     _fields_ = [("bg_bottom", C.c_float * 4), ("bg_top", C.c_float * 4), ("srgb_encode", C.c_int32)]
@@ -131,6 +145,15 @@ class SlicePlane(C.Structure):
 
 class SliceOutputs(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("rgba", "depth", "label", "flags", "value", "lod")]
+
+    @classmethod
+    def of(cls, res):
+        """The struct over the planes of a slice / slab result; a plane the result leaves out (None) is NULL."""
+        ob = cls()
+        for name, _ in cls._fields_:
+            t = getattr(res, name)
+            setattr(ob, name, t.data_ptr() if t is not None else None)
+        return ob
 
 
 class SlabParams(C.Structure):

@@ -788,14 +788,7 @@ class SubVolume(_HasWorld):
         if cached is not None and cached[0] is res:
             ob = cached[1]
         else:
-            ob = N.Outputs()
-            ob.rgba = res.rgba.data_ptr()
-            ob.depth = res.depth.data_ptr() if res.depth is not None else None
-            ob.label = res.label.data_ptr() if res.label is not None else None
-            ob.flags = res.flags.data_ptr() if res.flags is not None else None
-            ob.steps = res.steps.data_ptr() if (count_steps and res.steps is not None) else None
-            ob.pick = res.pick.data_ptr() if (pick and res.pick is not None) else None   # the `write_pick` shader variant
-            ob.pick_id = self.id & 0xFFFFFFFF
+            ob = N.Outputs.of(res, steps=count_steps, pick=pick, pick_id=self.id & 0xFFFFFFFF)
             if len(self._ob_cache) > 8:
                 self._ob_cache.clear()
             self._ob_cache[okey] = (res, ob)
@@ -1000,11 +993,7 @@ class SubVolume(_HasWorld):
 
     @staticmethod
     def _plane_ob(res):
-        ob = N.SliceOutputs()
-        for name in ("rgba",) + tuple(n for n, _ in _SLICE_PLANES):
-            t = getattr(res, name)
-            setattr(ob, name, t.data_ptr() if t is not None else None)
-        return ob
+        return N.SliceOutputs.of(res)
 
     def _plane_stream(self, stream):
         import torch

@@ -4,8 +4,8 @@ the bench's workload) seen from camera K1, for two transfer functions:
   a  faint: alpha <= 0.02 over the whole range, cutoff 1.0 — no ray terminates early, so every ray visits every sample
      (the count is checked against the instrumented march's steps in full LMIP mode, the same rays);
   b  opaque: alpha 0 below 0.3 of the range, rising to 1 at 0.6, cutoff 0.99 — rays stop at the first dense structure.
-Called through the C ABI with prebuilt argument structs (steps = NULL: the production call), timed as
-tools/slab_time.py times slabs:
+Called through the C ABI with prebuilt argument structs (steps = NULL: the production call), timed with
+the held windows of tools/timing.py:
   call_ms  HIP events around back-to-back calls;
   gpu_ms   the same calls queued behind a sleep kernel (GPU time per call, free of host pacing).
 Per case also the samples the kernel visits (the sum of the steps plane of one render with count_steps=True) and
@@ -17,13 +17,13 @@ usage: python tools/composite_time.py [--case a|b|all] [--storage native|float32
        python tools/composite_time.py --stats DIR          (no GPU needed: the composite kernels of DIR's *kernel_stats.csv)
 """
 import argparse
-import csv
-import glob
 import json
 import os
 import sys
 
 import numpy as np
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -40,14 +40,8 @@ def transfer_functions():
 
 
 def stats(path):
-    for name in sorted(glob.glob(os.path.join(path, "**", "*kernel_stats.csv"), recursive=True)):
-        with open(name) as f:
-            for row in csv.DictReader(f):
-                if "composite" in row.get("Name", ""):
-                    print(json.dumps({"file": os.path.relpath(name, path), "kernel": row["Name"][:80],
-                                      "calls": int(row["Calls"]), "average_ms": round(float(row["AverageNs"]) / 1e6, 4),
-                                      "min_ms": round(float(row["MinNs"]) / 1e6, 4),
-                                      "max_ms": round(float(row["MaxNs"]) / 1e6, 4)}))
+    for row in timing.kernel_stats(path, ("composite",), 80):
+        print(json.dumps(row))
 
 
 def main():
@@ -57,8 +51,7 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--boxes", type=int, default=3)
     ap.add_argument("--volume-n", type=int, default=1024)
-    ap.add_argument("--interpolation", default="nearest", choices=("nearest", "linear", "both"),
-                    help="svr_set_interpolation mode of the timed calls; both: nearest and linear alternate, case by case")
+    timing.add_interpolation_argument(ap)
     ap.add_argument("--cut", default="none", choices=("none", "half", "wedge", "all-cases"),
                     help="svr_set_cut_planes state of the timed calls (tools/cut_cases.py: planes through the camera's focus "
                          "that open the side towards the camera); all-cases: none, half and wedge alternate, case by case")
@@ -71,35 +64,16 @@ def main():
 
     import torch
 
-    import bench
     import cut_cases
-    from sub_volume_renderer_amd import _native as N, synth, testing
+    from sub_volume_renderer_amd import _native as N
 
     if not torch.cuda.is_available():
         raise SystemExit("composite_time.py needs a GPU")
     dev = torch.device("cuda", 0)
     n_vol, W, H = args.volume_n, 1920, 1080
-    pairs = [synth.volume(n_vol, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
-    torch.cuda.synchronize()
     stream = torch.cuda.current_stream(dev)
     lib = N.lib()
-
-    def window(calls, hold_cycles=0):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        if hold_cycles:
-            torch.cuda._sleep(hold_cycles)
-        a.record(stream)
-        calls()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b) / 1e3
-
-    probe = 10_000_000
-    per_cycle = window(lambda: torch.cuda._sleep(probe)) / probe
-
-    spec = bench.config2_spec(n_vol, W, H, "K1", pairs)
-    spec.ring_storage = args.storage
-    scene = testing.build(spec)
+    spec, scene = timing.c2_scene(n_vol, W, H, "K1", args.storage)
     vol, cam = scene.volume, scene.camera
     m = vol.material
     print(json.dumps({"storage": vol._rings.density_storage, "frame": [W, H], "volume_n": n_vol, "camera": "K1"}), flush=True)
@@ -124,24 +98,17 @@ def main():
             vol._push_transfer_function()
             cb, fb = vol.camera_block(cam), vol.frame_block(W, H, None)
             cp = N.CompositeParams(cutoff, 0)
-            ob = N.Outputs()
-            ob.rgba, ob.depth, ob.label, ob.flags = (getattr(res, k).data_ptr() for k in ("rgba", "depth", "label", "flags"))
-            ob.steps, ob.pick, ob.pick_id = None, None, vol.id
+            ob = N.Outputs.of(res, pick_id=vol.id)
             argv = (handle, C.byref(cb), C.byref(fb), C.byref(cp), C.byref(ob), C.c_void_p(stream.cuda_stream))
 
-            def calls(k=args.calls):
-                for _ in range(k):
-                    N.check(lib.svr_composite(*argv), "svr_composite")
+            def one():
+                N.check(lib.svr_composite(*argv), "svr_composite")
 
-            for interp in (("nearest", "linear") if args.interpolation == "both" else (args.interpolation,)):
+            for interp in timing.interpolations(args.interpolation):
                 # (samples and hit_pixels are the nearest render's: the rays are the same, linear values end some earlier or later)
                 N.check(lib.svr_set_interpolation(handle, N.INTERPOLATIONS[interp]), "svr_set_interpolation")
                 N.check(cut_cases.push(lib, handle, planes, mode, N.CUT_MODES), "svr_set_cut_planes")
-                calls(5)
-                call_s = [window(calls) / args.calls for _ in range(args.boxes)]
-                hold = int(max(4.0 * max(call_s) * args.calls, 0.02) / per_cycle)
-                gpu_s = [window(calls, hold) / args.calls for _ in range(args.boxes)]
-                torch.cuda.synchronize()
+                call_s, gpu_s = timing.held(one, args.calls, args.boxes, warmup=5)
                 gpu = float(np.median(gpu_s))
                 row = {"case": case, "storage": vol._rings.density_storage, "interpolation": interp, "cut": cut, "table_entries": tf.size,
                        "alpha_cutoff": cutoff, "call_ms": round(float(np.median(call_s)) * 1e3, 4), "gpu_ms": round(gpu * 1e3, 4),

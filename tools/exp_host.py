@@ -3,13 +3,10 @@
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import bench
-from sub_volume_renderer_amd import FrameRegion, synth, testing
-dev = torch.device("cuda", 0)
+import timing
+from sub_volume_renderer_amd import FrameRegion
 n, W, H = 1024, 1920, 1080
-pairs = [synth.volume(n, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
-spec = bench.config2_spec(n, W, H, "K1", pairs)
-scene = testing.build(spec); vol, cam = scene.volume, scene.camera
+scene = timing.c2_scene(n, W, H, "K1")[1]; vol, cam = scene.volume, scene.camera
 vol.material.lmip_threshold = float("inf")
 for world in (1, 2, 4, 8):
     reg = FrameRegion.stripes(W, H, 0, world, 16) if world > 1 else FrameRegion.full(W, H)

@@ -8,16 +8,14 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import bench  # noqa: E402
-from sub_volume_renderer_amd import synth, testing  # noqa: E402
+import timing  # noqa: E402
 from sub_volume_renderer_amd.distributed import TiledFrame  # noqa: E402
 
 camname = sys.argv[1] if len(sys.argv) > 1 else "K1"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 200
 n, W, H = 1024, 1920, 1080
 dev = torch.device("cuda", 0)
-pairs = [synth.volume(n, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
-scene = testing.build(bench.config2_spec(n, W, H, camname, pairs))
+scene = timing.c2_scene(n, W, H, camname)[1]
 vol, cam = scene.volume, scene.camera
 for mode in ("full", "lmip"):
     vol.material.lmip_threshold = float("inf") if mode == "full" else 127.5

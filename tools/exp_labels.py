@@ -8,15 +8,15 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import bench  # noqa: E402
-from sub_volume_renderer_amd import _native as N, synth, testing  # noqa: E402
+import timing  # noqa: E402
+from sub_volume_renderer_amd import _native as N  # noqa: E402
 
 
 def time_ms(vol, cam, W, H, iters=20):
     vol.prepare()
     cb, fb = vol.camera_block(cam), vol.frame_block(W, H, None)
     r = vol.render(cam, W, H)
-    ob = N.Outputs(); ob.rgba = r.rgba.data_ptr(); ob.depth = r.depth.data_ptr(); ob.label = r.label.data_ptr(); ob.flags = r.flags.data_ptr()
+    ob = N.Outputs.of(r)
     ms = C.c_float(0)
     for it in (5, iters):
         N.check(N.lib().svr_time_render(vol._rings.handle, C.byref(cb), C.byref(fb), C.byref(ob), it, C.byref(ms)), "time")
@@ -24,12 +24,10 @@ def time_ms(vol, cam, W, H, iters=20):
 
 
 n, W, H = 1024, 1920, 1080
-dev = torch.device("cuda", 0)
-pairs = [synth.volume(n, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
+pairs = timing.c2_pairs(n, torch.device("cuda", 0))
 for camname in ("K1", "K2"):
     for labelled in (True, False):
-        spec = bench.config2_spec(n, W, H, camname, pairs if labelled else [(d, None) for d, _ in pairs])
-        scene = testing.build(spec)
+        scene = timing.c2_scene(n, W, H, camname, pairs=pairs if labelled else [(d, None) for d, _ in pairs])[1]
         vol, cam = scene.volume, scene.camera
         for mode, thr in (("lmip", 127.5), ("full", float("inf")), ("all-hit", 1.0)):
             vol.material.lmip_threshold = thr

@@ -8,16 +8,14 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import bench  # noqa: E402
-from sub_volume_renderer_amd import _native as N, synth, testing  # noqa: E402
+import timing  # noqa: E402
+from sub_volume_renderer_amd import _native as N  # noqa: E402
 from sub_volume_renderer_amd._wobject import FrameRegion  # noqa: E402
 
 camname = sys.argv[1] if len(sys.argv) > 1 else "K1"
 variant = int(sys.argv[2], 0) if len(sys.argv) > 2 else 0
 n, W, H = 1024, 1920, 1080
-dev = torch.device("cuda", 0)
-pairs = [synth.volume(n, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
-scene = testing.build(bench.config2_spec(n, W, H, camname, pairs))
+scene = timing.c2_scene(n, W, H, camname)[1]
 vol, cam = scene.volume, scene.camera
 N.check(N.lib().svr_set_variant(vol._rings.handle, variant), "variant")
 for mode in ("full", "lmip"):
@@ -37,7 +35,7 @@ for mode in ("full", "lmip"):
         r = vol.render(cam, W, H, region=reg)
         vol.prepare()
         cb, fb = vol.camera_block(cam), vol.frame_block(W, H, reg)
-        ob = N.Outputs(); ob.rgba = r.rgba.data_ptr(); ob.depth = r.depth.data_ptr(); ob.label = r.label.data_ptr(); ob.flags = r.flags.data_ptr()
+        ob = N.Outputs.of(r)
         ms = C.c_float(0)
         for iters in (10, 20):
             N.check(N.lib().svr_time_render(vol._rings.handle, C.byref(cb), C.byref(fb), C.byref(ob), iters, C.byref(ms)), "time")

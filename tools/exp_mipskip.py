@@ -8,8 +8,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-import bench  # noqa: E402
-from sub_volume_renderer_amd import _native as N, synth, testing  # noqa: E402
+import timing  # noqa: E402
+from sub_volume_renderer_amd import _native as N, testing  # noqa: E402
 
 
 def census(vol):
@@ -22,7 +22,7 @@ def time_ms(vol, cam, W, H, iters=20):
     vol.prepare()
     cb, fb = vol.camera_block(cam), vol.frame_block(W, H, None)
     r = vol.render(cam, W, H)
-    ob = N.Outputs(); ob.rgba = r.rgba.data_ptr(); ob.depth = r.depth.data_ptr(); ob.label = r.label.data_ptr(); ob.flags = r.flags.data_ptr()
+    ob = N.Outputs.of(r)
     ms = C.c_float(0)
     for it in (5, iters):
         N.check(N.lib().svr_time_render(vol._rings.handle, C.byref(cb), C.byref(fb), C.byref(ob), it, C.byref(ms)), "time")
@@ -42,10 +42,9 @@ if len(sys.argv) > 1 and sys.argv[1] == "small":
     sys.exit(0)
 
 n, W, H = 1024, 1920, 1080
-dev = torch.device("cuda", 0)
-pairs = [synth.volume(n, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
+pairs = timing.c2_pairs(n, torch.device("cuda", 0))
 for camname in ("K1", "K2"):
-    scene = testing.build(bench.config2_spec(n, W, H, camname, pairs))
+    scene = timing.c2_scene(n, W, H, camname, pairs=pairs)[1]
     vol, cam = scene.volume, scene.camera
     for mode in ("lmip", "mip", "weighted_average"):
         vol.material.render_mode = mode

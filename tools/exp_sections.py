@@ -55,8 +55,7 @@ def main():
             r = vol.render(cam, W, H, region=reg)
             vol.prepare()
             cb, fb = vol.camera_block(cam), vol.frame_block(W, H, reg)
-            ob = N.Outputs()
-            ob.rgba, ob.depth, ob.label, ob.flags = r.rgba.data_ptr(), r.depth.data_ptr(), r.label.data_ptr(), r.flags.data_ptr()
+            ob = N.Outputs.of(r)
             ms = C.c_float(0)
             for iters in (5, 10):
                 N.check(N.lib().svr_time_render(h, C.byref(cb), C.byref(fb), C.byref(ob), iters, C.byref(ms)), "time")

@@ -8,24 +8,22 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import bench  # noqa: E402
-from sub_volume_renderer_amd import _native as N, synth, testing  # noqa: E402
+import timing  # noqa: E402
+from sub_volume_renderer_amd import _native as N  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 variants = [int(v, 0) for v in sys.argv[2].split(",")] if len(sys.argv) > 2 else [0]
 cams = sys.argv[3].split(",") if len(sys.argv) > 3 else ["K1"]
 W, H = 1920, 1080
-dev = torch.device("cuda", 0)
-pairs = [synth.volume(n, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
-torch.cuda.synchronize()
+pairs = timing.c2_pairs(n, torch.device("cuda", 0))
 c = (n - 1) / 2.0
 dirs = {"-x": (-1, 0.02, 0.03), "-y": (0.02, -1, 0.03), "-z": (0.02, 0.03, -1), "diag": (-1, -1, -1)}
 for camname in cams:
-    spec = bench.config2_spec(n, W, H, camname if camname in ("K1", "K2") else "K1", pairs)
+    view = {}
     if camname in dirs:
         d = np.array(dirs[camname], float); d /= np.linalg.norm(d)
-        spec.cam_position = tuple(np.array([c, c, c]) + 1.6 * n * d); spec.cam_target = (c, c, c)
-    scene = testing.build(spec)
+        view = {"cam_position": tuple(np.array([c, c, c]) + 1.6 * n * d), "cam_target": (c, c, c)}
+    scene = timing.c2_scene(n, W, H, camname if camname in ("K1", "K2") else "K1", pairs=pairs, **view)[1]
     vol, cam = scene.volume, scene.camera
     ref = {}
     for mode in ("full", "lmip"):
@@ -44,7 +42,7 @@ for camname in cams:
             same = "same" if sig == ref[mode] else "DIFFERENT!"
             vol.prepare()
             cb, fb = vol.camera_block(cam), vol.frame_block(W, H, None)
-            ob = N.Outputs(); ob.rgba = r.rgba.data_ptr(); ob.depth = r.depth.data_ptr(); ob.label = r.label.data_ptr(); ob.flags = r.flags.data_ptr()
+            ob = N.Outputs.of(r)
             ms = C.c_float(0)
             for iters in (10, 10):      # first pass = warm-up (clocks, caches)
                 N.check(N.lib().svr_time_render(vol._rings.handle, C.byref(cb), C.byref(fb), C.byref(ob), iters, C.byref(ms)), "time")

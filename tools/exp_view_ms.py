@@ -26,8 +26,7 @@ for mode in ("full", "lmip"):
     vol.material.lmip_threshold = float("inf") if mode == "full" else float(spec.material["lmip_threshold"])
     vol.prepare()
     cb, fb = vol.camera_block(scene.camera), vol.frame_block(W, H, None)
-    ob = N.Outputs()
-    ob.rgba, ob.depth, ob.label, ob.flags = r.rgba.data_ptr(), r.depth.data_ptr(), r.label.data_ptr(), r.flags.data_ptr()
+    ob = N.Outputs.of(r)
     ms = C.c_float(0)
     vals = []
     for _ in range(3):

@@ -20,6 +20,8 @@ import statistics
 import sys
 import time
 
+import timing
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -36,8 +38,7 @@ def main():
     import numpy as np
     import torch
 
-    import bench
-    from sub_volume_renderer_amd import _native as N, synth, testing
+    from sub_volume_renderer_amd import _native as N
 
     if not torch.cuda.is_available():
         raise SystemExit("histogram_time.py needs a GPU")
@@ -45,30 +46,6 @@ def main():
     n, K = args.volume_n, args.bins
     lib = N.lib()
     stream = torch.cuda.current_stream(dev)
-
-    def timed(enqueue):
-        """Median seconds per call of ``enqueue(k)`` (k back-to-back calls), and the spread of the runs."""
-        enqueue(10)                                                    # warm-up: code objects, clocks
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream); enqueue(10); b.record(stream); b.synchronize()
-        k = max(10, int(args.window / max(a.elapsed_time(b) / 1e3 / 10, 1e-7)) + 1)
-        runs = []
-        for _ in range(args.repeats):
-            a.record(stream); enqueue(k); b.record(stream); b.synchronize()
-            runs.append(a.elapsed_time(b) / 1e3 / k)
-        return statistics.median(runs), min(runs), max(runs), k
-
-    def copy_rate(nbytes):
-        src = torch.empty(nbytes, dtype=torch.uint8, device=dev).random_(0, 256)
-        dst = torch.empty_like(src)
-
-        def enqueue(k):
-            for _ in range(k):
-                dst.copy_(src, non_blocking=True)                     # hipMemcpyAsync, device to device
-
-        med, _, _, _ = timed(enqueue)
-        del src, dst
-        return nbytes / med
 
     def histogram_case(vol, lod, what, sel=None, **extra):
         handle = vol.prepare()
@@ -86,12 +63,8 @@ def main():
         ho = N.HistogramOutputs(counts.data_ptr(), tail.data_ptr(), rng.data_ptr())
         argv = (handle, C.byref(hp), C.byref(ho), C.c_void_p(stream.cuda_stream))
 
-        def enqueue(k):
-            for _ in range(k):
-                N.check(lib.svr_histogram(*argv), "svr_histogram")
-
-        med, lo, hi, k = timed(enqueue)
-        memcpy = copy_rate(nbytes)
+        med, lo, hi, k = timing.timed(lambda: N.check(lib.svr_histogram(*argv), "svr_histogram"), args.window, args.repeats, k0=10)
+        memcpy = nbytes / timing.copy_seconds(nbytes, args.window, args.repeats, k0=10)
         line = {"case": what, "storage": vol._rings.density_storage, "lod": lod, "window": list(state.shape), "bins": K,
                 "label_filter": sel is not None, "us_per_call": round(med * 1e6, 2), "us_min_max": [round(lo * 1e6, 2), round(hi * 1e6, 2)],
                 "calls_per_run": k, "runs": args.repeats, "read_bytes": nbytes, "GB_per_s": round(nbytes / med / 1e9, 1),
@@ -126,13 +99,10 @@ def main():
                           "total_ms": round((read_s + host_s) * 1e3, 2), "svr_histogram_ms": round(gpu_seconds * 1e3, 4),
                           "speedup": round((read_s + host_s) / gpu_seconds, 1)}), flush=True)
 
-    pairs = [synth.volume(n, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
-    torch.cuda.synchronize()
+    pairs = timing.c2_pairs(n, dev)
     print(json.dumps({"volume_n": n, "bins": K, "device": torch.cuda.get_device_name(0)}), flush=True)
     for storage in ("native", "float32"):
-        spec = bench.config2_spec(n, 1920, 1080, "K1", pairs)
-        spec.ring_storage = storage
-        vol = testing.build(spec).volume
+        vol = timing.c2_scene(n, 1920, 1080, "K1", storage, pairs)[1].volume
         torch.cuda.synchronize()
         seconds = [histogram_case(vol, lod, "full window") for lod in range(3)]
         labels = torch.unique(pairs[0][1].reshape(-1)[:: max(1, pairs[0][1].numel() // 100000)])[:16].to(torch.int32).contiguous()

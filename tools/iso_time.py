@@ -6,8 +6,8 @@ bench's workload) from camera K1 or the inside camera K2, against its two yardst
   A          svr_composite with a step table (alpha 0 below the level, 1 at and above it), alpha_cutoff 0.99: the same
              rays, stopped at the same coarse sample, no skipping;
   B          the LMIP march (svr_render) at lmip_threshold = iso_value: the bench's workload.
-Called through the C ABI with prebuilt argument structs (steps = NULL: the production calls), timed as
-tools/composite_time.py times composites:
+Called through the C ABI with prebuilt argument structs (steps = NULL: the production calls), timed with
+the held windows of tools/timing.py:
   call_ms  HIP events around back-to-back calls;
   gpu_ms   the same calls queued behind a sleep kernel (GPU time per call, free of host pacing), the median of
            --boxes windows, with their min and max (the run-to-run spread).
@@ -24,13 +24,13 @@ usage: python tools/iso_time.py [--camera K1|K2] [--storage native|float32] [--l
        python tools/iso_time.py --stats DIR          (no GPU needed: the kernels of DIR's *kernel_stats.csv)
 """
 import argparse
-import csv
-import glob
 import json
 import os
 import sys
 
 import numpy as np
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -42,15 +42,8 @@ class _NoExtraPlanes:
 
 
 def stats(path):
-    for name in sorted(glob.glob(os.path.join(path, "**", "*kernel_stats.csv"), recursive=True)):
-        with open(name) as f:
-            for row in csv.DictReader(f):
-                kernel = row.get("Name", "")
-                if any(k in kernel for k in ("iso_kernel", "composite_kernel", "march_")):
-                    print(json.dumps({"file": os.path.relpath(name, path), "kernel": kernel[:90],
-                                      "calls": int(row["Calls"]), "average_ms": round(float(row["AverageNs"]) / 1e6, 4),
-                                      "min_ms": round(float(row["MinNs"]) / 1e6, 4),
-                                      "max_ms": round(float(row["MaxNs"]) / 1e6, 4)}))
+    for row in timing.kernel_stats(path, ("iso_kernel", "composite_kernel", "march_"), 90):
+        print(json.dumps(row))
 
 
 def main():
@@ -64,8 +57,7 @@ def main():
     ap.add_argument("--boxes", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--volume-n", type=int, default=1024)
-    ap.add_argument("--interpolation", default="nearest", choices=("nearest", "linear", "both"),
-                    help="svr_set_interpolation mode of the timed calls; both: nearest and linear alternate, case by case")
+    timing.add_interpolation_argument(ap)
     ap.add_argument("--cut", default="none", choices=("none", "half", "wedge", "all-cases"),
                     help="cut planes of the timed iso / composite calls; all-cases: none, half and wedge alternate")
     ap.add_argument("--stats", default=None, help="print the kernels of a --stats run's CSV instead of timing")
@@ -77,35 +69,16 @@ def main():
 
     import torch
 
-    import bench
     import cut_cases
-    from sub_volume_renderer_amd import TransferFunction, _native as N, synth, testing
+    from sub_volume_renderer_amd import TransferFunction, _native as N
 
     if not torch.cuda.is_available():
         raise SystemExit("iso_time.py needs a GPU")
     dev = torch.device("cuda", 0)
     n_vol, W, H = args.volume_n, 1920, 1080
-    pairs = [synth.volume(n_vol, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
-    torch.cuda.synchronize()
     stream = torch.cuda.current_stream(dev)
     lib = N.lib()
-
-    def window(calls, hold_cycles=0):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        if hold_cycles:
-            torch.cuda._sleep(hold_cycles)
-        a.record(stream)
-        calls()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b) / 1e3
-
-    probe = 10_000_000
-    per_cycle = window(lambda: torch.cuda._sleep(probe)) / probe
-
-    spec = bench.config2_spec(n_vol, W, H, args.camera, pairs)
-    spec.ring_storage = args.storage
-    scene = testing.build(spec)
+    spec, scene = timing.c2_scene(n_vol, W, H, args.camera, args.storage)
     vol, cam = scene.volume, scene.camera
     m = vol.material
     level = args.level * 255.0
@@ -119,7 +92,7 @@ def main():
     print(json.dumps({"storage": vol._rings.density_storage, "frame": [W, H], "volume_n": n_vol, "camera": args.camera,
                       "iso_value": level, "refine": args.refine}), flush=True)
 
-    interps = ("nearest", "linear") if args.interpolation == "both" else (args.interpolation,)
+    interps = timing.interpolations(args.interpolation)
     cuts = {c: cut_cases.cut_case(c, spec.cam_position, spec.cam_target) for c in cut_cases.names_of(args.cut)}
     # one counted render of each (steps planes, skip counters), then the production argument structs
     m.render_mode = "iso"
@@ -150,9 +123,7 @@ def main():
     handle = vol.prepare()
     vol._push_transfer_function()
     cb, fb = vol.camera_block(cam), vol.frame_block(W, H, None)
-    ob = N.Outputs()
-    ob.rgba, ob.depth, ob.label, ob.flags = (getattr(res, k).data_ptr() for k in ("rgba", "depth", "label", "flags"))
-    ob.steps, ob.pick, ob.pick_id = None, None, vol.id
+    ob = N.Outputs.of(res, pick_id=vol.id)
     ip_on = vol._iso_params(_NoExtraPlanes)
     ip_off = vol._iso_params(_NoExtraPlanes)
     ip_off.no_skip = 1
@@ -171,16 +142,7 @@ def main():
                                        for c in (cuts if n != "B" else ("none",))):
             N.check(lib.svr_set_interpolation(handle, N.INTERPOLATIONS[interp]), "svr_set_interpolation")
             N.check(cut_cases.push(lib, handle, *cuts.get(cut, ([], "ANY")), N.CUT_MODES), "svr_set_cut_planes")
-
-            def calls(k=args.calls, one=one):
-                for _ in range(k):
-                    one()
-
-            calls(5)
-            call_s = [window(calls) / args.calls for _ in range(args.boxes)]
-            hold = int(max(4.0 * max(call_s) * args.calls, 0.02) / per_cycle)
-            gpu_s = [window(calls, hold) / args.calls for _ in range(args.boxes)]
-            torch.cuda.synchronize()
+            call_s, gpu_s = timing.held(one, args.calls, args.boxes, warmup=5)
             row = {"case": name, "interpolation": interp, "cut": cut, "round": rnd, "call_ms": round(float(np.median(call_s)) * 1e3, 4),
                    "gpu_ms": round(float(np.median(gpu_s)) * 1e3, 4), "gpu_ms_min": round(min(gpu_s) * 1e3, 4),
                    "gpu_ms_max": round(max(gpu_s) * 1e3, 4), "calls_per_box": args.calls}

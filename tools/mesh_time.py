@@ -16,9 +16,10 @@ import argparse
 import ctypes as C
 import json
 import os
-import statistics
 import sys
 import time
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -37,9 +38,8 @@ def main():
     import numpy as np
     import torch
 
-    import bench
     from mesh_twin import mesh_twin
-    from sub_volume_renderer_amd import _native as N, synth, testing
+    from sub_volume_renderer_amd import _native as N
 
     if not torch.cuda.is_available():
         raise SystemExit("mesh_time.py needs a GPU")
@@ -48,17 +48,8 @@ def main():
     lib = N.lib()
     stream = torch.cuda.current_stream(dev)
 
-    def timed(enqueue):
-        """Median seconds per call of ``enqueue(k)`` (k back-to-back calls), and the spread of the runs."""
-        enqueue(3)                                                     # warm-up: code objects, clocks, the scratch
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream); enqueue(3); b.record(stream); b.synchronize()
-        k = max(3, int(args.window / max(a.elapsed_time(b) / 1e3 / 3, 1e-7)) + 1)
-        runs = []
-        for _ in range(args.repeats):
-            a.record(stream); enqueue(k); b.record(stream); b.synchronize()
-            runs.append(a.elapsed_time(b) / 1e3 / k)
-        return statistics.median(runs), min(runs), max(runs), k
+    def timed(one):
+        return timing.timed(one, args.window, args.repeats, k0=3)          # (the warm-up also allocates the scratch)
 
     def mesh_call(vol, box, sel, level, vertices, triangles, header):
         mp = N.MeshParams(lod=0, use_box=1)
@@ -71,12 +62,11 @@ def main():
                            header.data_ptr(), 0 if vertices is None else vertices.shape[0], 0 if triangles is None else triangles.shape[0])
         argv = (vol.prepare(), C.byref(mp), C.byref(mo), C.c_void_p(stream.cuda_stream))
 
-        def enqueue(k):
-            for _ in range(k):
-                N.check(lib.svr_mesh(*argv), "svr_mesh")
+        def one():
+            N.check(lib.svr_mesh(*argv), "svr_mesh")
 
-        enqueue.keep = (mp, mo)
-        return enqueue
+        one.keep = (mp, mo)
+        return one
 
     def objects_seconds(vol, box):
         records = torch.empty((16384, 12), dtype=torch.int64, device=dev)
@@ -86,11 +76,7 @@ def main():
         oo = N.ObjectsOutputs(records.data_ptr(), header.data_ptr())
         argv = (vol.prepare(), C.byref(op), C.byref(oo), C.c_void_p(stream.cuda_stream))
 
-        def enqueue(k):
-            for _ in range(k):
-                N.check(lib.svr_objects(*argv), "svr_objects")
-
-        return timed(enqueue)[0]
+        return timed(lambda: N.check(lib.svr_objects(*argv), "svr_objects"))[0]
 
     def readback_route(vol, box, sel_ids, level):
         """svr_read_region of the box (unwrapped pieces of the ring) + the numpy twin on a 64^3 sub-box, scaled."""
@@ -112,13 +98,10 @@ def main():
         t3 = time.perf_counter()
         return (t1 - t0), (t3 - t2) * voxels / float(e ** 3), len(twin["vertices"])
 
-    pairs = [synth.volume(n, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
-    torch.cuda.synchronize()
+    pairs = timing.c2_pairs(n, dev)
     print(json.dumps({"volume_n": n, "device": torch.cuda.get_device_name(0)}), flush=True)
     for storage in args.storages.split(","):
-        spec = bench.config2_spec(n, 1920, 1080, "K1", pairs)
-        spec.ring_storage = storage
-        vol = testing.build(spec).volume
+        vol = timing.c2_scene(n, 1920, 1080, "K1", storage, pairs)[1].volume
         torch.cuda.synchronize()
         state = N.LodState()
         N.check(lib.svr_get_lod_state(vol.prepare(), 0, C.byref(state)), "svr_get_lod_state")

@@ -18,9 +18,10 @@ import argparse
 import ctypes as C
 import json
 import os
-import statistics
 import sys
 import time
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -38,8 +39,7 @@ def main():
     import numpy as np
     import torch
 
-    import bench
-    from sub_volume_renderer_amd import _native as N, synth, testing
+    from sub_volume_renderer_amd import _native as N
 
     if not torch.cuda.is_available():
         raise SystemExit("objects_time.py needs a GPU")
@@ -49,29 +49,8 @@ def main():
     stream = torch.cuda.current_stream(dev)
     readback_lods = [int(v) for v in args.readback_lods.split(",") if v != ""]
 
-    def timed(enqueue):
-        """Median seconds per call of ``enqueue(k)`` (k back-to-back calls), and the spread of the runs."""
-        enqueue(5)                                                     # warm-up: code objects, clocks
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream); enqueue(5); b.record(stream); b.synchronize()
-        k = max(5, int(args.window / max(a.elapsed_time(b) / 1e3 / 5, 1e-7)) + 1)
-        runs = []
-        for _ in range(args.repeats):
-            a.record(stream); enqueue(k); b.record(stream); b.synchronize()
-            runs.append(a.elapsed_time(b) / 1e3 / k)
-        return statistics.median(runs), min(runs), max(runs), k
-
-    def copy_seconds(nbytes):
-        src = torch.empty(nbytes, dtype=torch.uint8, device=dev).random_(0, 256)
-        dst = torch.empty_like(src)
-
-        def enqueue(k):
-            for _ in range(k):
-                dst.copy_(src, non_blocking=True)                     # hipMemcpyAsync, device to device
-
-        med, _, _, _ = timed(enqueue)
-        del src, dst
-        return med
+    def timed(one):
+        return timing.timed(one, args.window, args.repeats, k0=5)
 
     def window_of(vol, lod):
         state = N.LodState()
@@ -89,11 +68,7 @@ def main():
         ho = N.HistogramOutputs(counts.data_ptr(), tail.data_ptr(), None)
         argv = (vol.prepare(), C.byref(hp), C.byref(ho), C.c_void_p(stream.cuda_stream))
 
-        def enqueue(k):
-            for _ in range(k):
-                N.check(lib.svr_histogram(*argv), "svr_histogram")
-
-        return timed(enqueue)[0]
+        return timed(lambda: N.check(lib.svr_histogram(*argv), "svr_histogram"))[0]
 
     def objects_case(vol, lod, what, sel16, background, capacity, box=None, comparators=True):
         state = window_of(vol, lod)
@@ -110,18 +85,14 @@ def main():
         oo = N.ObjectsOutputs(records.data_ptr(), header.data_ptr())
         argv = (vol.prepare(), C.byref(op), C.byref(oo), C.c_void_p(stream.cuda_stream))
 
-        def enqueue(k):
-            for _ in range(k):
-                N.check(lib.svr_objects(*argv), "svr_objects")
-
-        med, lo, hi, k = timed(enqueue)
+        med, lo, hi, k = timed(lambda: N.check(lib.svr_objects(*argv), "svr_objects"))
         head = [int(v) for v in header.cpu().numpy()]
         line = {"case": what, "storage": vol._rings.density_storage, "lod": lod, "shape": shape, "background": background,
                 "capacity": capacity, "us_per_call": round(med * 1e6, 2), "us_min_max": [round(lo * 1e6, 2), round(hi * 1e6, 2)],
                 "calls_per_run": k, "runs": args.repeats, "read_bytes": nbytes, "GB_per_s": round(nbytes / med / 1e9, 1),
                 "objects": head[0], "considered": head[1], "overflow": head[2], "dropped_label_0": head[3]}
         if comparators:
-            memcpy = copy_seconds(nbytes)
+            memcpy = timing.copy_seconds(nbytes, args.window, args.repeats, k0=5)
             hist = histogram_seconds(vol, lod, sel16, box)
             line.update({"memcpy_d2d_us": round(memcpy * 1e6, 2), "ratio_to_memcpy": round(med / memcpy, 2),
                          "histogram_16_labels_us": round(hist * 1e6, 2), "ratio_to_histogram": round(med / hist, 2)})
@@ -150,14 +121,11 @@ def main():
                           "total_ms": round((t2 - t0) * 1e3, 2), "objects": int(ids.size), "svr_objects_ms": round(gpu_seconds * 1e3, 4),
                           "speedup": round((t2 - t0) / gpu_seconds, 1), "checksum": float(sums.sum()) + int(counts.sum())}), flush=True)
 
-    pairs = [synth.volume(n, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
-    torch.cuda.synchronize()
+    pairs = timing.c2_pairs(n, dev)
     print(json.dumps({"volume_n": n, "device": torch.cuda.get_device_name(0)}), flush=True)
     sel16 = torch.unique(pairs[0][1].reshape(-1)[:: max(1, pairs[0][1].numel() // 100000)])[:16].to(torch.int32).contiguous()
     for storage in ("native", "float32"):
-        spec = bench.config2_spec(n, 1920, 1080, "K1", pairs)
-        spec.ring_storage = storage
-        vol = testing.build(spec).volume
+        vol = timing.c2_scene(n, 1920, 1080, "K1", storage, pairs)[1].volume
         torch.cuda.synchronize()
         for lod in range(3):
             seconds = objects_case(vol, lod, "full window", sel16, True, args.capacity)

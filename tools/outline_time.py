@@ -14,6 +14,8 @@ import json
 import os
 import sys
 
+import timing
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -28,16 +30,13 @@ def main():
 
     import torch
 
-    import bench
-    from sub_volume_renderer_amd import _native as N, synth, testing
+    from sub_volume_renderer_amd import _native as N
 
     if not torch.cuda.is_available():
         raise SystemExit("outline_time.py needs a GPU")
     dev = torch.device("cuda", 0)
     n, W, H = args.volume_n, 1920, 1080
-    pairs = [synth.volume(n, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
-    torch.cuda.synchronize()
-    scene = testing.build(bench.config2_spec(n, W, H, "K1", pairs))
+    scene = timing.c2_scene(n, W, H, "K1")[1]
     res = scene.volume.render(scene.camera, W, H)
     torch.cuda.synchronize()
     hits = int((res.flags == 2).sum())
@@ -56,23 +55,15 @@ def main():
             argv = (handle, p(res.rgba), p(res.depth) if depth_test else None, p(res.label), p(res.flags), W, H,
                     C.byref(q), p(colors), colors.shape[0], None, 0, p(out), None, C.c_void_p(stream.cuda_stream))
 
-            def calls(k):
-                for _ in range(k):
-                    N.check(lib.svr_outline(*argv), "svr_outline")
-
-            calls(20)                                           # warm-up
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream); calls(50); b.record(stream); b.synchronize()
-            iters = max(50, int(args.window / (a.elapsed_time(b) / 1e3 / 50)) + 1)
-            a.record(stream); calls(iters); b.record(stream); b.synchronize()
-            ms = a.elapsed_time(b)
-            per_call = ms / 1e3 / iters
+            # one window of at least --window seconds, sized from 50 calls after a warm-up of 20
+            per_call, _, _, iters = timing.timed(lambda: N.check(lib.svr_outline(*argv), "svr_outline"), args.window,
+                                                 repeats=1, k0=50, warmup=20)
             nbytes = W * H * (16 + 16 + 4 + 1 + (4 if depth_test else 0))
             edges = torch.empty((H, W), dtype=torch.uint8, device=dev)
             N.check(lib.svr_outline(*argv[:13], p(edges), argv[14]), "svr_outline")
             torch.cuda.synchronize()
             print(json.dumps({"radius": radius, "depth_test": depth_test, "us_per_call": round(per_call * 1e6, 2),
-                              "calls": iters, "window_s": round(ms / 1e3, 3), "bytes_per_call": nbytes,
+                              "calls": iters, "window_s": round(per_call * iters, 3), "bytes_per_call": nbytes,
                               "GB_per_s": round(nbytes / per_call / 1e9, 1),
                               "hbm_peak_fraction": round(nbytes / per_call / HBM_PEAK, 3),
                               "edge_pixels": int(edges.sum())}), flush=True)

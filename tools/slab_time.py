@@ -3,7 +3,7 @@
 bench's workload) with byte rings and with float32 rings: z-, x-normal and one oblique slab through the camera's focus
 at 1 voxel per pixel and 1 voxel per sample, N in {1, 16, 64}, max and mean, with the default routing of the
 micro-block copy, rows only (variant bit 8) and the copy always (bit 9); plus svr_slice on the z-normal plane, the
-N = 1 yardstick.  Called through the C ABI with prebuilt argument structs, timed as tools/slice_time.py times slices:
+N = 1 yardstick.  Called through the C ABI with prebuilt argument structs, timed with the held windows of tools/timing.py:
   call_us  HIP events around back-to-back calls;
   gpu_us   the same calls queued behind a sleep kernel (GPU time per call, free of host pacing).
 Per case also the two floors:
@@ -25,6 +25,8 @@ import sys
 
 import numpy as np
 
+import timing
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -37,6 +39,7 @@ SAMPLES = (1, 16, 64)
 MODES = ("max", "mean")
 ROUTINGS = ("default", "rows", "copy")
 OBLIQUE = ((0.8, 0.6, 0.0), (-0.36, 0.48, 0.8), (0.48, -0.64, 0.6))     # u, v, w: orthonormal
+WARMUP = 20                                   # calls before the timed windows of a case: kernel_times skips as many
 
 
 def cases():
@@ -56,15 +59,15 @@ def kernel_times(db_path, calls, boxes):
          if "slab_kernel" in n or "slice_kernel" in n]
     timed = 2 * boxes * calls
     per = list(cases())
-    if len(d) != len(STORAGES) * (2 + len(per) * (20 + timed)):
+    if len(d) != len(STORAGES) * (2 + len(per) * (WARMUP + timed)):
         raise SystemExit(f"{len(d)} slice / slab dispatches: not a traced run with --calls {calls} --boxes {boxes}")
     i = 0
     for storage in STORAGES:
         i += 2
         for kind, s, n, mode, routing in per:
-            seg = np.array([t for k, t in d[i + 20:i + 20 + timed]])
-            assert all(k == kind for k, _ in d[i:i + 20 + timed])
-            i += 20 + timed
+            seg = np.array([t for k, t in d[i + WARMUP:i + WARMUP + timed]])
+            assert all(k == kind for k, _ in d[i:i + WARMUP + timed])
+            i += WARMUP + timed
             print(json.dumps({"storage": storage, "kind": kind, "slab": s, "samples": n, "mode": mode, "routing": routing,
                               "kernel_us": round(float(np.median(seg)), 2),
                               "kernel_us_p10_p90": [round(float(np.percentile(seg, q)), 2) for q in (10, 90)]}))
@@ -110,8 +113,7 @@ def main():
     ap.add_argument("--volume-n", type=int, default=1024)
     ap.add_argument("--valu-per-sample", type=float, default=None,
                     help="VALU per sample of slab_kernel's loop, from its ISA (DESIGN.md); omit: no VALU floor")
-    ap.add_argument("--interpolation", default="nearest", choices=("nearest", "linear", "both"),
-                    help="svr_set_interpolation mode of the timed calls; both: nearest and linear alternate, case by case")
+    timing.add_interpolation_argument(ap)
     ap.add_argument("--trace-db", default=None, help="attribute the kernels of a traced run instead of timing")
     args = ap.parse_args()
     if args.trace_db:
@@ -121,37 +123,21 @@ def main():
 
     import torch
 
-    import bench
-    from sub_volume_renderer_amd import SubVolume, _native as N, synth, testing
+    from sub_volume_renderer_amd import SubVolume, _native as N
 
     if not torch.cuda.is_available():
         raise SystemExit("slab_time.py needs a GPU")
     dev = torch.device("cuda", 0)
     n_vol, W, H = args.volume_n, 1920, 1080
-    pairs = [synth.volume(n_vol, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
-    torch.cuda.synchronize()
+    pairs = timing.c2_pairs(n_vol, dev)
     stream = torch.cuda.current_stream(dev)
     lib = N.lib()
-    interps = ("nearest", "linear") if args.interpolation == "both" else (args.interpolation,)
-
-    def window(calls, hold_cycles=0):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        if hold_cycles:
-            torch.cuda._sleep(hold_cycles)
-        a.record(stream)
-        calls()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b) / 1e3
-
-    probe = 10_000_000
-    per_cycle = window(lambda: torch.cuda._sleep(probe)) / probe
+    interps = timing.interpolations(args.interpolation)
     written = W * H * (16 + 4 + 4 + 1 + 4 + 1)
 
     for storage in ("native", "float32"):
-        spec = bench.config2_spec(n_vol, W, H, "K1", pairs)
-        spec.ring_storage = storage
-        vol = testing.build(spec).volume
+        spec, scene = timing.c2_scene(n_vol, W, H, "K1", storage, pairs)
+        vol = scene.volume
         focus = tuple(float(c) for c in spec.centers[0][0])
         es = {"uint8": 1, "uint16": 2}.get(vol._rings.density_storage, 4)
         print(json.dumps({"storage": vol._rings.density_storage, "frame": [W, H], "volume_n": n_vol, "focus": focus,
@@ -161,24 +147,14 @@ def main():
         res = vol.render_slab(o, u, v, (0.0, 0.0, 1.0), 1, W, H)
         handle = vol.prepare()
         fb = vol.frame_block(W, H, None)
-
-        def outputs(r):
-            ob = N.SliceOutputs()
-            for name in ("rgba", "depth", "label", "flags", "value", "lod"):
-                setattr(ob, name, getattr(r, name).data_ptr())
-            return ob
-
-        ob_slice, ob_slab = outputs(res_slice), outputs(res)
+        ob_slice, ob_slab = N.SliceOutputs.of(res_slice), N.SliceOutputs.of(res)
         foot = {}
         for kind, s, n, mode, routing, interp in ((*c, i) for c in cases() for i in interps):
             if s == "oblique":
                 origin, (u, v, w) = focus, OBLIQUE
             else:
                 origin, u, v, w = SubVolume.axis_slab_plane(s, focus, 1.0, 1.0)
-            pl = N.SlicePlane()
-            pl.world_inv = N.mat_to_c(vol.world.inverse_matrix)
-            pl.volume_dimensions[:] = [float(c) for c in vol._volume_dimensions]
-            pl.origin[:], pl.u[:], pl.v[:] = origin, u, v
+            pl = vol._plane_struct(origin, u, v)
             if kind == "slice":
                 argv = (handle, C.byref(pl), C.byref(fb), C.byref(ob_slice), C.c_void_p(stream.cuda_stream))
                 fn, name = lib.svr_slice, "svr_slice"
@@ -193,17 +169,12 @@ def main():
                 foot[(s, n)] = footprint(vol, origin, u, v, w, n, W, H)
             inside, texels = foot[(s, n)]
 
-            def calls(k=args.calls):
-                for _ in range(k):
-                    N.check(fn(*argv), name)
+            def one():
+                N.check(fn(*argv), name)
 
             N.check(lib.svr_set_variant(handle, {"default": 0, "rows": 0x100, "copy": 0x200}[routing]), "svr_set_variant")
             N.check(lib.svr_set_interpolation(handle, N.INTERPOLATIONS[interp]), "svr_set_interpolation")
-            calls(20)
-            call_s = [window(calls) / args.calls for _ in range(args.boxes)]
-            hold = int(max(4.0 * max(call_s) * args.calls, 0.02) / per_cycle)
-            gpu_s = [window(calls, hold) / args.calls for _ in range(args.boxes)]
-            torch.cuda.synchronize()
+            call_s, gpu_s = timing.held(one, args.calls, args.boxes, warmup=WARMUP)
             read = texels * (es + (4 if vol._rings.labels else 0))
             row = {"storage": vol._rings.density_storage, "kind": kind, "slab": s, "samples": n, "mode": mode,
                    "routing": routing, "interpolation": interp, "call_us": round(float(np.median(call_s)) * 1e6, 2),

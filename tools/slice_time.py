@@ -4,7 +4,7 @@ bench's workload) with byte rings and with float32 rings: z-, y-, x-normal and o
 focus at 1 voxel per pixel, with the default routing of the micro-block copy of LOD 0, rows only (variant bit 8) and
 the copy always (bit 9).  svr_slice is called through the C ABI with prebuilt argument structs, as
 tools/outline_time.py calls svr_outline.  Two numbers per case, each the median of --boxes windows of --calls calls
-after a warm-up:
+after a warm-up (timing.held, tools/timing.py):
   call_us  HIP events around back-to-back calls: what a caller that issues slices one after another sees (host
            enqueue and device both count, whichever is slower);
   gpu_us   the same calls enqueued while the stream is held by a sleep kernel (calibrated to outlast the enqueue), the
@@ -25,6 +25,8 @@ import os
 import sys
 
 import numpy as np
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -63,6 +65,7 @@ def texels_read(vol, origin, u, v, W, H):
 
 STORAGES = ("uint8", "float32")
 ROUTINGS = ("default", "rows", "copy")
+WARMUP = 20                                   # calls before the timed windows of a case: kernel_times skips as many
 
 
 def kernel_times(db_path, calls, boxes):
@@ -73,15 +76,15 @@ def kernel_times(db_path, calls, boxes):
     rows = sqlite3.connect(db_path).execute("select name, start, end from kernels order by start").fetchall()
     d = np.array([e - s for n, s, e in rows if "slice_kernel" in n], np.float64) / 1e3
     timed = 2 * boxes * calls
-    if len(d) != len(STORAGES) * (1 + len(PLANES) * len(ROUTINGS) * (20 + timed)):
+    if len(d) != len(STORAGES) * (1 + len(PLANES) * len(ROUTINGS) * (WARMUP + timed)):
         raise SystemExit(f"{len(d)} slice_kernel dispatches: not a traced run with --calls {calls} --boxes {boxes}")
     i = 0
     for storage in STORAGES:
         i += 1
         for plane, _ in PLANES:
             for routing in ROUTINGS:
-                seg = d[i + 20:i + 20 + timed]
-                i += 20 + timed
+                seg = d[i + WARMUP:i + WARMUP + timed]
+                i += WARMUP + timed
                 print(json.dumps({"storage": storage, "plane": plane, "routing": routing,
                                   "kernel_us": round(float(np.median(seg)), 2),
                                   "kernel_us_p10_p90": [round(float(np.percentile(seg, q)), 2) for q in (10, 90)]}))
@@ -92,8 +95,7 @@ def main():
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--boxes", type=int, default=5)
     ap.add_argument("--volume-n", type=int, default=1024)
-    ap.add_argument("--interpolation", default="nearest", choices=("nearest", "linear", "both"),
-                    help="svr_set_interpolation mode of the timed calls; both: nearest and linear alternate, case by case")
+    timing.add_interpolation_argument(ap)
     ap.add_argument("--trace-db", default=None, help="attribute the kernels of a traced run instead of timing")
     args = ap.parse_args()
     if args.trace_db:
@@ -103,37 +105,20 @@ def main():
 
     import torch
 
-    import bench
-    from sub_volume_renderer_amd import SubVolume, _native as N, synth, testing
+    from sub_volume_renderer_amd import SubVolume, _native as N
 
     if not torch.cuda.is_available():
         raise SystemExit("slice_time.py needs a GPU")
     dev = torch.device("cuda", 0)
     n, W, H = args.volume_n, 1920, 1080
-    pairs = [synth.volume(n, k, 4096, xp=torch, device=dev, slab=16) for k in range(3)]
-    torch.cuda.synchronize()
+    pairs = timing.c2_pairs(n, dev)
     stream = torch.cuda.current_stream(dev)
     lib = N.lib()
-    interps = ("nearest", "linear") if args.interpolation == "both" else (args.interpolation,)
-
-    def window(calls, hold_cycles=0):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        if hold_cycles:
-            torch.cuda._sleep(hold_cycles)
-        a.record(stream)
-        calls()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b) / 1e3
-
-    # sleep cycles that outlast the enqueue of one window by a wide margin (>= 4x its back-to-back time, >= 20 ms)
-    probe = 10_000_000
-    per_cycle = window(lambda: torch.cuda._sleep(probe)) / probe
+    interps = timing.interpolations(args.interpolation)
 
     for storage in ("native", "float32"):
-        spec = bench.config2_spec(n, W, H, "K1", pairs)
-        spec.ring_storage = storage
-        vol = testing.build(spec).volume
+        spec, scene = timing.c2_scene(n, W, H, "K1", storage, pairs)
+        vol = scene.volume
         focus = tuple(float(c) for c in spec.centers[0][0])
         es = {"uint8": 1, "uint16": 2}.get(vol._rings.density_storage, 4)
         print(json.dumps({"storage": vol._rings.density_storage, "frame": [W, H], "volume_n": n, "focus": focus,
@@ -141,33 +126,23 @@ def main():
         res = vol.render_slice(*SubVolume.axis_slice_plane("z", focus, 1.0), W, H)      # the output tensors
         handle = vol.prepare()
         fb = vol.frame_block(W, H, None)
-        ob = N.SliceOutputs()
-        for name in ("rgba", "depth", "label", "flags", "value", "lod"):
-            setattr(ob, name, getattr(res, name).data_ptr())
+        ob = N.SliceOutputs.of(res)
         for name, uv in PLANES:
             if uv is None:
                 origin, u, v = SubVolume.axis_slice_plane(name, focus, 1.0)
             else:
                 origin, (u, v) = focus, uv
-            pl = N.SlicePlane()
-            pl.world_inv = N.mat_to_c(vol.world.inverse_matrix)
-            pl.volume_dimensions[:] = [float(c) for c in vol._volume_dimensions]
-            pl.origin[:], pl.u[:], pl.v[:] = origin, u, v
+            pl = vol._plane_struct(origin, u, v)
             argv = (handle, C.byref(pl), C.byref(fb), C.byref(ob), C.c_void_p(stream.cuda_stream))
             read = texels_read(vol, origin, u, v, W, H) * (es + (4 if vol._rings.labels else 0))
 
-            def calls(k=args.calls):
-                for _ in range(k):
-                    N.check(lib.svr_slice(*argv), "svr_slice")
+            def one():
+                N.check(lib.svr_slice(*argv), "svr_slice")
 
             for routing, variant, interp in ((r, x, i) for r, x in zip(ROUTINGS, (0, 0x100, 0x200)) for i in interps):
                 N.check(lib.svr_set_variant(handle, variant), "svr_set_variant")
                 N.check(lib.svr_set_interpolation(handle, N.INTERPOLATIONS[interp]), "svr_set_interpolation")
-                calls(20)                                             # warm-up
-                call_s = [window(calls) / args.calls for _ in range(args.boxes)]
-                hold = int(max(4.0 * max(call_s) * args.calls, 0.02) / per_cycle)
-                gpu_s = [window(calls, hold) / args.calls for _ in range(args.boxes)]
-                torch.cuda.synchronize()
+                call_s, gpu_s = timing.held(one, args.calls, args.boxes, warmup=WARMUP)
                 call_us, gpu_us = float(np.median(call_s)) * 1e6, float(np.median(gpu_s)) * 1e6
                 written = W * H * (16 + 4 + 4 + 1 + 4 + 1)
                 print(json.dumps({"storage": vol._rings.density_storage, "plane": name, "routing": routing, "interpolation": interp,
