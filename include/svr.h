@@ -913,6 +913,87 @@ typedef struct svr_mesh_outputs {       /* DEVICE pointers; header required */
 } svr_mesh_outputs;
 int  svr_mesh(svr_ctx* ctx, const svr_mesh_params* params, const svr_mesh_outputs* out, void* stream);
 
+/* ---- connected components of the resident rings: how many blobs does a level set have, how big is each, where is the
+ * biggest, which one lies under a picked point; is a label one piece or five?  (No counterpart in the reference; what a
+ * viewer answers today by reading the window back and labelling it on the CPU.)  An addition within ABI version 9: one
+ * new symbol and three new structs, nothing older changes.  The window is labelled in HBM (union-find over atomic
+ * minima); nothing is copied to the host.
+ * Defined HERE (numpy restatement: tests/components_twin.py):
+ *   box B       [lo, lo + n): the intersection of box and window exactly as in svr_histogram (use_box, box_off,
+ *               box_shape).  A window of None and a box that misses the window give no component.  The texel of voxel
+ *               (x, y, z) is ring slot (x % ring_x, y % ring_y, z % ring_z) of the row-major ring (the micro-block copy is
+ *               never read).
+ *   inside(p)   p is in B, and
+ *                 SVR_COMPONENTS_LEVEL   v >= level, v being the density element converted to f32 exactly as svr_mesh
+ *                                        converts it.  A NaN is outside.  selected, ignore_zero and join_labels are not
+ *                                        read, and every label below reads as 0.
+ *                 SVR_COMPONENTS_LABELS  the label texel of p is one of selected[0 .. selected_count) (sorted
+ *                                        ascending), or any label when selected_count == 0; and, with ignore_zero != 0,
+ *                                        it is not 0: the voxels of label 0 that passed `selected` are outside and are
+ *                                        counted in header[13].  Without label rings every label reads as 0.
+ *   connect(p, q)  p and q are neighbours under `connectivity` (6: they differ by one on one axis; 26: by at most one on
+ *               every axis, and are not equal), both are inside, and, in SVR_COMPONENTS_LABELS with join_labels == 0,
+ *               their labels are equal.  Nothing connects across B's border.
+ *   component   a class of the transitive closure of connect().  Its FIRST voxel is its smallest in (z, then y, then x)
+ *               order.
+ *   numbering   components are numbered 1 .. N in ascending order of their first voxels (the numbering of
+ *               scipy.ndimage.label).
+ *   ids         dense [n_z][n_y][n_x] over B (not ring-shaped): 0 for a voxel that is outside, else the number of its
+ *               component.  Written, whole, only when ids_capacity >= n_x n_y n_z; else not touched.
+ *   records     N records of 80 bytes in id order.  Written, all of them, only when record_capacity >= N; else not
+ *               touched.  sum[] is relative to the window offset (header[4..6]); first, lo and hi are logical voxel
+ *               coordinates of the LOD in shader order (x, y, z), lo and hi both inclusive.
+ *   header      16 x uint64_t:
+ *                 [0] N                          [1] inside voxels
+ *                 [2] elements of ids written    [3] records written
+ *                 [4..6] the window offset (x, y, z) of the LOD the call used, as int64 bit patterns
+ *                 [7..9] B's first voxel (x, y, z), as int64 bit patterns      [10..12] n_x, n_y, n_z
+ *                 [13] label-0 voxels dropped by ignore_zero
+ *                 [14..15] 0
+ *               An empty B gives [7..12] = 0.  The header is overwritten by every call.  Capacities of 0 with NULL
+ *               arrays are the count-only call.
+ * Everything is an integer and fully specified: two calls on the same rings give identical bytes.  Ordered like svr_mesh:
+ * it waits for published uploads, and later uploads are ordered behind it.  Enqueued on `stream`; asynchronous.  The
+ * call works in scratch memory owned by the context (8 bytes per voxel of B, grown on demand, SVR_ERR_NOMEM when it
+ * cannot be, released by svr_destroy); a call is ordered behind the previous svr_components of the same context,
+ * whatever its stream.  The material, the variant, the interpolation and the cut planes are not read.
+ * SVR_ERR_INVALID, with nothing enqueued and the outputs untouched, for: a NULL ctx, params, outputs or header; lod out of
+ * range; an unknown mode; a connectivity other than 6 or 26; a NaN level (SVR_COMPONENTS_LEVEL); selected == NULL with
+ * selected_count > 0; a negative box_shape component (with use_box != 0); more than SVR_COMPONENTS_MAX_VOXELS voxels in
+ * B; a NULL array with a non-zero capacity. */
+#define SVR_COMPONENTS_LABELS 0
+#define SVR_COMPONENTS_LEVEL  1
+#define SVR_COMPONENTS_MAX_VOXELS (1u << 30)
+typedef struct svr_components_params {
+    int32_t lod;
+    int32_t use_box;                    /* 0: the LOD's whole resident window */
+    int32_t box_off[3], box_shape[3];   /* LOD-l logical voxels, shader order: svr_histogram_params' */
+    int32_t mode;                       /* SVR_COMPONENTS_LABELS or SVR_COMPONENTS_LEVEL */
+    float   level;                      /* SVR_COMPONENTS_LEVEL: inside is v >= level; not NaN */
+    const uint32_t* selected;           /* SVR_COMPONENTS_LABELS: DEVICE, sorted ascending; NULL when the count is 0 */
+    uint32_t selected_count;            /* 0: every label */
+    int32_t  ignore_zero;               /* SVR_COMPONENTS_LABELS: != 0: label-0 voxels are outside; counted in header[13] */
+    int32_t  join_labels;               /* SVR_COMPONENTS_LABELS: != 0: inside neighbours connect whatever their labels */
+    int32_t  connectivity;              /* 6 (faces) or 26 (faces, edges, corners) */
+} svr_components_params;
+typedef struct svr_component_record {   /* 80 bytes */
+    uint32_t id;          /* 1 .. N */
+    uint32_t label;       /* the label of the first voxel (SVR_COMPONENTS_LEVEL: 0) */
+    uint64_t voxels;
+    uint64_t sum[3];      /* sum over them of (x - off_x), (y - off_y), (z - off_z); off = header[4..6] */
+    int32_t  first[3];    /* the first voxel in (z, y, x) order, as (x, y, z) */
+    int32_t  lo[3], hi[3];/* smallest and largest logical voxel coordinate, both inclusive */
+    uint32_t reserved;    /* 0 */
+} svr_component_record;
+typedef struct svr_components_outputs { /* DEVICE pointers; header required */
+    uint32_t* ids;                      /* ids_capacity elements */
+    uint64_t  ids_capacity;             /* 0: ids may be NULL */
+    svr_component_record* records;      /* record_capacity records */
+    uint64_t  record_capacity;          /* 0: records may be NULL */
+    uint64_t* header;                   /* 16 */
+} svr_components_outputs;
+int  svr_components(svr_ctx* ctx, const svr_components_params* params, const svr_components_outputs* out, void* stream);
+
 /* ---- sync */
 int  svr_sync(svr_ctx* ctx);                 /* both streams idle */
 int  svr_sync_uploads(svr_ctx* ctx);         /* upload stream idle */

@@ -16,6 +16,7 @@ from ._transform import AffineTransform, OrthographicCamera, PerspectiveCamera
 from ._wobject import FrameRegion, HistogramResult, IsoResult, ObjectTable, RenderResult, SliceResult, SubVolume
 from ._wrapping_buffer import WrappingBuffer, subtract_rois
 from .mesh import SurfaceMesh
+from .components import ComponentLabels
 
 __all__ = [
     "SubVolume",
@@ -35,6 +36,7 @@ __all__ = [
     "HistogramResult",
     "ObjectTable",
     "SurfaceMesh",
+    "ComponentLabels",
     "subtract_rois",
     # display-side output of a render (pygfx's job in the reference)
     "compose",

@@ -278,6 +278,50 @@ class MeshOutputs(C.Structure):
 MESH_LABELS, MESH_LEVEL = 0, 1                      # SVR_MESH_*
 MESH_MAX_CELLS = 1 << 28                            # SVR_MESH_MAX_CELLS
 
+
+class ComponentsParams(C.Structure):
+    _fields_ = [
+        ("lod", C.c_int32),
+        ("use_box", C.c_int32),
+        ("box_off", C.c_int32 * 3),
+        ("box_shape", C.c_int32 * 3),
+        ("mode", C.c_int32),
+        ("level", C.c_float),
+        ("selected", C.c_void_p),
+        ("selected_count", C.c_uint32),
+        ("ignore_zero", C.c_int32),
+        ("join_labels", C.c_int32),
+        ("connectivity", C.c_int32),
+    ]
+
+
+class ComponentRecord(C.Structure):
+    _fields_ = [
+        ("id", C.c_uint32),
+        ("label", C.c_uint32),
+        ("voxels", C.c_uint64),
+        ("sum", C.c_uint64 * 3),
+        ("first", C.c_int32 * 3),
+        ("lo", C.c_int32 * 3),
+        ("hi", C.c_int32 * 3),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class ComponentsOutputs(C.Structure):
+    _fields_ = [
+        ("ids", C.c_void_p),
+        ("ids_capacity", C.c_uint64),
+        ("records", C.c_void_p),
+        ("record_capacity", C.c_uint64),
+        ("header", C.c_void_p),
+    ]
+
+
+COMPONENTS_LABELS, COMPONENTS_LEVEL = 0, 1          # SVR_COMPONENTS_*
+COMPONENTS_MAX_VOXELS = 1 << 30                     # SVR_COMPONENTS_MAX_VOXELS
+COMPONENT_RECORD_BYTES = 80                         # sizeof(svr_component_record)
+
 INTERPOLATIONS = {"nearest": 0, "linear": 1}      # SVR_INTERP_*
 CUT_MODES = {"ANY": 0, "ALL": 1}                  # SVR_CUT_*
 MAX_CUT_PLANES = 8                                # SVR_MAX_CUT_PLANES
@@ -340,6 +384,7 @@ SIGNATURES = {
     "svr_histogram": (C.c_int, [C.c_void_p, C.POINTER(HistogramParams), C.POINTER(HistogramOutputs), C.c_void_p]),
     "svr_objects": (C.c_int, [C.c_void_p, C.POINTER(ObjectsParams), C.POINTER(ObjectsOutputs), C.c_void_p]),
     "svr_mesh": (C.c_int, [C.c_void_p, C.POINTER(MeshParams), C.POINTER(MeshOutputs), C.c_void_p]),
+    "svr_components": (C.c_int, [C.c_void_p, C.POINTER(ComponentsParams), C.POINTER(ComponentsOutputs), C.c_void_p]),
     "svr_sync": (C.c_int, [C.c_void_p]),
     "svr_sync_uploads": (C.c_int, [C.c_void_p]),
     "svr_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),

@@ -1204,5 +1204,24 @@ class SubVolume(_HasWorld):
 
         return mesh(self, labels=labels, level=level, lod=lod, box=box, stream=stream)
 
+    # -- how many pieces, how big, which one is under the cursor? -----------------------
+    def components(self, level=None, labels=None, background: bool = False, join: bool = False, connectivity: int = 6, lod: int = 0,
+                   box=None, stream=None):
+        """The connected components of what LOD ``lod`` holds in HBM, labelled on the device (definition:
+        ``svr_components`` in include/svr.h) -> :class:`~.components.ComponentLabels`: a dense volume of component
+        numbers and one row per component (voxel count, first voxel, bounding box, centroid, label), numbered like
+        ``scipy.ndimage.label``.  With ``level`` the voxels whose value is >= ``level`` are inside (the ring's own units,
+        like the iso value): the blobs of a level set.  Without it the segmentation decides: ``labels`` (None: every
+        label) are inside, ``background=False`` leaves the voxels of label 0 out (they are counted in
+        ``ComponentLabels.background``), and neighbours connect only where their labels are equal, so a label that lies
+        in five pieces gives five components, unless ``join=True`` joins the inside voxels whatever their labels.
+        ``level`` together with ``labels``, and a ``connectivity`` other than 6 (faces) or 26 (faces, edges, corners),
+        raise ``ValueError``.  ``box`` means what it means in :meth:`histogram`; nothing connects across the border of box
+        and window.  The call SYNCHRONISES twice: it counts first, allocates exactly, then emits."""
+        from .components import components
+
+        return components(self, level=level, labels=labels, background=background, join=join, connectivity=connectivity, lod=lod,
+                          box=box, stream=stream)
+
     def synchronize(self):
         N.check(N.lib().svr_sync(self._rings.handle), "svr_sync")

@@ -1,0 +1,438 @@
+// Connected components of the resident rings (svr_components, include/svr.h): union-find over a box of one LOD's window,
+// components numbered by their first voxels, a dense volume of numbers and one record per component.  gfx950.
+//
+// The chain (layout of the scratch: components_plan.h), every kernel a plain launch on the caller's stream; no
+// workgroup waits for another inside a launch and nothing spins on a flag:
+//   init     the one pass over the rings.  A lane owns 4 consecutive ring slots at a multiple of 4 (components_plan.h:
+//            head): one 16-byte load of the label or float32 ring, 8 bytes of a u16 ring, 4 of a u8 ring where the slot is
+//            whole, inside the row and aligned, else its elements one by one (a row's head and tail, the slot the
+//            ring's wrap seam cuts).  Writes parent[i]: kUfOutside for a voxel that is outside, else the first voxel of
+//            the run of connecting voxels it belongs to among the lane's 4, so x neighbours inside a lane are linked for
+//            free; and, where labels split components, the label into aux[i], so that no later pass reads a wrapped ring
+//            row.  Counts the inside voxels and the dropped zeros, one atomic each per wave.
+//   merge    a thread per voxel joins it with the neighbours before it (components_uf.h: uf_merge_voxel, the rules of
+//            the union-find are stated there); 6- and 26-connectivity, with and without labels, are compile-time variants.
+//   flatten  parent[i] = root(i), and the number of roots among each workgroup's voxels: level 0 of the scan.
+//   scan     an exclusive prefix of those counts in place: per-block sums level by level, one workgroup over the top
+//            level (which also writes the header), then each level adds its block's prefix on the way down.
+//   rank     a root in (z, y, x) order is the first voxel of its component, so the number of roots before it is its
+//            component's number minus one: into aux[root]; and, when the records fit, the root starts its record (id,
+//            label, first; empty sums and an empty box).
+//   emit     a thread per voxel: ids[i] = aux[parent[i]] + 1, and the voxel's share of its record.  The lanes of a
+//            wave that belong to one component add up and reduce their shares with shuffles first, so a component that
+//            fills the wave costs one set of integer atomics per wave, not 64.  Skipped by the count-only call.
+// parent is only ever written by the init pass and by atomic minima; every other store is an ordinary vector store.
+#include <limits.h>
+
+#include "svr_host.h"
+#include "components_plan.h"
+#include "components_uf.h"
+#include "ring_pieces.h"
+
+namespace {
+
+constexpr int kCompThreads = 256;
+static_assert(kCompScanBlock == (uint32_t)kCompThreads, "one entry, and one voxel, per thread");
+
+struct CompArgs {
+    const void* density;
+    const uint32_t* labels;    // null: every label reads as 0
+    uint32_t ring[3];
+    uint32_t n[3];             // extent of the box B
+    uint32_t s0[3];            // ring slot of B's first voxel
+    int32_t lo[3];             // B's first voxel
+    int32_t rel[3];            // B's first voxel minus the window offset
+    uint32_t voxels, head, upr, units;
+    float level;
+    const uint32_t* sel;
+    uint32_t nsel;
+    int32_t ignore_zero, label_mode;
+    uint32_t* parent;
+    uint32_t* aux;
+    uint32_t* cnt;             // level 0 of the scan
+    unsigned long long* header;
+    uint32_t* ids;             // null: not written (none given, or too small)
+    svr_component_record* records;
+    unsigned long long rcap;
+};
+
+template <typename T> struct CompElem;
+template <> struct CompElem<uint8_t> {
+    static __device__ __forceinline__ void load4(const uint8_t* p, float v[4]) {
+        const uint32_t q = *reinterpret_cast<const uint32_t*>(p);
+        v[0] = (float)(q & 0xFFu); v[1] = (float)((q >> 8) & 0xFFu); v[2] = (float)((q >> 16) & 0xFFu); v[3] = (float)(q >> 24);
+    }
+};
+template <> struct CompElem<uint16_t> {
+    static __device__ __forceinline__ void load4(const uint16_t* p, float v[4]) {
+        const uint2 q = *reinterpret_cast<const uint2*>(p);
+        v[0] = (float)(q.x & 0xFFFFu); v[1] = (float)(q.x >> 16); v[2] = (float)(q.y & 0xFFFFu); v[3] = (float)(q.y >> 16);
+    }
+};
+template <> struct CompElem<float> {
+    static __device__ __forceinline__ void load4(const float* p, float v[4]) {
+        const float4 q = *reinterpret_cast<const float4*>(p);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    }
+};
+
+// ring slot of voxel r (0 <= r < n <= ring) of the box on one axis
+__device__ __forceinline__ uint32_t comp_slot(uint32_t s0, uint32_t r, uint32_t ring) {
+    const uint32_t s = s0 + r;
+    return s >= ring ? s - ring : s;
+}
+
+// element offset of the row (ry, rz) of the box in the ring: 64-bit, a ring may hold 2^32 elements or more
+__device__ __forceinline__ size_t comp_row_offset(const CompArgs& a, uint32_t ry, uint32_t rz) {
+    const uint32_t sy = comp_slot(a.s0[1], ry, a.ring[1]), sz = comp_slot(a.s0[2], rz, a.ring[2]);
+    return ((size_t)sz * a.ring[1] + sy) * (size_t)a.ring[0];
+}
+
+// ---- init ---------------------------------------------------------------------------------------------------------------
+// LEVEL: the value reaches the level; else the label passes `selected` and ignore_zero.  KEYED: labels split components.
+template <typename T, bool LEVEL, bool KEYED>
+__global__ __launch_bounds__(kCompThreads) void comp_init_kernel(const CompArgs a) {
+    const T* const ring = static_cast<const T*>(a.density);
+    const uint32_t n0 = a.n[0];
+    uint32_t count = 0u, zeros = 0u;                        // this lane's: fewer than 2^32 in a box
+    uint32_t last_label = 0u; bool last_in = false, have_last = false;
+    for (uint32_t unit = blockIdx.x * kCompThreads + threadIdx.x; unit < a.units; unit += gridDim.x * kCompThreads) {
+        const uint32_t row = unit / a.upr, w = unit - row * a.upr;
+        const uint32_t ry = row % a.n[1], rz = row / a.n[1];
+        const int32_t r0 = (int32_t)(4u * w) - (int32_t)a.head;                 // the lane's voxels: r0 .. r0 + 3 of the row
+        const size_t rowoff = comp_row_offset(a, ry, rz);
+        uint32_t lab[4] = {0u, 0u, 0u, 0u};
+        float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        uint32_t have = 0u;
+        bool whole = r0 >= 0 && r0 + 4 <= (int32_t)n0;
+        uint32_t sx0 = 0u;
+        if (whole) {
+            sx0 = comp_slot(a.s0[0], (uint32_t)r0, a.ring[0]);
+            whole = sx0 + 4u <= a.ring[0];                                       // not the slot the wrap seam cuts
+        }
+        if (whole) {
+            have = 0xFu;
+            if (LEVEL) {
+                const T* const p = ring + rowoff + sx0;
+                if ((reinterpret_cast<uintptr_t>(p) & (4u * sizeof(T) - 1u)) == 0u) CompElem<T>::load4(p, val);
+                else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) val[j] = (float)p[j];
+                }
+            } else if (a.labels) {
+                const uint32_t* const p = a.labels + rowoff + sx0;
+                if ((reinterpret_cast<uintptr_t>(p) & 15u) == 0u) {
+                    const uint4 q = *reinterpret_cast<const uint4*>(p);
+                    lab[0] = q.x; lab[1] = q.y; lab[2] = q.z; lab[3] = q.w;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) lab[j] = p[j];
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int32_t r = r0 + j;
+                if (r >= 0 && r < (int32_t)n0) {
+                    have |= 1u << j;
+                    const size_t e = rowoff + comp_slot(a.s0[0], (uint32_t)r, a.ring[0]);
+                    if (LEVEL) val[j] = (float)ring[e];
+                    else if (a.labels) lab[j] = a.labels[e];
+                }
+            }
+        }
+        const uint32_t i0 = row * n0 + (uint32_t)r0;                             // dense index of voxel r0 (wraps where r0 < 0: only r0 + j >= 0 is used)
+        uint32_t start = 0u; bool prev_in = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (!(have & (1u << j))) { prev_in = false; continue; }
+            bool in;
+            if (LEVEL) in = val[j] >= a.level;                                   // a NaN is outside
+            else {
+                if (!have_last || lab[j] != last_label) {
+                    last_in = a.nsel == 0u || ring_in_set(a.sel, a.nsel, lab[j]); last_label = lab[j]; have_last = true;
+                }
+                in = last_in;
+                if (in && a.ignore_zero && lab[j] == 0u) { in = false; ++zeros; }
+            }
+            const uint32_t i = i0 + (uint32_t)j;
+            if (in) {
+                const bool joins = prev_in && (!KEYED || lab[j] == lab[j - (j > 0)]);
+                if (!joins) start = i;
+                a.parent[i] = start;
+                if (KEYED) a.aux[i] = lab[j];
+                ++count;
+            } else a.parent[i] = kUfOutside;
+            prev_in = in;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        count += (uint32_t)__shfl_xor((int)count, d);
+        zeros += (uint32_t)__shfl_xor((int)zeros, d);
+    }
+    if (__lane_id() == 0u) {
+        if (count) atomicAdd(&a.header[1], (unsigned long long)count);
+        if (zeros) atomicAdd(&a.header[13], (unsigned long long)zeros);
+    }
+}
+
+// ---- merge --------------------------------------------------------------------------------------------------------------
+template <bool CONN26, bool KEYED>
+__global__ __launch_bounds__(kCompThreads) void comp_merge_kernel(const CompArgs a) {
+    const uint32_t i = blockIdx.x * kCompThreads + threadIdx.x;
+    if (i < a.voxels) uf_merge_voxel<CONN26, KEYED>(a.parent, a.aux, i, a.n, a.head);
+}
+
+// the sum of v over the workgroup, in every thread
+__device__ __forceinline__ uint32_t comp_block_sum(uint32_t v, uint32_t* part) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
+    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint32_t s = 0u;
+#pragma unroll
+    for (int k = 0; k < kCompThreads / 64; ++k) s += part[k];
+    return s;
+}
+
+// the sum of v over the threads of the workgroup before this one
+__device__ __forceinline__ uint32_t comp_block_exclusive(uint32_t v, uint32_t* part) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t p = (uint32_t)__shfl_up((int)inc, d);
+        if (lane >= (uint32_t)d) inc += p;
+    }
+    if (lane == 63u) part[wave] = inc;
+    __syncthreads();
+    uint32_t before = 0u;
+    for (uint32_t k = 0; k < wave; ++k) before += part[k];
+    return before + inc - v;
+}
+
+// ---- flatten ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kCompThreads) void comp_flatten_kernel(const CompArgs a) {
+    __shared__ uint32_t part[kCompThreads / 64];
+    const uint32_t i = blockIdx.x * kCompThreads + threadIdx.x;
+    uint32_t is_root = 0u;
+    if (i < a.voxels) {
+        const uint32_t p = uf_load(a.parent + i);
+        if (p != kUfOutside) {
+            const uint32_t r = uf_find(a.parent, p);
+            if (r != p) (void)uf_min(a.parent + i, r);
+            is_root = r == i;
+        }
+    }
+    const uint32_t total = comp_block_sum(is_root, part);
+    if (threadIdx.x == 0u) a.cnt[blockIdx.x] = total;
+}
+
+// ---- scan ---------------------------------------------------------------------------------------------------------------
+// out[b] = the sum of block b's kCompScanBlock entries of in[0 .. n)
+__global__ __launch_bounds__(kCompThreads) void comp_scan_sums_kernel(const uint32_t* in, uint32_t n, uint32_t* out) {
+    __shared__ uint32_t part[kCompThreads / 64];
+    const uint32_t i = blockIdx.x * kCompScanBlock + threadIdx.x;
+    const uint32_t total = comp_block_sum(i < n ? in[i] : 0u, part);
+    if (threadIdx.x == 0u) out[blockIdx.x] = total;
+}
+
+// what the top level writes into the header beside N
+struct CompHeader {
+    unsigned long long* header;
+    unsigned long long ids_written, rcap;
+    int32_t off[3], lo[3];
+    uint32_t n[3];
+};
+
+// data[0 .. n): every block's entries become their exclusive prefix inside the block plus base[block] (null: 0).  The top
+// level (`top`: one block holds it all) writes the header but for [1] and [13], which the init pass counted.
+__global__ __launch_bounds__(kCompThreads) void comp_scan_apply_kernel(uint32_t* data, uint32_t n, const uint32_t* base, int top,
+                                                                       const CompHeader h) {
+    __shared__ uint32_t part[kCompThreads / 64];
+    const uint32_t i = blockIdx.x * kCompScanBlock + threadIdx.x;
+    const uint32_t v = i < n ? data[i] : 0u;
+    const uint32_t before = comp_block_exclusive(v, part) + (base ? base[blockIdx.x] : 0u);
+    if (i < n) data[i] = before;
+    if (top && threadIdx.x == kCompThreads - 1) {
+        const unsigned long long N = (unsigned long long)before + v;
+        h.header[0] = N;
+        h.header[2] = h.ids_written;
+        h.header[3] = N <= h.rcap ? N : 0ull;
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+            h.header[4 + ax] = (unsigned long long)(long long)h.off[ax];
+            h.header[7 + ax] = (unsigned long long)(long long)h.lo[ax];
+            h.header[10 + ax] = h.n[ax];
+        }
+        h.header[14] = 0ull; h.header[15] = 0ull;
+    }
+}
+
+// ---- rank ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kCompThreads) void comp_rank_kernel(const CompArgs a) {
+    __shared__ uint32_t part[kCompThreads / 64];
+    const uint32_t i = blockIdx.x * kCompThreads + threadIdx.x;
+    const uint32_t is_root = i < a.voxels && a.parent[i] == i;
+    const uint32_t rank = comp_block_exclusive(is_root, part) + a.cnt[blockIdx.x];
+    if (!is_root) return;
+    a.aux[i] = rank;
+    if (!a.records || a.header[0] > a.rcap) return;
+    const uint32_t rx = i % a.n[0], row = i / a.n[0], ry = row % a.n[1], rz = row / a.n[1];
+    uint32_t label = 0u;
+    if (a.label_mode && a.labels) label = a.labels[comp_row_offset(a, ry, rz) + comp_slot(a.s0[0], rx, a.ring[0])];
+    svr_component_record& r = a.records[rank];
+    r.id = rank + 1u; r.label = label;
+    r.voxels = 0u;
+    r.first[0] = a.lo[0] + (int32_t)rx; r.first[1] = a.lo[1] + (int32_t)ry; r.first[2] = a.lo[2] + (int32_t)rz;
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) { r.sum[ax] = 0u; r.lo[ax] = INT_MAX; r.hi[ax] = INT_MIN; }
+    r.reserved = 0u;
+}
+
+// ---- emit ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kCompThreads) void comp_emit_kernel(const CompArgs a) {
+    const uint32_t i = blockIdx.x * kCompThreads + threadIdx.x;
+    uint32_t id = 0u;
+    if (i < a.voxels) {
+        const uint32_t p = a.parent[i];
+        if (p != kUfOutside) id = a.aux[p] + 1u;
+        if (a.ids) a.ids[i] = id;
+    }
+    if (!a.records || a.header[0] > a.rcap) return;         // the same for every thread of the launch
+    const uint32_t rx = i % a.n[0], row = i / a.n[0], ry = row % a.n[1], rz = row / a.n[1];
+    const uint32_t c[3] = {rx, ry, rz};
+    unsigned long long todo = __ballot(id != 0u);
+    while (todo) {                                          // wave-uniform: a round per component that has lanes left
+        const int leader = __ffsll((long long)todo) - 1;
+        const uint32_t lid = (uint32_t)__shfl((int)id, leader);
+        const bool mine = id == lid;
+        const unsigned long long peers = __ballot(mine);
+        todo &= ~peers;
+        uint32_t cmin[3], cmax[3];
+        unsigned long long sum[3];
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+            cmin[ax] = mine ? c[ax] : 0xFFFFFFFFu; cmax[ax] = mine ? c[ax] : 0u;
+            sum[ax] = mine ? (unsigned long long)((uint32_t)a.rel[ax] + c[ax]) : 0ull;
+        }
+        if (__popcll(peers) > 1) {
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) {
+                    cmin[ax] = min(cmin[ax], (uint32_t)__shfl_xor((int)cmin[ax], d));
+                    cmax[ax] = max(cmax[ax], (uint32_t)__shfl_xor((int)cmax[ax], d));
+                    sum[ax] += __shfl_xor(sum[ax], d);
+                }
+            }
+        }
+        if ((int)__lane_id() == leader) {
+            svr_component_record& r = a.records[lid - 1u];
+            atomicAdd(reinterpret_cast<unsigned long long*>(&r.voxels), (unsigned long long)__popcll(peers));
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                atomicAdd(reinterpret_cast<unsigned long long*>(&r.sum[ax]), sum[ax]);
+                atomicMin(&r.lo[ax], a.lo[ax] + (int32_t)cmin[ax]);
+                atomicMax(&r.hi[ax], a.lo[ax] + (int32_t)cmax[ax]);
+            }
+        }
+    }
+}
+
+template <typename T, bool LEVEL>
+void comp_launch_init(const CompArgs& a, bool keyed, uint32_t blocks, hipStream_t stream) {
+    if constexpr (!LEVEL) {
+        if (keyed) { hipLaunchKernelGGL((comp_init_kernel<T, false, true>), dim3(blocks), dim3(kCompThreads), 0, stream, a); return; }
+    }
+    hipLaunchKernelGGL((comp_init_kernel<T, LEVEL, false>), dim3(blocks), dim3(kCompThreads), 0, stream, a);
+}
+
+}  // namespace
+
+// lo: the first voxel of the box (box and window intersected) in logical voxels of the LOD; plan: comp_plan of its
+// extent, or null for an empty box; scratch: plan->bytes of device memory no other call is using.  Everything was
+// validated by svr_components.
+hipError_t svr_launch_components(const svr_ctx* c, int lod, const int64_t lo[3], const CompPlan* plan, const svr_components_params& cp,
+                                 void* scratch, const svr_components_outputs& out, hipStream_t stream) {
+    const LodStorage& L = c->lod[lod];
+    const svr_lod_state& st = L.state;
+    CompHeader h;
+    h.header = reinterpret_cast<unsigned long long*>(out.header);
+    h.ids_written = 0ull; h.rcap = out.record_capacity;
+    for (int ax = 0; ax < 3; ++ax) { h.off[ax] = st.offset[ax]; h.lo[ax] = 0; h.n[ax] = 0u; }
+    hipError_t e = hipMemsetAsync(h.header, 0, 16 * sizeof(uint64_t), stream);
+    if (e != hipSuccess) return e;
+    if (!plan) {                                            // no voxel: the header alone
+        hipLaunchKernelGGL(comp_scan_apply_kernel, dim3(1), dim3(kCompThreads), 0, stream, nullptr, 0u, nullptr, 1, h);
+        return hipGetLastError();
+    }
+    const CompPlan& p = *plan;
+    char* const base = static_cast<char*>(scratch);
+    const bool is_level = cp.mode == SVR_COMPONENTS_LEVEL;
+    const bool keyed = !is_level && cp.join_labels == 0;
+    const bool ids_fit = out.ids_capacity >= (uint64_t)p.voxels;
+    CompArgs a;
+    a.density = L.density; a.labels = L.labels;
+    for (int ax = 0; ax < 3; ++ax) {
+        a.ring[ax] = (uint32_t)L.ring[ax];
+        a.n[ax] = p.n[ax];
+        a.s0[ax] = (uint32_t)(lo[ax] % (int64_t)L.ring[ax]);
+        a.lo[ax] = (int32_t)lo[ax];
+        a.rel[ax] = (int32_t)(lo[ax] - (int64_t)st.offset[ax]);
+        h.lo[ax] = a.lo[ax]; h.n[ax] = p.n[ax];
+    }
+    a.voxels = p.voxels; a.head = p.head; a.upr = p.upr; a.units = p.units;
+    a.level = cp.level;
+    a.sel = is_level ? nullptr : cp.selected; a.nsel = is_level ? 0u : cp.selected_count;
+    a.ignore_zero = cp.ignore_zero; a.label_mode = is_level ? 0 : 1;
+    a.parent = reinterpret_cast<uint32_t*>(base + p.parent_off);
+    a.aux = reinterpret_cast<uint32_t*>(base + p.aux_off);
+    a.cnt = reinterpret_cast<uint32_t*>(base + p.cnt_off[0]);
+    a.header = h.header;
+    a.ids = ids_fit ? out.ids : nullptr;
+    a.records = out.record_capacity > 0 ? out.records : nullptr;
+    a.rcap = out.record_capacity;
+    h.ids_written = ids_fit ? (unsigned long long)p.voxels : 0ull;
+
+    // init: 256 units of 4 voxels per workgroup and round, 8 workgroups per CU at the most
+    const uint64_t want = ((uint64_t)p.units + kCompThreads - 1) / kCompThreads;
+    const uint64_t most = ring_workgroups(c->device, 8);
+    const uint32_t init_blocks = (uint32_t)(want < most ? want : most);
+    if (!is_level)                             comp_launch_init<uint8_t, false>(a, keyed, init_blocks, stream);   // the density ring is not read
+    else if (c->density_storage == SVR_U8)     comp_launch_init<uint8_t, true>(a, false, init_blocks, stream);
+    else if (c->density_storage == SVR_U16)    comp_launch_init<uint16_t, true>(a, false, init_blocks, stream);
+    else                                       comp_launch_init<float, true>(a, false, init_blocks, stream);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+
+    const dim3 grid(p.count[0]), block(kCompThreads);
+    const bool conn26 = cp.connectivity == 26;
+    if (conn26 && keyed)  hipLaunchKernelGGL((comp_merge_kernel<true, true>), grid, block, 0, stream, a);
+    else if (conn26)      hipLaunchKernelGGL((comp_merge_kernel<true, false>), grid, block, 0, stream, a);
+    else if (keyed)       hipLaunchKernelGGL((comp_merge_kernel<false, true>), grid, block, 0, stream, a);
+    else                  hipLaunchKernelGGL((comp_merge_kernel<false, false>), grid, block, 0, stream, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(comp_flatten_kernel, grid, block, 0, stream, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+
+    uint32_t* lev[kCompMaxLevels];
+    for (int k = 0; k < p.levels; ++k) lev[k] = reinterpret_cast<uint32_t*>(base + p.cnt_off[k]);
+    for (int k = 0; k + 1 < p.levels; ++k) {
+        hipLaunchKernelGGL(comp_scan_sums_kernel, dim3(p.count[k + 1]), block, 0, stream, lev[k], p.count[k], lev[k + 1]);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    const int top = p.levels - 1;
+    hipLaunchKernelGGL(comp_scan_apply_kernel, dim3(1), block, 0, stream, lev[top], p.count[top], nullptr, 1, h);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    for (int k = top - 1; k >= 0; --k) {
+        hipLaunchKernelGGL(comp_scan_apply_kernel, dim3(p.count[k + 1]), block, 0, stream, lev[k], p.count[k], lev[k + 1], 0, h);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    // the count-only call skips the last two kernels; a call whose records cannot fit finds that out on the device
+    if (!a.ids && !a.records) return hipSuccess;
+    hipLaunchKernelGGL(comp_rank_kernel, grid, block, 0, stream, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(comp_emit_kernel, grid, block, 0, stream, a);
+    return hipGetLastError();
+}

@@ -176,6 +176,8 @@ int svr_destroy(svr_ctx* c) {
     for (float* p : svr_ext(c)->tf_retired) (void)hipFree(p);
     if (svr_ext(c)->mesh_scratch) (void)hipFree(svr_ext(c)->mesh_scratch);
     if (svr_ext(c)->mesh_done) (void)hipEventDestroy(svr_ext(c)->mesh_done);
+    if (svr_ext(c)->comp_scratch) (void)hipFree(svr_ext(c)->comp_scratch);
+    if (svr_ext(c)->comp_done) (void)hipEventDestroy(svr_ext(c)->comp_done);
     if (c->dbg_dev) (void)hipFree(c->dbg_dev);
     for (auto& t : c->tile_orders) if (t.dev) (void)hipFree(t.dev);
     for (auto& t : c->cost_orders) {

@@ -50,6 +50,11 @@ hipError_t svr_launch_objects(const svr_ctx* c, int lod, const int64_t lo[3], co
 struct MeshPlan;
 hipError_t svr_launch_mesh(const svr_ctx* c, int lod, const int64_t lo[3], const MeshPlan* plan, int mode, float level,
                            const uint32_t* sel, uint32_t nsel, void* scratch, const svr_mesh_outputs& out, hipStream_t stream);
+// components_kernels.hip.  lo as for the mesh; plan: comp_plan (components_plan.h) of the box's extent, null for an empty
+// box; scratch: plan->bytes of the context's components scratch; everything checked by svr_components.
+struct CompPlan;
+hipError_t svr_launch_components(const svr_ctx* c, int lod, const int64_t lo[3], const CompPlan* plan, const svr_components_params& cp,
+                                 void* scratch, const svr_components_outputs& out, hipStream_t stream);
 
 // the context as svr_create really allocates it ------------------------------------------------------------------------
 // The state of svr_set_transfer_function, svr_set_interpolation and svr_set_cut_planes (svr_modes.hip).  Like the colour
@@ -75,6 +80,12 @@ struct svr_ctx_ext : svr_ctx {
     size_t mesh_scratch_bytes = 0;
     hipEvent_t mesh_done = nullptr;
     bool mesh_pending = false;             // mesh_done has been recorded
+    // svr_components (svr_modes.hip): its scratch, kept and ordered in the same way
+    std::mutex comp_mu;
+    void* comp_scratch = nullptr;
+    size_t comp_scratch_bytes = 0;
+    hipEvent_t comp_done = nullptr;
+    bool comp_pending = false;
 };
 // (every svr_ctx* of the ABI comes from svr_create)
 inline svr_ctx_ext* svr_ext(svr_ctx* c) { return static_cast<svr_ctx_ext*>(c); }

@@ -1,13 +1,14 @@
 // The render modes and passes of the C ABI (include/svr.h) beside the march: slices, slabs, composite and iso renders,
-// histograms, object tables and surface meshes, and the three setters of the state they share (svr_ctx_ext,
+// histograms, object tables, surface meshes and connected components, and the three setters of the state they share (svr_ctx_ext,
 // svr_host.h).  Each entry point checks its arguments and hands the launch of its kernel unit to draw_ordered; svr_mesh
-// besides keeps the scratch memory its kernels work in.
+// and svr_components besides keep the scratch memory their kernels work in.
 #include <math.h>
 
 #include <algorithm>
 
 #include "svr_host.h"
 #include "mesh_plan.h"
+#include "components_plan.h"
 
 // What svr_slice, svr_slab, svr_composite and svr_iso check first, in this order (who: the entry point's name, the
 // prefix of its error texts; args_ok: its own null test), and the frame with band_h defaulted to one band.
@@ -188,6 +189,53 @@ int svr_mesh(svr_ctx* c, const svr_mesh_params* mp, const svr_mesh_outputs* out,
         // recorded behind whatever was enqueued, a failed chain's kernels too: the next call waits for them
         const hipError_t r = hipEventRecord(x->mesh_done, s);
         if (r == hipSuccess) x->mesh_pending = true;
+        return e != hipSuccess ? e : r;
+    });
+}
+
+int svr_components(svr_ctx* c, const svr_components_params* cp, const svr_components_outputs* out, void* stream) {
+    SVR_REQUIRE(c && cp && out && out->header, "svr_components: null argument");
+    { const int rc = box_lod("svr_components", c, cp->lod); if (rc) return rc; }
+    SVR_REQUIRE(cp->mode == SVR_COMPONENTS_LABELS || cp->mode == SVR_COMPONENTS_LEVEL, "svr_components: unknown mode");
+    SVR_REQUIRE(cp->connectivity == 6 || cp->connectivity == 26, "svr_components: connectivity must be 6 or 26");
+    if (cp->mode == SVR_COMPONENTS_LEVEL) SVR_REQUIRE(cp->level == cp->level, "svr_components: level must not be NaN");
+    SVR_REQUIRE(out->ids || out->ids_capacity == 0, "svr_components: NULL ids with a non-zero ids_capacity");
+    SVR_REQUIRE(out->records || out->record_capacity == 0, "svr_components: NULL records with a non-zero record_capacity");
+    int64_t lo[3], n[3];
+    { const int rc = box_window("svr_components", c, cp->lod, cp->use_box, cp->box_off, cp->box_shape, cp->selected, cp->selected_count, lo, n); if (rc) return rc; }
+    CompPlan plan;
+    bool too_many = false;
+    const bool any = comp_plan(n, n[0] > 0 ? comp_head(lo[0], (uint32_t)c->lod[cp->lod].ring[0]) : 0u, plan, &too_many);
+    SVR_REQUIRE(!too_many, "svr_components: more than SVR_COMPONENTS_MAX_VOXELS voxels");
+
+    svr_ctx_ext* x = svr_ext(c);
+    std::lock_guard<std::mutex> lock(x->comp_mu);
+    {
+        DeviceGuard guard(c->device);
+        if (!x->comp_done) SVR_HIP_TRY(hipEventCreateWithFlags(&x->comp_done, hipEventDisableTiming));
+        if (any && plan.bytes > x->comp_scratch_bytes) {
+            // the call that may still be working in the old scratch ends first
+            if (x->comp_pending) SVR_HIP_TRY(hipEventSynchronize(x->comp_done));
+            if (x->comp_scratch) (void)hipFree(x->comp_scratch);
+            x->comp_scratch = nullptr; x->comp_scratch_bytes = 0;
+            if (hipMalloc(&x->comp_scratch, (size_t)plan.bytes) != hipSuccess) {
+                x->comp_scratch = nullptr;
+                (void)hipGetLastError();
+                svr_set_error("svr_components: out of device memory for the scratch of " + std::to_string(plan.bytes) + " bytes");
+                return SVR_ERR_NOMEM;
+            }
+            x->comp_scratch_bytes = (size_t)plan.bytes;
+        }
+    }
+    const int lod = cp->lod;
+    const svr_components_params params = *cp;
+    return draw_ordered(c, stream, "svr_launch_components", [&](hipStream_t s) {
+        hipError_t e = x->comp_pending ? hipStreamWaitEvent(s, x->comp_done, 0) : hipSuccess;
+        if (e != hipSuccess) return e;
+        e = svr_launch_components(c, lod, lo, any ? &plan : nullptr, params, x->comp_scratch, *out, s);
+        // recorded behind whatever was enqueued, a failed chain's kernels too: the next call waits for them
+        const hipError_t r = hipEventRecord(x->comp_done, s);
+        if (r == hipSuccess) x->comp_pending = true;
         return e != hipSuccess ? e : r;
     });
 }
