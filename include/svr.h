@@ -994,6 +994,74 @@ typedef struct svr_components_outputs { /* DEVICE pointers; header required */
 } svr_components_outputs;
 int  svr_components(svr_ctx* ctx, const svr_components_params* params, const svr_components_outputs* out, void* stream);
 
+/* ---- exact Euclidean distance transform of the resident rings: how thick is an object, where is its deepest point, what
+ * is left of it after eroding by r voxels, what does it touch after dilating by r?  (No counterpart in the reference; what a
+ * viewer answers today by reading the window back and running scipy.ndimage.distance_transform_edt on the CPU.)  An
+ * addition within ABI version 9: one new symbol and two new structs, nothing older changes.  The squared distances are
+ * integers in voxel units, computed in HBM axis by axis; nothing is copied to the host.
+ * Defined HERE (numpy restatement: tests/distance_twin.py):
+ *   box B       [lo, lo + n): exactly svr_components' (use_box, box_off, box_shape, the ring-slot rule; the micro-block
+ *               copy is never read).  A window of None and a box that misses the window give an empty B.
+ *   inside(p)   exactly svr_components', with the same two mode constants: SVR_COMPONENTS_LEVEL (v >= level, a NaN is
+ *               outside; selected and ignore_zero are not read) or SVR_COMPONENTS_LABELS (selected, selected_count,
+ *               ignore_zero; the dropped label-0 voxels are counted in header[13]).  There is no connectivity and no join.
+ *   targets, sources
+ *               invert == 0: the targets are the inside voxels of B, the sources the voxels of B that are not inside.
+ *               invert != 0: the two are swapped: the distance of every outside voxel to the nearest inside one.
+ *               invert == 0 and border != 0: every lattice point beyond B is a source too ("everything outside box
+ *               and window is outside", as in svr_mesh), so an object that the box or the window cuts is thin there.
+ *               border == 0: nothing beyond B is known (the convention of scipy).  invert != 0: border is not read.
+ *   d2          dense int32 [n_z][n_y][n_x] over B (not ring-shaped).  For a target p the minimum over the sources q of
+ *               (p_x - q_x)^2 + (p_y - q_y)^2 + (p_z - q_z)^2; for a voxel that is no target 0; for a target where
+ *               there is no source at all SVR_DISTANCE_FAR.  Written, whole, only when d2_capacity >= n_x n_y n_z;
+ *               else not touched, and the call is the count-only call.
+ *   limits      every extent of B is at most SVR_DISTANCE_MAX_EXTENT, so that d2 <= 3 * 2^28 fits int32 below
+ *               SVR_DISTANCE_FAR, and B holds at most 2^30 voxels.
+ *   header      16 x uint64_t:
+ *                 [0] targets                    [1] inside voxels
+ *                 [2] elements of d2 written     [3] the largest d2 over the targets that are not FAR (0 if none)
+ *                 [4..6] the window offset (x, y, z) of the LOD the call used, as int64 bit patterns
+ *                 [7..9] B's first voxel (x, y, z), as int64 bit patterns      [10..12] n_x, n_y, n_z
+ *                 [13] label-0 voxels dropped by ignore_zero
+ *                 [14] the linear index (z n_y + y) n_x + x in B of the first voxel, in (z, y, x) order, that attains
+ *                      [3] (0 if none)
+ *                 [15] targets whose d2 is FAR
+ *               An empty B gives [7..12] = 0.  The header is overwritten by every call.  A capacity of 0 with a NULL
+ *               array is the count-only call: it runs the pass over the ring alone, fills [0], [1], [4..13] and leaves
+ *               [2], [3], [14], [15] at 0; so does a call whose capacity is too small.
+ * Everything is an integer and fully specified, whatever algorithm computes it: two calls on the same rings give
+ * identical bytes.  Distances are in voxels of the chosen LOD (no anisotropic spacing); the nearest source itself is
+ * not returned (it is not unique at ties).  Ordered like svr_components: it waits for published uploads, and later
+ * uploads are ordered behind it.  Enqueued on `stream`; asynchronous.  The call works in scratch memory owned by the
+ * context (8 bytes and 1 bit per voxel of B, grown on demand, SVR_ERR_NOMEM when it cannot be, released by svr_destroy);
+ * a call is ordered behind the previous svr_distance of the same context, whatever its stream.  The material, the
+ * variant, the interpolation and the cut planes are not read.
+ * SVR_ERR_INVALID, with nothing enqueued and the outputs untouched, for: a NULL ctx, params, outputs or header; lod out of
+ * range; an unknown mode; a NaN level (SVR_COMPONENTS_LEVEL); selected == NULL with selected_count > 0; a negative
+ * box_shape component (with use_box != 0); an extent of B above SVR_DISTANCE_MAX_EXTENT; more than
+ * SVR_DISTANCE_MAX_VOXELS voxels in B; a NULL array with a non-zero capacity. */
+#define SVR_DISTANCE_FAR 0x7FFFFFFF
+#define SVR_DISTANCE_MAX_EXTENT 16384
+#define SVR_DISTANCE_MAX_VOXELS (1u << 30)
+typedef struct svr_distance_params {
+    int32_t lod;
+    int32_t use_box;                    /* 0: the LOD's whole resident window */
+    int32_t box_off[3], box_shape[3];   /* LOD-l logical voxels, shader order: svr_histogram_params' */
+    int32_t mode;                       /* SVR_COMPONENTS_LABELS or SVR_COMPONENTS_LEVEL */
+    float   level;                      /* SVR_COMPONENTS_LEVEL: inside is v >= level; not NaN */
+    const uint32_t* selected;           /* SVR_COMPONENTS_LABELS: DEVICE, sorted ascending; NULL when the count is 0 */
+    uint32_t selected_count;            /* 0: every label */
+    int32_t  ignore_zero;               /* SVR_COMPONENTS_LABELS: != 0: label-0 voxels are outside; counted in header[13] */
+    int32_t  invert;                    /* != 0: targets and sources are swapped */
+    int32_t  border;                    /* invert == 0: != 0: every lattice point beyond B is a source */
+} svr_distance_params;
+typedef struct svr_distance_outputs {   /* DEVICE pointers; header required */
+    int32_t*  d2;                       /* d2_capacity elements */
+    uint64_t  d2_capacity;              /* 0: d2 may be NULL */
+    uint64_t* header;                   /* 16 */
+} svr_distance_outputs;
+int  svr_distance(svr_ctx* ctx, const svr_distance_params* params, const svr_distance_outputs* out, void* stream);
+
 /* ---- sync */
 int  svr_sync(svr_ctx* ctx);                 /* both streams idle */
 int  svr_sync_uploads(svr_ctx* ctx);         /* upload stream idle */

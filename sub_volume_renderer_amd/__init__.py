@@ -17,6 +17,7 @@ from ._wobject import FrameRegion, HistogramResult, IsoResult, ObjectTable, Rend
 from ._wrapping_buffer import WrappingBuffer, subtract_rois
 from .mesh import SurfaceMesh
 from .components import ComponentLabels
+from .distance import DistanceField
 
 __all__ = [
     "SubVolume",
@@ -37,6 +38,7 @@ __all__ = [
     "ObjectTable",
     "SurfaceMesh",
     "ComponentLabels",
+    "DistanceField",
     "subtract_rois",
     # display-side output of a render (pygfx's job in the reference)
     "compose",

@@ -322,6 +322,35 @@ COMPONENTS_LABELS, COMPONENTS_LEVEL = 0, 1          # SVR_COMPONENTS_*
 COMPONENTS_MAX_VOXELS = 1 << 30                     # SVR_COMPONENTS_MAX_VOXELS
 COMPONENT_RECORD_BYTES = 80                         # sizeof(svr_component_record)
 
+
+class DistanceParams(C.Structure):
+    _fields_ = [
+        ("lod", C.c_int32),
+        ("use_box", C.c_int32),
+        ("box_off", C.c_int32 * 3),
+        ("box_shape", C.c_int32 * 3),
+        ("mode", C.c_int32),
+        ("level", C.c_float),
+        ("selected", C.c_void_p),
+        ("selected_count", C.c_uint32),
+        ("ignore_zero", C.c_int32),
+        ("invert", C.c_int32),
+        ("border", C.c_int32),
+    ]
+
+
+class DistanceOutputs(C.Structure):
+    _fields_ = [
+        ("d2", C.c_void_p),
+        ("d2_capacity", C.c_uint64),
+        ("header", C.c_void_p),
+    ]
+
+
+DISTANCE_FAR = 0x7FFFFFFF                           # SVR_DISTANCE_FAR
+DISTANCE_MAX_EXTENT = 16384                         # SVR_DISTANCE_MAX_EXTENT
+DISTANCE_MAX_VOXELS = 1 << 30                       # SVR_DISTANCE_MAX_VOXELS
+
 INTERPOLATIONS = {"nearest": 0, "linear": 1}      # SVR_INTERP_*
 CUT_MODES = {"ANY": 0, "ALL": 1}                  # SVR_CUT_*
 MAX_CUT_PLANES = 8                                # SVR_MAX_CUT_PLANES
@@ -385,6 +414,7 @@ SIGNATURES = {
     "svr_objects": (C.c_int, [C.c_void_p, C.POINTER(ObjectsParams), C.POINTER(ObjectsOutputs), C.c_void_p]),
     "svr_mesh": (C.c_int, [C.c_void_p, C.POINTER(MeshParams), C.POINTER(MeshOutputs), C.c_void_p]),
     "svr_components": (C.c_int, [C.c_void_p, C.POINTER(ComponentsParams), C.POINTER(ComponentsOutputs), C.c_void_p]),
+    "svr_distance": (C.c_int, [C.c_void_p, C.POINTER(DistanceParams), C.POINTER(DistanceOutputs), C.c_void_p]),
     "svr_sync": (C.c_int, [C.c_void_p]),
     "svr_sync_uploads": (C.c_int, [C.c_void_p]),
     "svr_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),

@@ -1223,5 +1223,24 @@ class SubVolume(_HasWorld):
         return components(self, level=level, labels=labels, background=background, join=join, connectivity=connectivity, lod=lod,
                           box=box, stream=stream)
 
+    # -- how thick, where is the deepest point, what is left after eroding by r? -----------
+    def distance(self, level=None, labels=None, background: bool = False, invert: bool = False, border: bool = True, signed: bool = False,
+                 lod: int = 0, box=None, stream=None):
+        """The exact Euclidean distance transform of what LOD ``lod`` holds in HBM, computed on the device (definition:
+        ``svr_distance`` in include/svr.h) -> :class:`~.distance.DistanceField`: the squared distance, in LOD voxels, of
+        every inside voxel to the nearest voxel that is not inside, as int32, with the largest one and where it lies.
+        ``level``, ``labels`` and ``background`` decide what is inside exactly as in :meth:`components`.
+        ``border=True`` counts everything beyond box and window as not inside, so an object that the box cuts is thin
+        there; ``border=False`` knows nothing beyond the box (the convention of scipy), and an object that fills the box
+        is ``FAR`` from everything.  ``invert=True`` gives the distance of every voxel that is NOT inside to the nearest
+        inside one (``border`` is not read).  ``signed=True`` makes both calls (``invert`` is not read) and returns
+        ``squared`` = d2(inside) - d2(outside): positive inside, negative outside; a side without any source stays
+        ``+FAR`` or ``-FAR``.  ``level`` together with ``labels`` raises ``ValueError``.  ``box`` means what it means in
+        :meth:`histogram`.  The call SYNCHRONISES twice: it counts first, allocates exactly, then emits."""
+        from .distance import distance
+
+        return distance(self, level=level, labels=labels, background=background, invert=invert, border=border, signed=signed, lod=lod,
+                        box=box, stream=stream)
+
     def synchronize(self):
         N.check(N.lib().svr_sync(self._rings.handle), "svr_sync")

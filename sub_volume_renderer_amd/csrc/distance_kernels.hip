@@ -1,0 +1,327 @@
+// Exact Euclidean distance transform of the resident rings (svr_distance, include/svr.h): squared distances, in voxels,
+// of the targets of a box of one LOD's window to the nearest source, axis by axis.  gfx950.
+//
+// The chain (layout of the scratch: distance_plan.h), every kernel a plain launch on the caller's stream; no workgroup
+// waits for another inside a launch and nothing spins on a flag:
+//   init     the one pass over the rings, with the loads and the seam handling of the components' init pass.  A lane
+//            owns 4 consecutive ring slots at a multiple of 4: one 16-byte load of the label or float32 ring, 8 bytes of
+//            a u16 ring, 4 of a u8 ring where the slot is whole, inside the row and aligned, else its elements one by one
+//            (a row's head and tail, the slot the ring's wrap seam cuts).  Its 4 source bits are a nibble; 8 adjacent
+//            lanes OR theirs together with three shuffles and one of them stores the word.  Counts the inside voxels and
+//            the dropped zeros, one atomic each per wave.
+//   header   one thread: the words of the header that need no distance.  The count-only call ends here.
+//   x        a thread per voxel: the squared distance to the nearest source bit of its row, from count-leading and
+//            count-trailing-zero operations on the row's words (distance_plan.h: dist_row_nearest), into d2.
+//   y, z     a thread per column, a wave's lanes adjacent in x, so that every load and store of one position of the
+//            column is one contiguous run per wave: the lower envelope of parabolas (distance_scan.h), in place in d2,
+//            its stack in the scratch, the last 16 entries pushed also in LDS, where most pops find what they need.
+//            Linear in the column's length whatever the data.
+//            The z pass ends the chain: it takes the minimum with the squared distance to the nearest lattice point
+//            beyond the box (border: the smallest of the six face distances plus one, squared: that point lies straight
+//            across the nearest face), and reduces header [3], [14], [15]: shuffles first, then one 64-bit atomic maximum
+//            per wave on (d2 << 32) | (0xFFFFFFFF - index), and one add.
+//   finish   one thread: unpacks that maximum into header [3] and [14].
+// Every store is an ordinary vector store; the only atomics are the counters of the header.
+#include "svr_host.h"
+#include "distance_plan.h"
+#include "distance_scan.h"
+#include "ring_pieces.h"
+
+namespace {
+
+constexpr int kDistThreads = 256;      // init and x pass
+constexpr int kDistColumnThreads = 64; // y and z pass: one wave, so that few columns still spread over the CUs
+constexpr uint32_t kDistRingEntries = 16;  // of a column's stack kept in LDS (distance_scan.h: DistRing): 8 KiB per workgroup
+
+struct DistArgs {
+    const void* density;
+    const uint32_t* labels;    // null: every label reads as 0
+    uint32_t ring[3];
+    uint32_t n[3];             // extent of the box B
+    uint32_t s0[3];            // ring slot of B's first voxel
+    uint32_t voxels, head, upr, wpr, units;
+    float level;
+    const uint32_t* sel;
+    uint32_t nsel;
+    int32_t ignore_zero, invert, border;
+    uint32_t* bits;
+    DistEntry* stack;
+    int32_t* d2;
+    unsigned long long* header;
+};
+
+template <typename T> struct DistElem;
+template <> struct DistElem<uint8_t> {
+    static __device__ __forceinline__ void load4(const uint8_t* p, float v[4]) {
+        const uint32_t q = *reinterpret_cast<const uint32_t*>(p);
+        v[0] = (float)(q & 0xFFu); v[1] = (float)((q >> 8) & 0xFFu); v[2] = (float)((q >> 16) & 0xFFu); v[3] = (float)(q >> 24);
+    }
+};
+template <> struct DistElem<uint16_t> {
+    static __device__ __forceinline__ void load4(const uint16_t* p, float v[4]) {
+        const uint2 q = *reinterpret_cast<const uint2*>(p);
+        v[0] = (float)(q.x & 0xFFFFu); v[1] = (float)(q.x >> 16); v[2] = (float)(q.y & 0xFFFFu); v[3] = (float)(q.y >> 16);
+    }
+};
+template <> struct DistElem<float> {
+    static __device__ __forceinline__ void load4(const float* p, float v[4]) {
+        const float4 q = *reinterpret_cast<const float4*>(p);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    }
+};
+
+// ring slot of voxel r (0 <= r < n <= ring) of the box on one axis
+__device__ __forceinline__ uint32_t dist_slot(uint32_t s0, uint32_t r, uint32_t ring) {
+    const uint32_t s = s0 + r;
+    return s >= ring ? s - ring : s;
+}
+
+// element offset of the row (ry, rz) of the box in the ring: 64-bit, a ring may hold 2^32 elements or more
+__device__ __forceinline__ size_t dist_row_offset(const DistArgs& a, uint32_t ry, uint32_t rz) {
+    const uint32_t sy = dist_slot(a.s0[1], ry, a.ring[1]), sz = dist_slot(a.s0[2], rz, a.ring[2]);
+    return ((size_t)sz * a.ring[1] + sy) * (size_t)a.ring[0];
+}
+
+// ---- init ---------------------------------------------------------------------------------------------------------------
+// LEVEL: the value reaches the level; else the label passes `selected` and ignore_zero.  a.units is a multiple of 8 and so
+// is every stride of the loop, so the 8 lanes that share a word of bits enter and leave the loop together.
+template <typename T, bool LEVEL>
+__global__ __launch_bounds__(kDistThreads) void dist_init_kernel(const DistArgs a) {
+    const T* const ring = static_cast<const T*>(a.density);
+    const uint32_t n0 = a.n[0];
+    uint32_t count = 0u, zeros = 0u;                        // this lane's: fewer than 2^32 in a box
+    uint32_t last_label = 0u; bool last_in = false, have_last = false;
+    for (uint32_t unit = blockIdx.x * kDistThreads + threadIdx.x; unit < a.units; unit += gridDim.x * kDistThreads) {
+        const uint32_t row = unit / a.upr, w = unit - row * a.upr;
+        const uint32_t ry = row % a.n[1], rz = row / a.n[1];
+        const int32_t r0 = (int32_t)(4u * w) - (int32_t)a.head;                 // the lane's voxels: r0 .. r0 + 3 of the row
+        const size_t rowoff = dist_row_offset(a, ry, rz);
+        uint32_t lab[4] = {0u, 0u, 0u, 0u};
+        float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        uint32_t have = 0u;
+        bool whole = r0 >= 0 && r0 + 4 <= (int32_t)n0;
+        uint32_t sx0 = 0u;
+        if (whole) {
+            sx0 = dist_slot(a.s0[0], (uint32_t)r0, a.ring[0]);
+            whole = sx0 + 4u <= a.ring[0];                                       // not the slot the wrap seam cuts
+        }
+        if (whole) {
+            have = 0xFu;
+            if (LEVEL) {
+                const T* const p = ring + rowoff + sx0;
+                if ((reinterpret_cast<uintptr_t>(p) & (4u * sizeof(T) - 1u)) == 0u) DistElem<T>::load4(p, val);
+                else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) val[j] = (float)p[j];
+                }
+            } else if (a.labels) {
+                const uint32_t* const p = a.labels + rowoff + sx0;
+                if ((reinterpret_cast<uintptr_t>(p) & 15u) == 0u) {
+                    const uint4 q = *reinterpret_cast<const uint4*>(p);
+                    lab[0] = q.x; lab[1] = q.y; lab[2] = q.z; lab[3] = q.w;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) lab[j] = p[j];
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int32_t r = r0 + j;
+                if (r >= 0 && r < (int32_t)n0) {
+                    have |= 1u << j;
+                    const size_t e = rowoff + dist_slot(a.s0[0], (uint32_t)r, a.ring[0]);
+                    if (LEVEL) val[j] = (float)ring[e];
+                    else if (a.labels) lab[j] = a.labels[e];
+                }
+            }
+        }
+        uint32_t nibble = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (!(have & (1u << j))) continue;
+            bool in;
+            if (LEVEL) in = val[j] >= a.level;                                   // a NaN is outside
+            else {
+                if (!have_last || lab[j] != last_label) {
+                    last_in = a.nsel == 0u || ring_in_set(a.sel, a.nsel, lab[j]); last_label = lab[j]; have_last = true;
+                }
+                in = last_in;
+                if (in && a.ignore_zero && lab[j] == 0u) { in = false; ++zeros; }
+            }
+            if (in) ++count;
+            if (in == (a.invert != 0)) nibble |= 1u << j;                        // a source
+        }
+        uint32_t word = nibble << (4u * (w & 7u));
+        word |= (uint32_t)__shfl_xor((int)word, 1);
+        word |= (uint32_t)__shfl_xor((int)word, 2);
+        word |= (uint32_t)__shfl_xor((int)word, 4);
+        if ((w & 7u) == 0u) a.bits[(size_t)row * a.wpr + (w >> 3)] = word;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        count += (uint32_t)__shfl_xor((int)count, d);
+        zeros += (uint32_t)__shfl_xor((int)zeros, d);
+    }
+    if (__lane_id() == 0u) {
+        if (count) atomicAdd(&a.header[1], (unsigned long long)count);
+        if (zeros) atomicAdd(&a.header[13], (unsigned long long)zeros);
+    }
+}
+
+// ---- header and finish ----------------------------------------------------------------------------------------------------
+struct DistHeader {
+    unsigned long long* header;
+    unsigned long long voxels, written;
+    int32_t invert;
+    int32_t off[3], lo[3];
+    uint32_t n[3];
+};
+
+// the header but for [1] and [13], which the init pass counted, and [3], [14], [15], which the z pass reduces
+__global__ void dist_header_kernel(const DistHeader h) {
+    if (blockIdx.x != 0u || threadIdx.x != 0u) return;
+    const unsigned long long inside = h.header[1];
+    h.header[0] = h.invert ? h.voxels - inside : inside;
+    h.header[2] = h.written;
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        h.header[4 + ax] = (unsigned long long)(long long)h.off[ax];
+        h.header[7 + ax] = (unsigned long long)(long long)h.lo[ax];
+        h.header[10 + ax] = h.n[ax];
+    }
+}
+
+// header[3] holds the maximum of (d2 << 32) | (0xFFFFFFFF - index) over the targets that are not FAR, or 0
+__global__ void dist_finish_kernel(unsigned long long* header) {
+    if (blockIdx.x != 0u || threadIdx.x != 0u) return;
+    const unsigned long long key = header[3];
+    header[3] = key >> 32;
+    header[14] = key ? 0xFFFFFFFFull - (key & 0xFFFFFFFFull) : 0ull;
+}
+
+// ---- x ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kDistThreads) void dist_x_kernel(const DistArgs a) {
+    const uint32_t i = blockIdx.x * kDistThreads + threadIdx.x;
+    if (i >= a.voxels) return;
+    const uint32_t row = i / a.n[0], rx = i - row * a.n[0];
+    a.d2[i] = dist_row_nearest(a.bits + (size_t)row * a.wpr, a.wpr, rx + a.head);
+}
+
+// ---- y and z ------------------------------------------------------------------------------------------------------------
+// FINAL: the z pass, else the y pass.  columns = voxels / length.
+template <bool FINAL>
+__global__ __launch_bounds__(kDistColumnThreads) void dist_column_kernel(const DistArgs a, uint32_t columns) {
+    __shared__ DistEntry slots[kDistRingEntries * kDistColumnThreads];     // slot j of lane l at [j * 64 + l]: no bank conflicts
+    const DistRing<kDistRingEntries> ring(slots + threadIdx.x, kDistColumnThreads);
+    const uint32_t c = blockIdx.x * kDistColumnThreads + threadIdx.x;
+    const uint32_t n0 = a.n[0], n1 = a.n[1], n2 = a.n[2];
+    uint32_t far = 0u;
+    unsigned long long key = 0ull;
+    if (c < columns) {
+        const uint32_t x = c % n0, other = c / n0;           // FINAL: other is y; else z
+        const uint32_t base = FINAL ? c : other * n1 * n0 + x;
+        const uint32_t stride = FINAL ? n0 * n1 : n0, length = FINAL ? n2 : n1;
+        int32_t* const col = a.d2 + base;
+        if (FINAL) {
+            // the squared distance to the nearest lattice point beyond the box is ((face distance) + 1)^2; without a
+            // border nothing lies there
+            const bool border = a.border != 0 && a.invert == 0;
+            const uint32_t fxy = min(min(x + 1u, n0 - x), min(other + 1u, n1 - other));
+            dist_scan_column(col, stride, length, a.stack + c, columns, ring, [&](uint32_t u, int32_t v) {
+                if (border && v != 0) {
+                    const uint32_t f = min(fxy, min(u + 1u, n2 - u));
+                    v = min(v, (int32_t)(f * f));
+                }
+                col[(size_t)u * stride] = v;
+                if (v == kDistFar) ++far;
+                else if (v != 0) {
+                    // u runs downward: an equal value at a smaller index replaces the key, as its low half is larger
+                    const unsigned long long k = ((unsigned long long)(uint32_t)v << 32) | (0xFFFFFFFFu - (base + u * stride));
+                    if (k > key) key = k;
+                }
+            });
+        } else {
+            dist_scan_column(col, stride, length, a.stack + c, columns, ring, [&](uint32_t u, int32_t v) { col[(size_t)u * stride] = v; });
+        }
+    }
+    if (FINAL) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            far += (uint32_t)__shfl_xor((int)far, d);
+            const unsigned long long o = __shfl_xor(key, d);
+            if (o > key) key = o;
+        }
+        if (__lane_id() == 0u) {
+            if (key) atomicMax(&a.header[3], key);
+            if (far) atomicAdd(&a.header[15], (unsigned long long)far);
+        }
+    }
+}
+
+}  // namespace
+
+// lo: the first voxel of the box (box and window intersected) in logical voxels of the LOD; plan: dist_plan of its
+// extent, or null for an empty box; scratch: plan->bytes of device memory no other call is using.  Everything was
+// validated by svr_distance.
+hipError_t svr_launch_distance(const svr_ctx* c, int lod, const int64_t lo[3], const DistPlan* plan, const svr_distance_params& dp,
+                               void* scratch, const svr_distance_outputs& out, hipStream_t stream) {
+    const LodStorage& L = c->lod[lod];
+    const svr_lod_state& st = L.state;
+    DistHeader h;
+    h.header = reinterpret_cast<unsigned long long*>(out.header);
+    h.voxels = 0ull; h.written = 0ull; h.invert = dp.invert != 0;
+    for (int ax = 0; ax < 3; ++ax) { h.off[ax] = st.offset[ax]; h.lo[ax] = 0; h.n[ax] = 0u; }
+    hipError_t e = hipMemsetAsync(h.header, 0, 16 * sizeof(uint64_t), stream);
+    if (e != hipSuccess) return e;
+    if (!plan) {                                            // no voxel: the header alone
+        hipLaunchKernelGGL(dist_header_kernel, dim3(1), dim3(1), 0, stream, h);
+        return hipGetLastError();
+    }
+    const DistPlan& p = *plan;
+    char* const base = static_cast<char*>(scratch);
+    const bool is_level = dp.mode == SVR_COMPONENTS_LEVEL;
+    const bool fits = out.d2_capacity >= (uint64_t)p.voxels;
+    DistArgs a;
+    a.density = L.density; a.labels = L.labels;
+    for (int ax = 0; ax < 3; ++ax) {
+        a.ring[ax] = (uint32_t)L.ring[ax];
+        a.n[ax] = p.n[ax];
+        a.s0[ax] = (uint32_t)(lo[ax] % (int64_t)L.ring[ax]);
+        h.lo[ax] = (int32_t)lo[ax]; h.n[ax] = p.n[ax];
+    }
+    a.voxels = p.voxels; a.head = p.head; a.upr = p.upr; a.wpr = p.wpr; a.units = p.units;
+    a.level = dp.level;
+    a.sel = is_level ? nullptr : dp.selected; a.nsel = is_level ? 0u : dp.selected_count;
+    a.ignore_zero = is_level ? 0 : dp.ignore_zero; a.invert = dp.invert != 0; a.border = dp.border != 0;
+    a.bits = reinterpret_cast<uint32_t*>(base + p.bits_off);
+    a.stack = reinterpret_cast<DistEntry*>(base + p.stack_off);
+    a.d2 = fits ? out.d2 : nullptr;
+    a.header = h.header;
+    h.voxels = p.voxels; h.written = fits ? (unsigned long long)p.voxels : 0ull;
+
+    // init: 256 units of 4 voxels per workgroup and round, 8 workgroups per CU at the most
+    const uint64_t want = ((uint64_t)p.units + kDistThreads - 1) / kDistThreads;
+    const uint64_t most = ring_workgroups(c->device, 8);
+    const dim3 init_grid((uint32_t)(want < most ? want : most)), block(kDistThreads);
+    if (!is_level)                             hipLaunchKernelGGL((dist_init_kernel<uint8_t, false>), init_grid, block, 0, stream, a);   // the density ring is not read
+    else if (c->density_storage == SVR_U8)     hipLaunchKernelGGL((dist_init_kernel<uint8_t, true>), init_grid, block, 0, stream, a);
+    else if (c->density_storage == SVR_U16)    hipLaunchKernelGGL((dist_init_kernel<uint16_t, true>), init_grid, block, 0, stream, a);
+    else                                       hipLaunchKernelGGL((dist_init_kernel<float, true>), init_grid, block, 0, stream, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(dist_header_kernel, dim3(1), dim3(1), 0, stream, h);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (!a.d2) return hipSuccess;                           // the count-only call, and a capacity that is too small
+
+    hipLaunchKernelGGL(dist_x_kernel, dim3((p.voxels + kDistThreads - 1u) / kDistThreads), block, 0, stream, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const dim3 column_block(kDistColumnThreads);
+    hipLaunchKernelGGL((dist_column_kernel<false>), dim3((p.columns[0] + kDistColumnThreads - 1u) / kDistColumnThreads), column_block, 0,
+                       stream, a, p.columns[0]);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL((dist_column_kernel<true>), dim3((p.columns[1] + kDistColumnThreads - 1u) / kDistColumnThreads), column_block, 0,
+                       stream, a, p.columns[1]);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(dist_finish_kernel, dim3(1), dim3(1), 0, stream, h.header);
+    return hipGetLastError();
+}

@@ -178,6 +178,8 @@ int svr_destroy(svr_ctx* c) {
     if (svr_ext(c)->mesh_done) (void)hipEventDestroy(svr_ext(c)->mesh_done);
     if (svr_ext(c)->comp_scratch) (void)hipFree(svr_ext(c)->comp_scratch);
     if (svr_ext(c)->comp_done) (void)hipEventDestroy(svr_ext(c)->comp_done);
+    if (svr_ext(c)->dist_scratch) (void)hipFree(svr_ext(c)->dist_scratch);
+    if (svr_ext(c)->dist_done) (void)hipEventDestroy(svr_ext(c)->dist_done);
     if (c->dbg_dev) (void)hipFree(c->dbg_dev);
     for (auto& t : c->tile_orders) if (t.dev) (void)hipFree(t.dev);
     for (auto& t : c->cost_orders) {

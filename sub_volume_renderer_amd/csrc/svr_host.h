@@ -55,6 +55,11 @@ hipError_t svr_launch_mesh(const svr_ctx* c, int lod, const int64_t lo[3], const
 struct CompPlan;
 hipError_t svr_launch_components(const svr_ctx* c, int lod, const int64_t lo[3], const CompPlan* plan, const svr_components_params& cp,
                                  void* scratch, const svr_components_outputs& out, hipStream_t stream);
+// distance_kernels.hip.  lo as for the mesh; plan: dist_plan (distance_plan.h) of the box's extent, null for an empty box;
+// scratch: plan->bytes of the context's distance scratch; everything checked by svr_distance.
+struct DistPlan;
+hipError_t svr_launch_distance(const svr_ctx* c, int lod, const int64_t lo[3], const DistPlan* plan, const svr_distance_params& dp,
+                               void* scratch, const svr_distance_outputs& out, hipStream_t stream);
 
 // the context as svr_create really allocates it ------------------------------------------------------------------------
 // The state of svr_set_transfer_function, svr_set_interpolation and svr_set_cut_planes (svr_modes.hip).  Like the colour
@@ -86,6 +91,12 @@ struct svr_ctx_ext : svr_ctx {
     size_t comp_scratch_bytes = 0;
     hipEvent_t comp_done = nullptr;
     bool comp_pending = false;
+    // svr_distance (svr_modes.hip): its scratch, kept and ordered in the same way
+    std::mutex dist_mu;
+    void* dist_scratch = nullptr;
+    size_t dist_scratch_bytes = 0;
+    hipEvent_t dist_done = nullptr;
+    bool dist_pending = false;
 };
 // (every svr_ctx* of the ABI comes from svr_create)
 inline svr_ctx_ext* svr_ext(svr_ctx* c) { return static_cast<svr_ctx_ext*>(c); }

@@ -1,7 +1,7 @@
 // The render modes and passes of the C ABI (include/svr.h) beside the march: slices, slabs, composite and iso renders,
-// histograms, object tables, surface meshes and connected components, and the three setters of the state they share (svr_ctx_ext,
-// svr_host.h).  Each entry point checks its arguments and hands the launch of its kernel unit to draw_ordered; svr_mesh
-// and svr_components besides keep the scratch memory their kernels work in.
+// histograms, object tables, surface meshes, connected components and distance transforms, and the three setters of the
+// state they share (svr_ctx_ext, svr_host.h).  Each entry point checks its arguments and hands the launch of its kernel
+// unit to draw_ordered; svr_mesh, svr_components and svr_distance besides keep the scratch memory their kernels work in.
 #include <math.h>
 
 #include <algorithm>
@@ -9,6 +9,7 @@
 #include "svr_host.h"
 #include "mesh_plan.h"
 #include "components_plan.h"
+#include "distance_plan.h"
 
 // What svr_slice, svr_slab, svr_composite and svr_iso check first, in this order (who: the entry point's name, the
 // prefix of its error texts; args_ok: its own null test), and the frame with band_h defaulted to one band.
@@ -236,6 +237,53 @@ int svr_components(svr_ctx* c, const svr_components_params* cp, const svr_compon
         // recorded behind whatever was enqueued, a failed chain's kernels too: the next call waits for them
         const hipError_t r = hipEventRecord(x->comp_done, s);
         if (r == hipSuccess) x->comp_pending = true;
+        return e != hipSuccess ? e : r;
+    });
+}
+
+int svr_distance(svr_ctx* c, const svr_distance_params* dp, const svr_distance_outputs* out, void* stream) {
+    SVR_REQUIRE(c && dp && out && out->header, "svr_distance: null argument");
+    { const int rc = box_lod("svr_distance", c, dp->lod); if (rc) return rc; }
+    SVR_REQUIRE(dp->mode == SVR_COMPONENTS_LABELS || dp->mode == SVR_COMPONENTS_LEVEL, "svr_distance: unknown mode");
+    if (dp->mode == SVR_COMPONENTS_LEVEL) SVR_REQUIRE(dp->level == dp->level, "svr_distance: level must not be NaN");
+    SVR_REQUIRE(out->d2 || out->d2_capacity == 0, "svr_distance: NULL d2 with a non-zero d2_capacity");
+    int64_t lo[3], n[3];
+    { const int rc = box_window("svr_distance", c, dp->lod, dp->use_box, dp->box_off, dp->box_shape, dp->selected, dp->selected_count, lo, n); if (rc) return rc; }
+    DistPlan plan;
+    int refused = 0;
+    const bool any = dist_plan(n, n[0] > 0 ? dist_head(lo[0], (uint32_t)c->lod[dp->lod].ring[0]) : 0u, plan, &refused);
+    SVR_REQUIRE(refused != 1, "svr_distance: an extent of more than SVR_DISTANCE_MAX_EXTENT voxels");
+    SVR_REQUIRE(refused != 2, "svr_distance: more than SVR_DISTANCE_MAX_VOXELS voxels");
+
+    svr_ctx_ext* x = svr_ext(c);
+    std::lock_guard<std::mutex> lock(x->dist_mu);
+    {
+        DeviceGuard guard(c->device);
+        if (!x->dist_done) SVR_HIP_TRY(hipEventCreateWithFlags(&x->dist_done, hipEventDisableTiming));
+        // the count-only call works in the bits alone, but sizes the scratch for the call that follows it
+        if (any && plan.bytes > x->dist_scratch_bytes) {
+            // the call that may still be working in the old scratch ends first
+            if (x->dist_pending) SVR_HIP_TRY(hipEventSynchronize(x->dist_done));
+            if (x->dist_scratch) (void)hipFree(x->dist_scratch);
+            x->dist_scratch = nullptr; x->dist_scratch_bytes = 0;
+            if (hipMalloc(&x->dist_scratch, (size_t)plan.bytes) != hipSuccess) {
+                x->dist_scratch = nullptr;
+                (void)hipGetLastError();
+                svr_set_error("svr_distance: out of device memory for the scratch of " + std::to_string(plan.bytes) + " bytes");
+                return SVR_ERR_NOMEM;
+            }
+            x->dist_scratch_bytes = (size_t)plan.bytes;
+        }
+    }
+    const int lod = dp->lod;
+    const svr_distance_params params = *dp;
+    return draw_ordered(c, stream, "svr_launch_distance", [&](hipStream_t s) {
+        hipError_t e = x->dist_pending ? hipStreamWaitEvent(s, x->dist_done, 0) : hipSuccess;
+        if (e != hipSuccess) return e;
+        e = svr_launch_distance(c, lod, lo, any ? &plan : nullptr, params, x->dist_scratch, *out, s);
+        // recorded behind whatever was enqueued, a failed chain's kernels too: the next call waits for them
+        const hipError_t r = hipEventRecord(x->dist_done, s);
+        if (r == hipSuccess) x->dist_pending = true;
         return e != hipSuccess ? e : r;
     });
 }
