@@ -14,6 +14,7 @@ import pytest
 from scipy import ndimage
 
 from components_twin import RECORD, components_twin, label_components, neighbour_offsets
+from odd_ring_scenes import plan_cases
 from sub_volume_renderer_amd import ComponentLabels, SubVolume, SubVolumeMaterial, _native as N
 from sub_volume_renderer_amd.components import components_arguments
 
@@ -308,6 +309,10 @@ def test_components_plan(driver):
     cases = [(nx, 3, 2, h) for nx in (1, 3, 4, 5, 65) for h in (0, 1, 3)]
     cases += [(block, 1, 1, 0), (block + 1, 1, 1, 0), (block, block, 1, 2), (block, block, 1 + 1, 0), (16, block * block // 16, 1, 0),
               (16, block * block // 16 + 1, 1, 0), (1 << 10, 1 << 10, 1 << 10, 0)]
+    # the windows and boxes of tests/test_gpu_odd_rings.py: head is the ring slot modulo 4 of the first voxel
+    odd = [(*n, lo[0] % ring[0] & 3) for ring, off, lo, n in plan_cases()]
+    assert {c[3] for c in odd} == {0, 1, 2, 3} and {1, 3, 63} <= {c[0] for c in odd}
+    cases += odd
     _, res = plans(driver, cases)
     for c, p in zip(cases, res):
         nx, ny, nz, head = c

@@ -11,6 +11,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from odd_ring_scenes import plan_cases
+
 HEADER_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sub_volume_renderer_amd", "csrc")
 
 # per line "rx ry rz  ox oy oz  lox loy loz  nx ny nz  bytes_per_voxel per_slot slot_base workgroups min_share" ->
@@ -197,6 +199,25 @@ def test_shares(driver):
     assert P["rows"] == 400 and P["rows_per_wg"] == (2 ** 32 - 1) // (2 ** 24 - 1) == 256
     wrapped = case((2 ** 24 + 5, 24, 24), (9, 20, 1), (2 ** 24 - 1, 20, 20), OBJ[1], workgroups=1, base=NO_POINTER)
     assert len(check(wrapped, plans(driver, [wrapped])[0], mark=False)) == 4
+
+
+def test_windows_and_boxes_of_the_odd_ring_scenes(driver):
+    """What tests/test_gpu_odd_rings.py asks the plan for: rings of 63, 21, 42, 36, 40, 3 and 1 voxels along x, windows
+    of a whole ring's worth that begin inside it, one at 2^31 - 1 - shape, and the boxes of the 63-voxel ring; the
+    histogram on each storage and the objects pass, with and without a label ring to align to."""
+    cases = []
+    for ring, off, lo, n in plan_cases():
+        for consts, base in ((HIST[1], ALIGNED), (HIST[2], ALIGNED), (HIST[4], ALIGNED), (OBJ[1], ALIGNED), (OBJ[4], NO_POINTER)):
+            cases.append(case(ring, lo, n, consts, base=base, off=off))
+    assert len(cases) == 5 * (7 * 5 + 2 + 34)
+    spr_by_ring = {}
+    for c, plan in zip(cases, plans(driver, cases)):
+        pieces = check(c, plan)
+        assert len(pieces) == np.prod([1 + (c["lo"][a] % c["ring"][a] + c["n"][a] > c["ring"][a]) for a in range(3)])
+        if c["n"] == c["ring"]:
+            spr_by_ring.setdefault((c["ring"][0], c["per_slot"]), set()).update(P["spr"] for P in pieces)
+    # a row of one voxel takes one slot whatever comes before it; a row of 3 voxels may lie in two slots of 4
+    assert spr_by_ring[(1, 4)] == {1} and spr_by_ring[(1, 16)] == {1} and 2 in spr_by_ring[(3, 4)]
 
 
 def test_every_box_of_a_small_ring(driver):
