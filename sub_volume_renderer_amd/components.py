@@ -4,12 +4,12 @@ which labels the blobs of a level set (``level``) or the pieces of the segmentat
 
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _native as N
+from ._box_pass import box_pass, level32
 from ._wobject import finest_box, label_ids, lod_center_to_data
 
 __all__ = ["ComponentLabels", "components", "components_arguments"]
@@ -104,13 +104,7 @@ def components_arguments(level, labels, background, join, connectivity):
     if level is None:
         ids = label_ids(labels) if labels is not None else None
         return N.COMPONENTS_LABELS, ids, 0.0, 0 if background else 1, 1 if join else 0, int(connectivity)
-    if isinstance(level, (bool, np.bool_)) or not isinstance(level, (int, float, np.integer, np.floating)):
-        raise ValueError("components: level must be a number")
-    with np.errstate(over="ignore"):
-        level32 = float(np.float32(level))
-    if level32 != level32:
-        raise ValueError("components: level must not be NaN")
-    return N.COMPONENTS_LEVEL, None, level32, 0, 0, int(connectivity)
+    return N.COMPONENTS_LEVEL, None, level32("components", level), 0, 0, int(connectivity)
 
 
 def components(volume, level=None, labels=None, background=False, join=False, connectivity=6, lod: int = 0, box=None,
@@ -118,33 +112,14 @@ def components(volume, level=None, labels=None, background=False, join=False, co
     """``SubVolume.components``: see there."""
     import torch
 
-    mode, ids, level32, ignore_zero, join_labels, connectivity = components_arguments(level, labels, background, join, connectivity)
-    lod = volume._check_lod(lod)
     cp = N.ComponentsParams()
-    cp.lod, cp.mode, cp.level = lod, mode, level32
-    cp.ignore_zero, cp.join_labels, cp.connectivity = ignore_zero, join_labels, connectivity
-    volume._box_params(cp, lod, box)
-    scale = tuple(float(v) for v in volume.wrapping_buffers[lod].scale_factor)
-    handle = volume.prepare()
-    dev = torch.device("cuda", volume._rings.device)
-    side = torch.cuda.ExternalStream(int(stream), device=dev) if stream is not None else None
-    sel = volume._upload_ids(cp, ids, dev, side)                       # held until the calls below have run
-    stream = volume._plane_stream(stream)
+    cp.mode, ids, cp.level, cp.ignore_zero, cp.join_labels, cp.connectivity = components_arguments(level, labels, background, join, connectivity)
+    lod, scale, dev, c_call = box_pass(volume, "svr_components", cp, lod, box, ids, stream)
 
     def call(dense, records):
-        header = torch.empty(16, dtype=torch.int64, device=dev)
-        if side is not None:
-            torch.cuda.current_stream(dev).synchronize()               # the allocator's memory may still be in use there
-        co = N.ComponentsOutputs(None if dense is None else dense.data_ptr(), 0 if dense is None else dense.numel(),
-                                 None if records is None else records.data_ptr(), 0 if records is None else records.shape[0],
-                                 header.data_ptr())
-        N.check(N.lib().svr_components(handle, C.byref(cp), C.byref(co), C.c_void_p(stream)), "svr_components")
-        if side is not None:
-            for t in (dense, records, header):
-                if t is not None:
-                    t.record_stream(side)
-            side.synchronize()
-        return [int(v) for v in header.cpu().numpy()]                  # synchronises; coordinates read as int64: signed already
+        co = lambda header: N.ComponentsOutputs(None if dense is None else dense.data_ptr(), 0 if dense is None else dense.numel(),
+                                                None if records is None else records.data_ptr(), 0 if records is None else records.shape[0], header)
+        return c_call(16, co, dense, records)
 
     head = call(None, None)                                            # count ...
     while True:
@@ -156,7 +131,6 @@ def components(volume, level=None, labels=None, background=False, join=False, co
         head = call(dense, records if count else None)                 # ... emit
         if (head[0], (head[12], head[11], head[10])) == (count, shape):
             break                                                      # else an upload or a new window came in between: allocate again
-    del sel
     # record fields by their 4- and 8-byte columns (svr_component_record)
     r64 = records.view(torch.int64) if count else torch.empty((0, N.COMPONENT_RECORD_BYTES // 8), dtype=torch.int64, device=dev)
     voxels = r64[:, 1].contiguous()

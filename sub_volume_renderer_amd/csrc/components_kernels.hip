@@ -4,12 +4,11 @@
 // The chain (layout of the scratch: components_plan.h), every kernel a plain launch on the caller's stream; no
 // workgroup waits for another inside a launch and nothing spins on a flag:
 //   init     the one pass over the rings.  A lane owns 4 consecutive ring slots at a multiple of 4 (components_plan.h:
-//            head): one 16-byte load of the label or float32 ring, 8 bytes of a u16 ring, 4 of a u8 ring where the slot is
-//            whole, inside the row and aligned, else its elements one by one (a row's head and tail, the slot the
-//            ring's wrap seam cuts).  Writes parent[i]: kUfOutside for a voxel that is outside, else the first voxel of
-//            the run of connecting voxels it belongs to among the lane's 4, so x neighbours inside a lane are linked for
-//            free; and, where labels split components, the label into aux[i], so that no later pass reads a wrapped ring
-//            row.  Counts the inside voxels and the dropped zeros, one atomic each per wave.
+//            head): a unit of box_units.h, which states how it is loaded, at a row's ends and at the ring's wrap seam
+//            too, and what inside() is.  Writes parent[i]: kUfOutside for a voxel that is outside, else the first voxel
+//            of the run of connecting voxels it belongs to among the lane's 4, so x neighbours inside a lane are linked
+//            for free; and, where labels split components, the label into aux[i], so that no later pass reads a wrapped
+//            ring row.  Counts the inside voxels and the dropped zeros, one atomic each per wave.
 //   merge    a thread per voxel joins it with the neighbours before it (components_uf.h: uf_merge_voxel, the rules of
 //            the union-find are stated there); 6- and 26-connectivity, with and without labels, are compile-time variants.
 //   flatten  parent[i] = root(i), and the number of roots among each workgroup's voxels: level 0 of the scan.
@@ -27,7 +26,7 @@
 #include "svr_host.h"
 #include "components_plan.h"
 #include "components_uf.h"
-#include "ring_pieces.h"
+#include "box_units.h"
 
 namespace {
 
@@ -56,38 +55,6 @@ struct CompArgs {
     unsigned long long rcap;
 };
 
-template <typename T> struct CompElem;
-template <> struct CompElem<uint8_t> {
-    static __device__ __forceinline__ void load4(const uint8_t* p, float v[4]) {
-        const uint32_t q = *reinterpret_cast<const uint32_t*>(p);
-        v[0] = (float)(q & 0xFFu); v[1] = (float)((q >> 8) & 0xFFu); v[2] = (float)((q >> 16) & 0xFFu); v[3] = (float)(q >> 24);
-    }
-};
-template <> struct CompElem<uint16_t> {
-    static __device__ __forceinline__ void load4(const uint16_t* p, float v[4]) {
-        const uint2 q = *reinterpret_cast<const uint2*>(p);
-        v[0] = (float)(q.x & 0xFFFFu); v[1] = (float)(q.x >> 16); v[2] = (float)(q.y & 0xFFFFu); v[3] = (float)(q.y >> 16);
-    }
-};
-template <> struct CompElem<float> {
-    static __device__ __forceinline__ void load4(const float* p, float v[4]) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    }
-};
-
-// ring slot of voxel r (0 <= r < n <= ring) of the box on one axis
-__device__ __forceinline__ uint32_t comp_slot(uint32_t s0, uint32_t r, uint32_t ring) {
-    const uint32_t s = s0 + r;
-    return s >= ring ? s - ring : s;
-}
-
-// element offset of the row (ry, rz) of the box in the ring: 64-bit, a ring may hold 2^32 elements or more
-__device__ __forceinline__ size_t comp_row_offset(const CompArgs& a, uint32_t ry, uint32_t rz) {
-    const uint32_t sy = comp_slot(a.s0[1], ry, a.ring[1]), sz = comp_slot(a.s0[2], rz, a.ring[2]);
-    return ((size_t)sz * a.ring[1] + sy) * (size_t)a.ring[0];
-}
-
 // ---- init ---------------------------------------------------------------------------------------------------------------
 // LEVEL: the value reaches the level; else the label passes `selected` and ignore_zero.  KEYED: labels split components.
 template <typename T, bool LEVEL, bool KEYED>
@@ -95,66 +62,23 @@ __global__ __launch_bounds__(kCompThreads) void comp_init_kernel(const CompArgs 
     const T* const ring = static_cast<const T*>(a.density);
     const uint32_t n0 = a.n[0];
     uint32_t count = 0u, zeros = 0u;                        // this lane's: fewer than 2^32 in a box
-    uint32_t last_label = 0u; bool last_in = false, have_last = false;
+    BoxInside cache = {};
     for (uint32_t unit = blockIdx.x * kCompThreads + threadIdx.x; unit < a.units; unit += gridDim.x * kCompThreads) {
         const uint32_t row = unit / a.upr, w = unit - row * a.upr;
         const uint32_t ry = row % a.n[1], rz = row / a.n[1];
         const int32_t r0 = (int32_t)(4u * w) - (int32_t)a.head;                 // the lane's voxels: r0 .. r0 + 3 of the row
-        const size_t rowoff = comp_row_offset(a, ry, rz);
+        const size_t rowoff = box_row_offset(a, ry, rz);
         uint32_t lab[4] = {0u, 0u, 0u, 0u};
-        float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        uint32_t have = 0u;
-        bool whole = r0 >= 0 && r0 + 4 <= (int32_t)n0;
-        uint32_t sx0 = 0u;
-        if (whole) {
-            sx0 = comp_slot(a.s0[0], (uint32_t)r0, a.ring[0]);
-            whole = sx0 + 4u <= a.ring[0];                                       // not the slot the wrap seam cuts
-        }
-        if (whole) {
-            have = 0xFu;
-            if (LEVEL) {
-                const T* const p = ring + rowoff + sx0;
-                if ((reinterpret_cast<uintptr_t>(p) & (4u * sizeof(T) - 1u)) == 0u) CompElem<T>::load4(p, val);
-                else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) val[j] = (float)p[j];
-                }
-            } else if (a.labels) {
-                const uint32_t* const p = a.labels + rowoff + sx0;
-                if ((reinterpret_cast<uintptr_t>(p) & 15u) == 0u) {
-                    const uint4 q = *reinterpret_cast<const uint4*>(p);
-                    lab[0] = q.x; lab[1] = q.y; lab[2] = q.z; lab[3] = q.w;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) lab[j] = p[j];
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int32_t r = r0 + j;
-                if (r >= 0 && r < (int32_t)n0) {
-                    have |= 1u << j;
-                    const size_t e = rowoff + comp_slot(a.s0[0], (uint32_t)r, a.ring[0]);
-                    if (LEVEL) val[j] = (float)ring[e];
-                    else if (a.labels) lab[j] = a.labels[e];
-                }
-            }
-        }
+        float val[4] = {0.0f, 0.0f, 0.0f, 0.0f}; uint32_t have = 0u;
+        BOX_GATHER(T, LEVEL, a, ring, n0, rowoff, r0, val, lab, have);
         const uint32_t i0 = row * n0 + (uint32_t)r0;                             // dense index of voxel r0 (wraps where r0 < 0: only r0 + j >= 0 is used)
         uint32_t start = 0u; bool prev_in = false;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (!(have & (1u << j))) { prev_in = false; continue; }
             bool in;
-            if (LEVEL) in = val[j] >= a.level;                                   // a NaN is outside
-            else {
-                if (!have_last || lab[j] != last_label) {
-                    last_in = a.nsel == 0u || ring_in_set(a.sel, a.nsel, lab[j]); last_label = lab[j]; have_last = true;
-                }
-                in = last_in;
-                if (in && a.ignore_zero && lab[j] == 0u) { in = false; ++zeros; }
-            }
+            BOX_INSIDE(in, LEVEL, cache, val[j], lab[j], a.level, a.nsel == 0u || ring_in_set(a.sel, a.nsel, lab[j]),
+                       BOX_DROP_ZERO(in, lab[j], a.ignore_zero, zeros));
             const uint32_t i = i0 + (uint32_t)j;
             if (in) {
                 const bool joins = prev_in && (!KEYED || lab[j] == lab[j - (j > 0)]);
@@ -166,15 +90,7 @@ __global__ __launch_bounds__(kCompThreads) void comp_init_kernel(const CompArgs 
             prev_in = in;
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        count += (uint32_t)__shfl_xor((int)count, d);
-        zeros += (uint32_t)__shfl_xor((int)zeros, d);
-    }
-    if (__lane_id() == 0u) {
-        if (count) atomicAdd(&a.header[1], (unsigned long long)count);
-        if (zeros) atomicAdd(&a.header[13], (unsigned long long)zeros);
-    }
+    BOX_WAVE_ADD2(&a.header[1], count, &a.header[13], zeros);
 }
 
 // ---- merge --------------------------------------------------------------------------------------------------------------
@@ -281,7 +197,7 @@ __global__ __launch_bounds__(kCompThreads) void comp_rank_kernel(const CompArgs 
     if (!a.records || a.header[0] > a.rcap) return;
     const uint32_t rx = i % a.n[0], row = i / a.n[0], ry = row % a.n[1], rz = row / a.n[1];
     uint32_t label = 0u;
-    if (a.label_mode && a.labels) label = a.labels[comp_row_offset(a, ry, rz) + comp_slot(a.s0[0], rx, a.ring[0])];
+    if (a.label_mode && a.labels) label = a.labels[box_row_offset(a, ry, rz) + box_slot(a.s0[0], rx, a.ring[0])];
     svr_component_record& r = a.records[rank];
     r.id = rank + 1u; r.label = label;
     r.voxels = 0u;

@@ -11,13 +11,15 @@
 //           From the rank pass on: at a root, the rank of its component (its number minus one).
 //   scan    level 0 holds one u32 per block of kCompScanBlock voxels, the roots among them; level k + 1 holds the sums
 //           of level k's blocks of kCompScanBlock entries, until one block holds a whole level.
-// The init pass reads a row in units of 4 ring slots at a multiple of 4, as svr_mesh does: voxel rx of a row is element
-// rx + head of it, head (0 .. 3) being the ring slot of the box's first voxel modulo 4, and a row has upr units.  The
-// voxels of one unit are linked along x by the init pass itself (comp_x_implied).
+// The init pass reads a row in the units of box_units.h, 4 ring slots at a multiple of 4: voxel rx of a row is element
+// rx + head of it, head (0 .. 3; box_head) being the ring slot of the box's first voxel modulo 4, and a row has upr
+// units.  The voxels of one unit are linked along x by the init pass itself (comp_x_implied).
 // 8 bytes per voxel, and 4 bytes per 256 voxels for the scan.
 #pragma once
 
 #include <stdint.h>
+
+#include "box_units.h"
 
 #ifdef __HIPCC__
 #define COMP_FN __host__ __device__ __forceinline__
@@ -42,14 +44,11 @@ struct CompPlan {
     uint64_t bytes;                    // of scratch in all
 };
 
-// the ring slot modulo 4 of the box's first voxel (lo_x >= 0: a window offset is never negative)
-inline uint32_t comp_head(int64_t lo_x, uint32_t ring_x) { return (uint32_t)(lo_x % (int64_t)ring_x) & 3u; }
-
 // voxels rx - 1 and rx of a row (rx >= 1) lie in one unit: where they connect, the init pass has linked them already
 COMP_FN bool comp_x_implied(uint32_t rx, uint32_t head) { return ((rx + head) & 3u) != 0u; }
 
-// n: the extent of the box, box and window already intersected.  false: the box is empty (an n <= 0) or has more than
-// kCompMaxVoxels voxels (*too_many says which).
+// n: the extent of the box, box and window already intersected; head: box_head of its first voxel.  false: the box is
+// empty (an n <= 0) or has more than kCompMaxVoxels voxels (*too_many says which).
 inline bool comp_plan(const int64_t n[3], uint32_t head, CompPlan& p, bool* too_many = nullptr) {
     if (too_many) *too_many = false;
     if (n[0] <= 0 || n[1] <= 0 || n[2] <= 0) return false;
@@ -63,13 +62,7 @@ inline bool comp_plan(const int64_t n[3], uint32_t head, CompPlan& p, bool* too_
     p.head = head;
     p.upr = (p.n[0] + head + 3u) / 4u;
     p.units = p.upr * p.n[1] * p.n[2];           // upr <= n[0] but for rows of one voxel, where it is 1 too
-    p.levels = 1;
-    p.count[0] = (p.voxels + kCompScanBlock - 1u) / kCompScanBlock;
-    for (int k = 1; k < kCompMaxLevels; ++k) p.count[k] = 0;
-    while (p.count[p.levels - 1] > kCompScanBlock) {
-        p.count[p.levels] = (p.count[p.levels - 1] + kCompScanBlock - 1u) / kCompScanBlock;
-        ++p.levels;
-    }
+    p.levels = box_scan_levels((p.voxels + kCompScanBlock - 1u) / kCompScanBlock, kCompScanBlock, kCompMaxLevels, p.count);
     p.parent_off = 0;
     p.aux_off = voxels * 4u;
     uint64_t at = voxels * 8u;

@@ -7,11 +7,11 @@
 // Layout.  Voxel (rx, ry, rz) of a box of n voxels per axis has the dense index i = (rz n_y + ry) n_x + rx < 2^30; row
 // (ry, rz) has the number rz n_y + ry.
 //   bits    one bit per voxel, set where the voxel is a SOURCE, in u32 words along x: wpr words per row.  The init pass
-//           reads a row in units of 4 ring slots at a multiple of 4, as svr_components does: voxel rx of a row is element
-//           e = rx + head of it, head (0 .. 3) being the ring slot of the box's first voxel modulo 4.  Bit e & 31 of word
-//           e >> 5 of the row belongs to element e, so a unit is one nibble of one word and 8 adjacent lanes make a word
-//           with three shuffles, without an atomic.  A row has upr = 8 wpr units; the bits of the elements before the
-//           first voxel and behind the last are 0.
+//           reads a row in the units of box_units.h, 4 ring slots at a multiple of 4: voxel rx of a row is element
+//           e = rx + head of it, head (0 .. 3; box_head) being the ring slot of the box's first voxel modulo 4.  Bit
+//           e & 31 of word e >> 5 of the row belongs to element e, so a unit is one nibble of one word and 8 adjacent
+//           lanes make a word with three shuffles, without an atomic.  A row has upr = 8 wpr units; the bits of the
+//           elements before the first voxel and behind the last are 0.
 //   stack   one DistEntry (distance_scan.h: 8 bytes) per voxel: the stacks of the column pass that is running, entry k
 //           of column c at index k * columns + c, so that the lanes of a wave, which hold adjacent columns, touch
 //           adjacent entries.  The y pass has n_x n_z columns of n_y entries, the z pass n_x n_y columns of n_z.
@@ -37,11 +37,9 @@ struct DistPlan {
     uint64_t bytes;                    // of scratch in all
 };
 
-// the ring slot modulo 4 of the box's first voxel (lo_x >= 0: a window offset is never negative)
-inline uint32_t dist_head(int64_t lo_x, uint32_t ring_x) { return (uint32_t)(lo_x % (int64_t)ring_x) & 3u; }
-
-// n: the extent of the box, box and window already intersected.  false: the box is empty (an n <= 0), has an extent of
-// more than kDistMaxExtent (*refused = 1) or more than kDistMaxVoxels voxels (*refused = 2).
+// n: the extent of the box, box and window already intersected; head: box_head (box_units.h) of its first voxel.
+// false: the box is empty (an n <= 0), has an extent of more than kDistMaxExtent (*refused = 1) or more than
+// kDistMaxVoxels voxels (*refused = 2).
 inline bool dist_plan(const int64_t n[3], uint32_t head, DistPlan& p, int* refused = nullptr) {
     if (refused) *refused = 0;
     if (n[0] <= 0 || n[1] <= 0 || n[2] <= 0) return false;

@@ -3,10 +3,9 @@
 //
 // The chain (layout of the scratch: mesh_plan.h), every kernel a plain launch on the caller's stream:
 //   inside     the one pass over the rings.  A lane owns 4 consecutive bits of a row of the bit map, which are 4
-//              consecutive ring slots at a multiple of 4 (mesh_plan.h: head): one 16-byte load of the label or float32
-//              ring, 8 bytes of a u16 ring, 4 of a u8 ring where the slot is whole, inside the row and aligned, else its
-//              elements one by one (a row's head and tail, the slot the ring's wrap seam cuts).  8 lanes join their bits
-//              into one u32.  Rows wrap in y and z by their ring slot.  Counts the inside voxels (header[7]).
+//              consecutive ring slots at a multiple of 4 (mesh_plan.h: head): a unit of box_units.h, which states how
+//              it is loaded, at a row's ends and at the ring's wrap seam too, and what inside() is.  8 lanes join
+//              their bits into one u32.  Rows wrap in y and z by their ring slot.  Counts the inside voxels (header[7]).
 //   classify   bit operations only: a thread makes one word of 16 cells from 17 bits of each of the 4 voxel rows
 //              (y, y + 1) x (z, z + 1); the x neighbour is the same bits shifted by one.  Rows outside the box read as
 //              zero without touching memory.  Writes the word and its two counts (active cells, crossing edges).
@@ -19,7 +18,7 @@
 // All stores are ordinary vector stores; the one atomic is the u64 add of the inside-voxel count, once per wave.
 #include "svr_host.h"
 #include "mesh_plan.h"
-#include "ring_pieces.h"
+#include "box_units.h"
 
 namespace {
 
@@ -48,38 +47,6 @@ struct MeshArgs {
     unsigned long long vcap, tcap;
 };
 
-template <typename T> struct MeshElem;
-template <> struct MeshElem<uint8_t> {
-    static __device__ __forceinline__ void load4(const uint8_t* p, float v[4]) {
-        const uint32_t q = *reinterpret_cast<const uint32_t*>(p);
-        v[0] = (float)(q & 0xFFu); v[1] = (float)((q >> 8) & 0xFFu); v[2] = (float)((q >> 16) & 0xFFu); v[3] = (float)(q >> 24);
-    }
-};
-template <> struct MeshElem<uint16_t> {
-    static __device__ __forceinline__ void load4(const uint16_t* p, float v[4]) {
-        const uint2 q = *reinterpret_cast<const uint2*>(p);
-        v[0] = (float)(q.x & 0xFFFFu); v[1] = (float)(q.x >> 16); v[2] = (float)(q.y & 0xFFFFu); v[3] = (float)(q.y >> 16);
-    }
-};
-template <> struct MeshElem<float> {
-    static __device__ __forceinline__ void load4(const float* p, float v[4]) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    }
-};
-
-// ring slot of voxel r (0 <= r < n <= ring) of the box on one axis
-__device__ __forceinline__ uint32_t mesh_slot(uint32_t s0, uint32_t r, uint32_t ring) {
-    const uint32_t s = s0 + r;
-    return s >= ring ? s - ring : s;
-}
-
-// element offset of the row (ry, rz) of the box in the ring: 64-bit, a ring may hold 2^32 elements or more
-__device__ __forceinline__ size_t mesh_row_offset(const MeshArgs& a, uint32_t ry, uint32_t rz) {
-    const uint32_t sy = mesh_slot(a.s0[1], ry, a.ring[1]), sz = mesh_slot(a.s0[2], rz, a.ring[2]);
-    return ((size_t)sz * a.ring[1] + sy) * (size_t)a.ring[0];
-}
-
 // ---- inside: the bit map ----------------------------------------------------------------------------------------------
 // LEVEL false: the label is one of sel; true: the value reaches the level
 template <typename T, bool LEVEL>
@@ -88,7 +55,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_inside_kernel(const MeshArg
     const T* const ring = static_cast<const T*>(a.density);
     const uint32_t n0 = a.n[0];
     uint32_t count = 0u;                                    // this lane's inside voxels: fewer than 2^32 in a box
-    uint32_t last_label = 0u; bool last_in = false, have_last = false;
+    BoxInside cache = {};
     // 8 lanes make one u32 of the bit map; the trip count is the same for the whole workgroup
     for (uint32_t u0 = blockIdx.x * (kMeshThreads / 8u); u0 < a.bit_words; u0 += gridDim.x * (kMeshThreads / 8u)) {
         const uint32_t unit = u0 + (tid >> 3);
@@ -98,58 +65,15 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_inside_kernel(const MeshArg
         const int32_t r0 = (int32_t)(32u * w + 4u * sub) - (int32_t)a.head;      // the lane's voxels: r0 .. r0 + 3 of the row
         uint32_t nibble = 0u;
         if (ok && r0 + 4 > 0 && r0 < (int32_t)n0) {
-            const size_t rowoff = mesh_row_offset(a, ry, rz);
+            const size_t rowoff = box_row_offset(a, ry, rz);
             uint32_t lab[4] = {0u, 0u, 0u, 0u};
-            float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            uint32_t have = 0u;
-            bool whole = r0 >= 0 && r0 + 4 <= (int32_t)n0;
-            uint32_t sx0 = 0u;
-            if (whole) {
-                sx0 = mesh_slot(a.s0[0], (uint32_t)r0, a.ring[0]);
-                whole = sx0 + 4u <= a.ring[0];                                   // not the slot the wrap seam cuts
-            }
-            if (whole) {
-                have = 0xFu;
-                if (LEVEL) {
-                    const T* const p = ring + rowoff + sx0;
-                    if ((reinterpret_cast<uintptr_t>(p) & (4u * sizeof(T) - 1u)) == 0u) MeshElem<T>::load4(p, val);
-                    else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) val[j] = (float)p[j];
-                    }
-                } else if (a.labels) {
-                    const uint32_t* const p = a.labels + rowoff + sx0;
-                    if ((reinterpret_cast<uintptr_t>(p) & 15u) == 0u) {
-                        const uint4 q = *reinterpret_cast<const uint4*>(p);
-                        lab[0] = q.x; lab[1] = q.y; lab[2] = q.z; lab[3] = q.w;
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) lab[j] = p[j];
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int32_t r = r0 + j;
-                    if (r >= 0 && r < (int32_t)n0) {
-                        have |= 1u << j;
-                        const size_t e = rowoff + mesh_slot(a.s0[0], (uint32_t)r, a.ring[0]);
-                        if (LEVEL) val[j] = (float)ring[e];
-                        else if (a.labels) lab[j] = a.labels[e];
-                    }
-                }
-            }
+            float val[4] = {0.0f, 0.0f, 0.0f, 0.0f}; uint32_t have = 0u;
+            BOX_GATHER(T, LEVEL, a, ring, n0, rowoff, r0, val, lab, have);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (have & (1u << j)) {
                     bool in;
-                    if (LEVEL) in = val[j] >= a.level;                           // a NaN is outside
-                    else {
-                        if (!have_last || lab[j] != last_label) {
-                            last_in = ring_in_set(a.sel, a.nsel, lab[j]); last_label = lab[j]; have_last = true;
-                        }
-                        in = last_in;
-                    }
+                    BOX_INSIDE(in, LEVEL, cache, val[j], lab[j], a.level, ring_in_set(a.sel, a.nsel, lab[j]));
                     if (in) nibble |= 1u << j;
                 }
             }
@@ -161,9 +85,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_inside_kernel(const MeshArg
         word |= (uint32_t)__shfl_xor((int)word, 4);
         if (ok && sub == 0u) a.bits[unit] = word;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) count += (uint32_t)__shfl_xor((int)count, d);
-    if (__lane_id() == 0u && count) atomicAdd(&a.header[7], (unsigned long long)count);
+    BOX_WAVE_ADD(&a.header[7], count);
 }
 
 // ---- classify: the words of cells ---------------------------------------------------------------------------------------
@@ -310,7 +232,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_emit_kernel(const MeshArgs 
                 const uint32_t rx = c[0] + (uint32_t)(d & 1) - 1u, ry = c[1] + (uint32_t)((d >> 1) & 1) - 1u, rz = c[2] + (uint32_t)(d >> 2) - 1u;
                 val[d] = 0.0f;
                 if (rx < a.n[0] && ry < a.n[1] && rz < a.n[2]) {
-                    val[d] = (float)ring[mesh_row_offset(a, ry, rz) + mesh_slot(a.s0[0], rx, a.ring[0])];
+                    val[d] = (float)ring[box_row_offset(a, ry, rz) + box_slot(a.s0[0], rx, a.ring[0])];
                     if (mesh_finite(val[d])) usable |= 1u << d;
                 }
             }

@@ -6,9 +6,9 @@
 //
 // Layout.  A box of n voxels per axis has n + 1 cells per axis.
 //   bits   one bit per voxel, inside or not: a row of voxels (along x) is `bpr` u32 words, voxel r of the row is bit
-//          r + head of it.  head (0 .. 3) is the ring slot of the box's first voxel modulo 4, so that a group of 4 bits
-//          at a multiple of 4 is 4 ring slots at a multiple of 4: one aligned 16-byte load of a 4-byte ring.  The bits
-//          below head and beyond the row are zero.
+//          r + head of it.  head (0 .. 3; box_units.h: box_head) is the ring slot of the box's first voxel modulo 4, so
+//          that a group of 4 bits at a multiple of 4 is 4 ring slots at a multiple of 4: one unit of box_units.h, an
+//          aligned 16-byte load of a 4-byte ring.  The bits below head and beyond the row are zero.
 //   cells  4 bits per cell (bit 0 / 1 / 2: the lattice edge that leaves the cell's first corner along x / y / z crosses
 //          the surface; bit 3: the cell is active); 16 cells are one 64-bit word, and a row of cells is a whole number
 //          of words, so that a word never spans two rows; the cells a row's last word has too many are zero.  Words are
@@ -19,6 +19,8 @@
 #pragma once
 
 #include <stdint.h>
+
+#include "box_units.h"
 
 constexpr uint32_t kMeshCellsPerWord = 16;
 constexpr uint32_t kMeshScanBlock = 256;          // entries one workgroup scans: one per thread
@@ -42,11 +44,8 @@ struct MeshPlan {
     uint64_t bytes;                    // of scratch in all
 };
 
-// the ring slot modulo 4 of the box's first voxel (lo_x >= 0: a window offset is never negative)
-inline uint32_t mesh_head(int64_t lo_x, uint32_t ring_x) { return (uint32_t)(lo_x % (int64_t)ring_x) & 3u; }
-
-// n: the extent of the box, box and window already intersected.  false: the box is empty (an n <= 0) or has more than
-// kMeshMaxCells cells (*too_many says which).
+// n: the extent of the box, box and window already intersected; head: box_head of its first voxel.  false: the box is
+// empty (an n <= 0) or has more than kMeshMaxCells cells (*too_many says which).
 inline bool mesh_plan(const int64_t n[3], uint32_t head, MeshPlan& p, bool* too_many = nullptr) {
     if (too_many) *too_many = false;
     if (n[0] <= 0 || n[1] <= 0 || n[2] <= 0) return false;
@@ -64,13 +63,7 @@ inline bool mesh_plan(const int64_t n[3], uint32_t head, MeshPlan& p, bool* too_
     p.wpr = (p.cells[0] + kMeshCellsPerWord - 1u) / kMeshCellsPerWord;
     p.rows = p.cells[1] * p.cells[2];
     p.words = p.wpr * p.rows;                    // wpr <= cells[0]: no more words than cells
-    p.levels = 1;
-    p.count[0] = p.words;
-    for (int k = 1; k < kMeshMaxLevels; ++k) p.count[k] = 0;
-    while (p.count[p.levels - 1] > kMeshScanBlock) {
-        p.count[p.levels] = (p.count[p.levels - 1] + kMeshScanBlock - 1u) / kMeshScanBlock;
-        ++p.levels;
-    }
+    p.levels = box_scan_levels(p.words, kMeshScanBlock, kMeshMaxLevels, p.count);
     p.nib_off = 0;
     uint64_t at = (uint64_t)p.words * 8u;
     for (int k = 0; k < kMeshMaxLevels; ++k) {

@@ -71,6 +71,16 @@ struct CutState {
     int mode;
     float planes[SVR_MAX_CUT_PLANES][4];
 };
+// The scratch the kernels of one box pass work in (svr_modes.hip: scratch_ordered), grown on demand and shared by every
+// call of that pass, so a call waits for the one before (done, recorded behind its last kernel) whatever its stream.
+struct ScratchSlot {
+    std::mutex mu;                         // one call at a time sizes the scratch and enqueues
+    void* mem = nullptr;
+    size_t bytes = 0;
+    hipEvent_t done = nullptr;
+    bool pending = false;                  // done has been recorded
+    void release() { if (mem) (void)hipFree(mem); if (done) (void)hipEventDestroy(done); }     // svr_destroy's
+};
 struct svr_ctx_ext : svr_ctx {
     std::mutex modes_mu;                   // setters write under it; a draw copies what it needs under it and launches outside
     float* tf_dev = nullptr;
@@ -78,25 +88,7 @@ struct svr_ctx_ext : svr_ctx {
     std::vector<float*> tf_retired;
     int interp = SVR_INTERP_NEAREST;
     CutState cut = {};
-    // svr_mesh (svr_modes.hip): the scratch its kernels work in, grown on demand and shared by every call, so a call is
-    // ordered behind the previous one (mesh_done, recorded behind every call's last kernel) whatever its stream
-    std::mutex mesh_mu;                    // one svr_mesh at a time sizes the scratch and enqueues
-    void* mesh_scratch = nullptr;
-    size_t mesh_scratch_bytes = 0;
-    hipEvent_t mesh_done = nullptr;
-    bool mesh_pending = false;             // mesh_done has been recorded
-    // svr_components (svr_modes.hip): its scratch, kept and ordered in the same way
-    std::mutex comp_mu;
-    void* comp_scratch = nullptr;
-    size_t comp_scratch_bytes = 0;
-    hipEvent_t comp_done = nullptr;
-    bool comp_pending = false;
-    // svr_distance (svr_modes.hip): its scratch, kept and ordered in the same way
-    std::mutex dist_mu;
-    void* dist_scratch = nullptr;
-    size_t dist_scratch_bytes = 0;
-    hipEvent_t dist_done = nullptr;
-    bool dist_pending = false;
+    ScratchSlot mesh, comp, dist;          // of svr_mesh, svr_components and svr_distance
 };
 // (every svr_ctx* of the ABI comes from svr_create)
 inline svr_ctx_ext* svr_ext(svr_ctx* c) { return static_cast<svr_ctx_ext*>(c); }

@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "svr_host.h"
+#include "box_units.h"
 #include "mesh_plan.h"
 #include "components_plan.h"
 #include "distance_plan.h"
@@ -73,6 +74,40 @@ static int box_window(const char* who, const svr_ctx* c, int lod, int use_box, c
         lo[a] = b; n[a] = e - b;
     }
     return SVR_OK;
+}
+
+// What svr_mesh, svr_components and svr_distance end with (who: the entry point, the prefix of the error text; what:
+// the launch as draw_ordered names it): launch(scratch, s) as draw_ordered runs it, in the pass's scratch (ScratchSlot)
+// grown to `bytes` (0: an empty box needs none), behind the pass's call before it.  Under the slot's lock throughout.
+template <class Launch>
+static int scratch_ordered(svr_ctx* c, ScratchSlot& slot, uint64_t bytes, void* stream, const char* who, const char* what, Launch&& launch) {
+    std::lock_guard<std::mutex> lock(slot.mu);
+    {
+        DeviceGuard guard(c->device);
+        if (!slot.done) SVR_HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+        if (bytes > slot.bytes) {
+            // the call that may still be working in the old scratch ends first
+            if (slot.pending) SVR_HIP_TRY(hipEventSynchronize(slot.done));
+            if (slot.mem) (void)hipFree(slot.mem);
+            slot.mem = nullptr; slot.bytes = 0;
+            if (hipMalloc(&slot.mem, (size_t)bytes) != hipSuccess) {
+                slot.mem = nullptr;
+                (void)hipGetLastError();
+                svr_set_error(std::string(who) + ": out of device memory for the scratch of " + std::to_string(bytes) + " bytes");
+                return SVR_ERR_NOMEM;
+            }
+            slot.bytes = (size_t)bytes;
+        }
+    }
+    return draw_ordered(c, stream, what, [&](hipStream_t s) {
+        hipError_t e = slot.pending ? hipStreamWaitEvent(s, slot.done, 0) : hipSuccess;
+        if (e != hipSuccess) return e;
+        e = launch(slot.mem, s);
+        // recorded behind whatever was enqueued, a failed chain's kernels too: the next call waits for them
+        const hipError_t r = hipEventRecord(slot.done, s);
+        if (r == hipSuccess) slot.pending = true;
+        return e != hipSuccess ? e : r;
+    });
 }
 
 extern "C" {
@@ -158,39 +193,12 @@ int svr_mesh(svr_ctx* c, const svr_mesh_params* mp, const svr_mesh_outputs* out,
     { const int rc = box_window("svr_mesh", c, mp->lod, mp->use_box, mp->box_off, mp->box_shape, nullptr, 0, lo, n); if (rc) return rc; }
     MeshPlan plan;
     bool too_many = false;
-    const bool any = mesh_plan(n, n[0] > 0 ? mesh_head(lo[0], (uint32_t)c->lod[mp->lod].ring[0]) : 0u, plan, &too_many);
+    const bool any = mesh_plan(n, n[0] > 0 ? box_head(lo[0], (uint32_t)c->lod[mp->lod].ring[0]) : 0u, plan, &too_many);
     SVR_REQUIRE(!too_many, "svr_mesh: more than SVR_MESH_MAX_CELLS cells");
 
-    svr_ctx_ext* x = svr_ext(c);
-    std::lock_guard<std::mutex> lock(x->mesh_mu);
-    {
-        DeviceGuard guard(c->device);
-        if (!x->mesh_done) SVR_HIP_TRY(hipEventCreateWithFlags(&x->mesh_done, hipEventDisableTiming));
-        if (any && plan.bytes > x->mesh_scratch_bytes) {
-            // the call that may still be working in the old scratch ends first
-            if (x->mesh_pending) SVR_HIP_TRY(hipEventSynchronize(x->mesh_done));
-            if (x->mesh_scratch) (void)hipFree(x->mesh_scratch);
-            x->mesh_scratch = nullptr; x->mesh_scratch_bytes = 0;
-            if (hipMalloc(&x->mesh_scratch, (size_t)plan.bytes) != hipSuccess) {
-                x->mesh_scratch = nullptr;
-                (void)hipGetLastError();
-                svr_set_error("svr_mesh: out of device memory for the scratch of " + std::to_string(plan.bytes) + " bytes");
-                return SVR_ERR_NOMEM;
-            }
-            x->mesh_scratch_bytes = (size_t)plan.bytes;
-        }
-    }
-    const int lod = mp->lod, mode = mp->mode;
-    const float level = mp->level;
     const uint32_t* sel = labels ? mp->selected : nullptr; const uint32_t nsel = labels ? mp->selected_count : 0u;
-    return draw_ordered(c, stream, "svr_launch_mesh", [&](hipStream_t s) {
-        hipError_t e = x->mesh_pending ? hipStreamWaitEvent(s, x->mesh_done, 0) : hipSuccess;
-        if (e != hipSuccess) return e;
-        e = svr_launch_mesh(c, lod, lo, any ? &plan : nullptr, mode, level, sel, nsel, x->mesh_scratch, *out, s);
-        // recorded behind whatever was enqueued, a failed chain's kernels too: the next call waits for them
-        const hipError_t r = hipEventRecord(x->mesh_done, s);
-        if (r == hipSuccess) x->mesh_pending = true;
-        return e != hipSuccess ? e : r;
+    return scratch_ordered(c, svr_ext(c)->mesh, any ? plan.bytes : 0u, stream, "svr_mesh", "svr_launch_mesh", [&](void* scratch, hipStream_t s) {
+        return svr_launch_mesh(c, mp->lod, lo, any ? &plan : nullptr, mp->mode, mp->level, sel, nsel, scratch, *out, s);
     });
 }
 
@@ -206,38 +214,11 @@ int svr_components(svr_ctx* c, const svr_components_params* cp, const svr_compon
     { const int rc = box_window("svr_components", c, cp->lod, cp->use_box, cp->box_off, cp->box_shape, cp->selected, cp->selected_count, lo, n); if (rc) return rc; }
     CompPlan plan;
     bool too_many = false;
-    const bool any = comp_plan(n, n[0] > 0 ? comp_head(lo[0], (uint32_t)c->lod[cp->lod].ring[0]) : 0u, plan, &too_many);
+    const bool any = comp_plan(n, n[0] > 0 ? box_head(lo[0], (uint32_t)c->lod[cp->lod].ring[0]) : 0u, plan, &too_many);
     SVR_REQUIRE(!too_many, "svr_components: more than SVR_COMPONENTS_MAX_VOXELS voxels");
 
-    svr_ctx_ext* x = svr_ext(c);
-    std::lock_guard<std::mutex> lock(x->comp_mu);
-    {
-        DeviceGuard guard(c->device);
-        if (!x->comp_done) SVR_HIP_TRY(hipEventCreateWithFlags(&x->comp_done, hipEventDisableTiming));
-        if (any && plan.bytes > x->comp_scratch_bytes) {
-            // the call that may still be working in the old scratch ends first
-            if (x->comp_pending) SVR_HIP_TRY(hipEventSynchronize(x->comp_done));
-            if (x->comp_scratch) (void)hipFree(x->comp_scratch);
-            x->comp_scratch = nullptr; x->comp_scratch_bytes = 0;
-            if (hipMalloc(&x->comp_scratch, (size_t)plan.bytes) != hipSuccess) {
-                x->comp_scratch = nullptr;
-                (void)hipGetLastError();
-                svr_set_error("svr_components: out of device memory for the scratch of " + std::to_string(plan.bytes) + " bytes");
-                return SVR_ERR_NOMEM;
-            }
-            x->comp_scratch_bytes = (size_t)plan.bytes;
-        }
-    }
-    const int lod = cp->lod;
-    const svr_components_params params = *cp;
-    return draw_ordered(c, stream, "svr_launch_components", [&](hipStream_t s) {
-        hipError_t e = x->comp_pending ? hipStreamWaitEvent(s, x->comp_done, 0) : hipSuccess;
-        if (e != hipSuccess) return e;
-        e = svr_launch_components(c, lod, lo, any ? &plan : nullptr, params, x->comp_scratch, *out, s);
-        // recorded behind whatever was enqueued, a failed chain's kernels too: the next call waits for them
-        const hipError_t r = hipEventRecord(x->comp_done, s);
-        if (r == hipSuccess) x->comp_pending = true;
-        return e != hipSuccess ? e : r;
+    return scratch_ordered(c, svr_ext(c)->comp, any ? plan.bytes : 0u, stream, "svr_components", "svr_launch_components", [&](void* scratch, hipStream_t s) {
+        return svr_launch_components(c, cp->lod, lo, any ? &plan : nullptr, *cp, scratch, *out, s);
     });
 }
 
@@ -251,40 +232,13 @@ int svr_distance(svr_ctx* c, const svr_distance_params* dp, const svr_distance_o
     { const int rc = box_window("svr_distance", c, dp->lod, dp->use_box, dp->box_off, dp->box_shape, dp->selected, dp->selected_count, lo, n); if (rc) return rc; }
     DistPlan plan;
     int refused = 0;
-    const bool any = dist_plan(n, n[0] > 0 ? dist_head(lo[0], (uint32_t)c->lod[dp->lod].ring[0]) : 0u, plan, &refused);
+    const bool any = dist_plan(n, n[0] > 0 ? box_head(lo[0], (uint32_t)c->lod[dp->lod].ring[0]) : 0u, plan, &refused);
     SVR_REQUIRE(refused != 1, "svr_distance: an extent of more than SVR_DISTANCE_MAX_EXTENT voxels");
     SVR_REQUIRE(refused != 2, "svr_distance: more than SVR_DISTANCE_MAX_VOXELS voxels");
 
-    svr_ctx_ext* x = svr_ext(c);
-    std::lock_guard<std::mutex> lock(x->dist_mu);
-    {
-        DeviceGuard guard(c->device);
-        if (!x->dist_done) SVR_HIP_TRY(hipEventCreateWithFlags(&x->dist_done, hipEventDisableTiming));
-        // the count-only call works in the bits alone, but sizes the scratch for the call that follows it
-        if (any && plan.bytes > x->dist_scratch_bytes) {
-            // the call that may still be working in the old scratch ends first
-            if (x->dist_pending) SVR_HIP_TRY(hipEventSynchronize(x->dist_done));
-            if (x->dist_scratch) (void)hipFree(x->dist_scratch);
-            x->dist_scratch = nullptr; x->dist_scratch_bytes = 0;
-            if (hipMalloc(&x->dist_scratch, (size_t)plan.bytes) != hipSuccess) {
-                x->dist_scratch = nullptr;
-                (void)hipGetLastError();
-                svr_set_error("svr_distance: out of device memory for the scratch of " + std::to_string(plan.bytes) + " bytes");
-                return SVR_ERR_NOMEM;
-            }
-            x->dist_scratch_bytes = (size_t)plan.bytes;
-        }
-    }
-    const int lod = dp->lod;
-    const svr_distance_params params = *dp;
-    return draw_ordered(c, stream, "svr_launch_distance", [&](hipStream_t s) {
-        hipError_t e = x->dist_pending ? hipStreamWaitEvent(s, x->dist_done, 0) : hipSuccess;
-        if (e != hipSuccess) return e;
-        e = svr_launch_distance(c, lod, lo, any ? &plan : nullptr, params, x->dist_scratch, *out, s);
-        // recorded behind whatever was enqueued, a failed chain's kernels too: the next call waits for them
-        const hipError_t r = hipEventRecord(x->dist_done, s);
-        if (r == hipSuccess) x->dist_pending = true;
-        return e != hipSuccess ? e : r;
+    // the count-only call works in the bits alone, but sizes the scratch for the call that follows it
+    return scratch_ordered(c, svr_ext(c)->dist, any ? plan.bytes : 0u, stream, "svr_distance", "svr_launch_distance", [&](void* scratch, hipStream_t s) {
+        return svr_launch_distance(c, dp->lod, lo, any ? &plan : nullptr, *dp, scratch, *out, s);
     });
 }
 

@@ -5,12 +5,12 @@ the dense volume of squared distances, its largest value and where that lies."""
 
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _native as N
+from ._box_pass import box_pass, level32
 from ._wobject import label_ids, lod_center_to_data
 
 __all__ = ["DistanceField", "distance", "distance_arguments", "signed_squared"]
@@ -108,13 +108,7 @@ def distance_arguments(level, labels, background, invert, border, signed):
     if level is None:
         ids = label_ids(labels) if labels is not None else None
         return (N.COMPONENTS_LABELS, ids, 0.0, 0 if background else 1, *switches)
-    if isinstance(level, (bool, np.bool_)) or not isinstance(level, (int, float, np.integer, np.floating)):
-        raise ValueError("distance: level must be a number")
-    with np.errstate(over="ignore"):
-        level32 = float(np.float32(level))
-    if level32 != level32:
-        raise ValueError("distance: level must not be NaN")
-    return (N.COMPONENTS_LEVEL, None, level32, 0, *switches)
+    return (N.COMPONENTS_LEVEL, None, level32("distance", level), 0, *switches)
 
 
 def distance(volume, level=None, labels=None, background=False, invert=False, border=True, signed=False, lod: int = 0, box=None,
@@ -122,30 +116,13 @@ def distance(volume, level=None, labels=None, background=False, invert=False, bo
     """``SubVolume.distance``: see there."""
     import torch
 
-    mode, ids, level32, ignore_zero, invert, border, signed = distance_arguments(level, labels, background, invert, border, signed)
-    lod = volume._check_lod(lod)
     dp = N.DistanceParams()
-    dp.lod, dp.mode, dp.level, dp.ignore_zero, dp.border = lod, mode, level32, ignore_zero, border
-    volume._box_params(dp, lod, box)
-    scale = tuple(float(v) for v in volume.wrapping_buffers[lod].scale_factor)
-    handle = volume.prepare()
-    dev = torch.device("cuda", volume._rings.device)
-    side = torch.cuda.ExternalStream(int(stream), device=dev) if stream is not None else None
-    sel = volume._upload_ids(dp, ids, dev, side)                       # held until the calls below have run
-    stream = volume._plane_stream(stream)
+    dp.mode, ids, dp.level, dp.ignore_zero, invert, dp.border, signed = distance_arguments(level, labels, background, invert, border, signed)
+    lod, scale, dev, c_call = box_pass(volume, "svr_distance", dp, lod, box, ids, stream)
 
     def call(dense):
-        header = torch.empty(16, dtype=torch.int64, device=dev)
-        if side is not None:
-            torch.cuda.current_stream(dev).synchronize()               # the allocator's memory may still be in use there
-        do = N.DistanceOutputs(None if dense is None else dense.data_ptr(), 0 if dense is None else dense.numel(), header.data_ptr())
-        N.check(N.lib().svr_distance(handle, C.byref(dp), C.byref(do), C.c_void_p(stream)), "svr_distance")
-        if side is not None:
-            for t in (dense, header):
-                if t is not None:
-                    t.record_stream(side)
-            side.synchronize()
-        return [int(v) for v in header.cpu().numpy()]                  # synchronises; coordinates read as int64: signed already
+        do = lambda header: N.DistanceOutputs(None if dense is None else dense.data_ptr(), 0 if dense is None else dense.numel(), header)
+        return c_call(16, do, dense)
 
     def run(inverted):
         dp.invert = inverted
@@ -170,7 +147,6 @@ def distance(volume, level=None, labels=None, background=False, invert=False, bo
             dense = signed_squared(dense, other)
             far += other_head[15]
         break
-    del sel
     n = (head[12], head[11], head[10])
     at = head[14]
     deepest = (head[9] + at // (n[1] * n[2]), head[8] + at // n[2] % n[1], head[7] + at % n[2]) if dense.numel() else (head[9], head[8], head[7])

@@ -4,12 +4,12 @@ which carries them and measures or exports them."""
 
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _native as N
+from ._box_pass import box_pass, level32
 from ._wobject import label_ids
 
 __all__ = ["SurfaceMesh", "mesh", "mesh_arguments"]
@@ -91,44 +91,21 @@ def mesh_arguments(labels, level):
         raise ValueError("mesh: give exactly one of labels= and level=")
     if labels is not None:
         return N.MESH_LABELS, label_ids(labels), 0.0
-    if isinstance(level, (bool, np.bool_)) or not isinstance(level, (int, float, np.integer, np.floating)):
-        raise ValueError("mesh: level must be a number")
-    with np.errstate(over="ignore"):
-        level32 = float(np.float32(level))
-    if level32 != level32:
-        raise ValueError("mesh: level must not be NaN")
-    return N.MESH_LEVEL, None, level32
+    return N.MESH_LEVEL, None, level32("mesh", level)
 
 
 def mesh(volume, labels=None, level=None, lod: int = 0, box=None, stream=None) -> SurfaceMesh:
     """``SubVolume.mesh``: see there."""
     import torch
 
-    mode, ids, level32 = mesh_arguments(labels, level)
-    lod = volume._check_lod(lod)
     mp = N.MeshParams()
-    mp.lod, mp.mode, mp.level = lod, mode, level32
-    volume._box_params(mp, lod, box)
-    scale = tuple(float(v) for v in volume.wrapping_buffers[lod].scale_factor)
-    handle = volume.prepare()
-    dev = torch.device("cuda", volume._rings.device)
-    side = torch.cuda.ExternalStream(int(stream), device=dev) if stream is not None else None
-    sel = volume._upload_ids(mp, ids, dev, side)                       # held until both calls below have run
-    stream = volume._plane_stream(stream)
+    mp.mode, ids, mp.level = mesh_arguments(labels, level)
+    lod, scale, dev, c_call = box_pass(volume, "svr_mesh", mp, lod, box, ids, stream)
 
     def call(vertices, triangles):
-        header = torch.empty(8, dtype=torch.int64, device=dev)
-        if side is not None:
-            torch.cuda.current_stream(dev).synchronize()               # the allocator's memory may still be in use there
-        mo = N.MeshOutputs(None if vertices is None else vertices.data_ptr(), None if triangles is None else triangles.data_ptr(),
-                           header.data_ptr(), 0 if vertices is None else vertices.shape[0], 0 if triangles is None else triangles.shape[0])
-        N.check(N.lib().svr_mesh(handle, C.byref(mp), C.byref(mo), C.c_void_p(stream)), "svr_mesh")
-        if side is not None:
-            for t in (vertices, triangles, header):
-                if t is not None:
-                    t.record_stream(side)
-            side.synchronize()
-        return [int(v) for v in header.cpu().numpy()]                  # synchronises
+        mo = lambda header: N.MeshOutputs(None if vertices is None else vertices.data_ptr(), None if triangles is None else triangles.data_ptr(),
+                                          header, 0 if vertices is None else vertices.shape[0], 0 if triangles is None else triangles.shape[0])
+        return c_call(8, mo, vertices, triangles)
 
     head = call(None, None)                                            # count ...
     while True:
@@ -140,6 +117,5 @@ def mesh(volume, labels=None, level=None, lod: int = 0, box=None, stream=None) -
         head = call(vertices, triangles)                               # ... emit
         if (head[0], head[1]) == (nv, nt):
             break                                                      # else an upload landed in between: allocate for the new counts
-    del sel
     return SurfaceMesh(vertices=vertices, triangles=triangles, offset=(head[4], head[5], head[6]), inside_voxels=head[7], lod=lod,
                        scale_factor=scale, volume=volume)

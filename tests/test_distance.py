@@ -319,7 +319,7 @@ def test_distance_plan(driver):
     assert 3 * (max_extent - 1) ** 2 < far                       # every distance fits below FAR
     cases = [(nx, 3, 2, h) for nx in (1, 3, 4, 5, 29, 30, 32, 33, 65) for h in (0, 1, 3)]
     cases += [(MAX_EXTENT, MAX_EXTENT, 4, 3), (1, MAX_EXTENT, MAX_EXTENT, 3), (30, 1 << 12, 1 << 13, 3), (1 << 10, 1 << 10, 1 << 10, 0)]
-    # the windows and boxes of tests/test_gpu_odd_rings.py: head is the ring slot modulo 4 of the first voxel (dist_head)
+    # the windows and boxes of tests/test_gpu_odd_rings.py: head is the ring slot modulo 4 of the first voxel (box_head)
     odd = [(*n, lo[0] % ring[0] & 3) for ring, off, lo, n in plan_cases()]
     assert {c[3] for c in odd} == {0, 1, 2, 3} and {1, 3, 63} <= {c[0] for c in odd}
     cases += odd
