@@ -1062,6 +1062,79 @@ typedef struct svr_distance_outputs {   /* DEVICE pointers; header required */
 } svr_distance_outputs;
 int  svr_distance(svr_ctx* ctx, const svr_distance_params* params, const svr_distance_outputs* out, void* stream);
 
+/* ---- contacts between resident objects: what does an object touch, over how much surface, where, and what does the
+ * data look like along that contact?  (No counterpart in the reference; the region adjacency graph of a segmentation:
+ * the neighbours of a picked object, its free and total surface, the edge scores of proof-reading and agglomeration.)
+ * An addition within ABI version 9: one new symbol and three new structs, nothing older changes.  One streaming pass
+ * over the label ring in HBM fills a table of records, one per unordered pair of touching labels; the density ring is
+ * read only beside a face; nothing is copied to the host.
+ * Defined HERE (numpy restatement: tests/contacts_twin.py):
+ *   voxels B    exactly svr_objects' voxels before its label filters: the logical voxels (x, y, z) of LOD `lod` in the
+ *               intersection of box and window, read from ring slot (x % ring_x, y % ring_y, z % ring_z) of the
+ *               row-major ring (the micro-block copy is never read); without label rings every label reads as 0.  A
+ *               window of None and a box that misses the window hold no voxel.
+ *   face        a voxel p of B, an axis k of x, y, z, and q = p + e_k also in B, with L(p) != L(q).  The face is owned
+ *               by p, so every face is seen once.  Nothing beyond B is known: a voxel on the border of box or window
+ *               has no face outward.  The pair is unordered: label_lo = min(L(p), L(q)), label_hi = max(L(p), L(q)),
+ *               and always label_lo < label_hi.
+ *   considered  with selected_count > 0, only the faces of which at least one label is one of
+ *               selected[0 .. selected_count).  Then, with ignore_zero != 0, the faces with label_lo == 0 are dropped:
+ *               they are counted in header[3] and nowhere else.
+ *   records     `capacity` records of 112 bytes.  One record per distinct considered pair that found a slot, in no
+ *               particular order; every byte of an unused record is 0.  The first 8 bytes, label_lo then label_hi as
+ *               one little-endian u64, are the key: label_hi >= 1 always, so the key of a pair is never 0 and 0 means
+ *               empty; there is no `used` word.  Labels 0 and 0xFFFFFFFF are ordinary labels.
+ *   header      8 x uint64_t:
+ *                 [0] occupied records
+ *                 [1] considered faces
+ *                 [2] overflow: the considered faces whose pair found no slot
+ *                 [3] faces dropped by ignore_zero (they passed `selected`; not part of [1])
+ *                 [4..6] the window offset (x, y, z) of the LOD the call used, as int64 bit patterns; sum2[] is relative to it
+ *                 [7] the voxels of B
+ *   slots       an insertion can reach every record (linear probing over the whole table), so header[2] != 0 if and
+ *               only if more than `capacity` distinct pairs are considered.  Then exactly `capacity` records are
+ *               occupied, every one of them is complete and exact for its pair (a pair that owns a record never
+ *               loses faces), and sum(faces[0] + faces[1] + faces[2]) + header[2] == header[1].  Which pairs got
+ *               records is unspecified.
+ *   value       the raw ring element; every face offers two, v(p) and v(q).  u8 / u16 rings: value_sum is the u64 sum,
+ *               finite == 2 * (faces[0] + faces[1] + faces[2]), vmin / vmax the extremes as f32 (exact).  float32
+ *               rings: only finite values count in finite, value_sum, vmin and vmax; value_sum holds the BITS of an
+ *               f64 sum whose every partial sum is held in f64.
+ * The call OVERWRITES its outputs: it zeroes them on `stream`, then fills them.  Every field is an integer sum, a
+ * minimum or a maximum, but value_sum on float32 rings (f64 additions in any order): on integer rings the result does
+ * not depend on the order in which the device visits the faces.  A render-thread call ordered like svr_objects: it
+ * waits for published uploads, and later uploads are ordered behind it.  Enqueued on `stream`; asynchronous.  The
+ * material, the variant, the interpolation and the cut planes are not read.
+ * SVR_ERR_INVALID, with nothing enqueued and the outputs untouched, for: a NULL ctx, params, outputs, records or
+ * header; lod out of range; capacity 0 or above SVR_CONTACTS_MAX_CAPACITY; a negative box_shape component (with
+ * use_box != 0); selected == NULL with selected_count > 0. */
+#define SVR_CONTACTS_MAX_CAPACITY (1u << 26)
+typedef struct svr_contacts_params {
+    int32_t lod;
+    int32_t use_box;                    /* 0: the LOD's whole resident window */
+    int32_t box_off[3], box_shape[3];   /* LOD-l logical voxels, shader order: svr_objects_params' */
+    const uint32_t* selected;           /* DEVICE, sorted ascending; NULL when the count is 0 */
+    uint32_t selected_count;            /* 0: every face */
+    int32_t  ignore_zero;               /* != 0: faces with label 0 take no part; they are counted in header[3] */
+    uint32_t capacity;                  /* records in svr_contacts_outputs::records, 1 .. SVR_CONTACTS_MAX_CAPACITY (any integer) */
+} svr_contacts_params;
+typedef struct svr_contact_record {
+    uint32_t label_lo, label_hi;  /* lo < hi; both 0: empty record, every byte of it is 0 */
+    uint64_t faces[3];            /* considered faces of the pair whose normal is x, y, z */
+    uint64_t sum2[3];             /* sum over the faces of 2 * (p - off) + e_k, per axis (x, y, z): twice the face
+                                     centre's coordinate relative to the window offset header[4..6], an integer */
+    int32_t  lo[3], hi[3];        /* smallest and largest coordinate of the owning voxel p, inclusive, shader order, LOD voxels */
+    uint64_t finite;              /* face-voxel values that are finite: each face offers v(p) and v(q) */
+    uint64_t value_sum;           /* u8 / u16 rings: u64 sum of those raw values; float32 rings: the BITS of an f64 sum */
+    float    vmin, vmax;          /* over those values; (+inf, -inf) when finite == 0 */
+    uint64_t reserved;            /* 0 */
+} svr_contact_record;             /* 112 bytes */
+typedef struct svr_contacts_outputs {   /* DEVICE pointers, both required */
+    svr_contact_record* records;        /* capacity */
+    uint64_t* header;                   /* 8 */
+} svr_contacts_outputs;
+int  svr_contacts(svr_ctx* ctx, const svr_contacts_params* params, const svr_contacts_outputs* out, void* stream);
+
 /* ---- sync */
 int  svr_sync(svr_ctx* ctx);                 /* both streams idle */
 int  svr_sync_uploads(svr_ctx* ctx);         /* upload stream idle */

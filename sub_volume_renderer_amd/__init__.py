@@ -18,6 +18,7 @@ from ._wrapping_buffer import WrappingBuffer, subtract_rois
 from .mesh import SurfaceMesh
 from .components import ComponentLabels
 from .distance import DistanceField
+from .contacts import ContactTable
 
 __all__ = [
     "SubVolume",
@@ -39,6 +40,7 @@ __all__ = [
     "SurfaceMesh",
     "ComponentLabels",
     "DistanceField",
+    "ContactTable",
     "subtract_rois",
     # display-side output of a render (pygfx's job in the reference)
     "compose",

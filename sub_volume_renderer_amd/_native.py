@@ -252,6 +252,34 @@ class ObjectsOutputs(C.Structure):
 OBJECTS_MAX_CAPACITY = 1 << 26                      # SVR_OBJECTS_MAX_CAPACITY
 OBJECT_RECORD_BYTES = 96                            # sizeof(svr_object_record)
 
+
+class ContactsParams(ObjectsParams):                # svr_contacts_params: svr_objects_params' fields
+    pass
+
+
+class ContactRecord(C.Structure):
+    _fields_ = [
+        ("label_lo", C.c_uint32),
+        ("label_hi", C.c_uint32),
+        ("faces", C.c_uint64 * 3),
+        ("sum2", C.c_uint64 * 3),
+        ("lo", C.c_int32 * 3),
+        ("hi", C.c_int32 * 3),
+        ("finite", C.c_uint64),
+        ("value_sum", C.c_uint64),
+        ("vmin", C.c_float),
+        ("vmax", C.c_float),
+        ("reserved", C.c_uint64),
+    ]
+
+
+class ContactsOutputs(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("records", "header")]
+
+
+CONTACTS_MAX_CAPACITY = 1 << 26                     # SVR_CONTACTS_MAX_CAPACITY
+CONTACT_RECORD_BYTES = 112                          # sizeof(svr_contact_record)
+
 class MeshParams(C.Structure):
     _fields_ = [
         ("lod", C.c_int32),
@@ -412,6 +440,7 @@ SIGNATURES = {
     "svr_set_cut_planes": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int]),
     "svr_histogram": (C.c_int, [C.c_void_p, C.POINTER(HistogramParams), C.POINTER(HistogramOutputs), C.c_void_p]),
     "svr_objects": (C.c_int, [C.c_void_p, C.POINTER(ObjectsParams), C.POINTER(ObjectsOutputs), C.c_void_p]),
+    "svr_contacts": (C.c_int, [C.c_void_p, C.POINTER(ContactsParams), C.POINTER(ContactsOutputs), C.c_void_p]),
     "svr_mesh": (C.c_int, [C.c_void_p, C.POINTER(MeshParams), C.POINTER(MeshOutputs), C.c_void_p]),
     "svr_components": (C.c_int, [C.c_void_p, C.POINTER(ComponentsParams), C.POINTER(ComponentsOutputs), C.c_void_p]),
     "svr_distance": (C.c_int, [C.c_void_p, C.POINTER(DistanceParams), C.POINTER(DistanceOutputs), C.c_void_p]),

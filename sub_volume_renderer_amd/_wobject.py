@@ -1191,6 +1191,23 @@ class SubVolume(_HasWorld):
                            min=vmm[:, 0].contiguous(), max=vmm[:, 1].contiguous(), considered=head[1], background=head[3], lod=lod,
                            scale_factor=scale, volume=self)
 
+    # -- what does an object touch? ---------------------------------------------------
+    def contacts(self, lod: int = 0, box=None, labels=None, background: bool = False, capacity=None, stream=None):
+        """The contacts between the objects that LOD ``lod`` holds in HBM (definition: ``svr_contacts`` in
+        include/svr.h): one pass over the label ring on the device -> :class:`~.contacts.ContactTable`, one row per
+        unordered pair of labels that share a voxel face, with the contact area per face normal, its bounding box and
+        mean face centre, and the mean, minimum and maximum of the values on both sides of the faces.  ``box`` and
+        ``labels`` mean what they mean in :meth:`objects`; ``labels`` reads "the contacts of these objects with
+        anything".  Nothing beyond box and window is known, so a voxel on their border has no face outward.
+        ``background=False`` leaves the faces with label 0 out (they are counted in ``ContactTable.background``);
+        ``background=True`` keeps them: an object's contact with 0 is its free surface.  ``capacity``: the records of
+        the device table; None starts at :meth:`objects`' first capacity and reruns the pass with 8 times more while
+        pairs found no record, up to ``SVR_CONTACTS_MAX_CAPACITY`` (then ``ValueError``); an explicit integer runs once
+        and raises ``ValueError`` when the table was too small.  The call SYNCHRONISES, as :meth:`objects` does."""
+        from .contacts import contacts
+
+        return contacts(self, lod=lod, box=box, labels=labels, background=background, capacity=capacity, stream=stream)
+
     # -- that object, or that level, as a surface ------------------------------------
     def mesh(self, labels=None, level=None, lod: int = 0, box=None, stream=None):
         """The surface of a picked object or of a level set of what LOD ``lod`` holds in HBM, extracted on the device

@@ -45,6 +45,9 @@ hipError_t svr_launch_histogram(const svr_ctx* c, int lod, const int64_t lo[3], 
 // object_kernels.hip.  lo, n as above; everything checked by svr_objects.
 hipError_t svr_launch_objects(const svr_ctx* c, int lod, const int64_t lo[3], const int64_t n[3], const uint32_t* sel, uint32_t nsel,
                               int ignore_zero, uint32_t capacity, const svr_objects_outputs& out, hipStream_t stream);
+// contacts_kernels.hip.  lo, n as above; everything checked by svr_contacts.
+hipError_t svr_launch_contacts(const svr_ctx* c, int lod, const int64_t lo[3], const int64_t n[3], const uint32_t* sel, uint32_t nsel,
+                               int ignore_zero, uint32_t capacity, const svr_contacts_outputs& out, hipStream_t stream);
 // mesh_kernels.hip.  lo: the first voxel of box and window intersected; plan: mesh_plan (mesh_plan.h) of its extent, null
 // for an empty box; scratch: plan->bytes of the context's mesh scratch; everything checked by svr_mesh.
 struct MeshPlan;

@@ -1,5 +1,5 @@
 // The render modes and passes of the C ABI (include/svr.h) beside the march: slices, slabs, composite and iso renders,
-// histograms, object tables, surface meshes, connected components and distance transforms, and the three setters of the
+// histograms, object and contact tables, surface meshes, connected components and distance transforms, and the three setters of the
 // state they share (svr_ctx_ext, svr_host.h).  Each entry point checks its arguments and hands the launch of its kernel
 // unit to draw_ordered; svr_mesh, svr_components and svr_distance besides keep the scratch memory their kernels work in.
 #include <math.h>
@@ -178,6 +178,17 @@ int svr_objects(svr_ctx* c, const svr_objects_params* op, const svr_objects_outp
     const int lod = op->lod, ignore_zero = op->ignore_zero;
     const uint32_t* sel = op->selected; const uint32_t nsel = op->selected_count, capacity = op->capacity;
     return SVR_DRAW_ORDERED(c, stream, svr_launch_objects(c, lod, lo, n, sel, nsel, ignore_zero, capacity, *out, s));
+}
+
+int svr_contacts(svr_ctx* c, const svr_contacts_params* cp, const svr_contacts_outputs* out, void* stream) {
+    SVR_REQUIRE(c && cp && out && out->records && out->header, "svr_contacts: null argument");
+    { const int rc = box_lod("svr_contacts", c, cp->lod); if (rc) return rc; }
+    SVR_REQUIRE(cp->capacity >= 1 && cp->capacity <= SVR_CONTACTS_MAX_CAPACITY, "svr_contacts: capacity must be in 1 .. 2^26");
+    int64_t lo[3], n[3];
+    { const int rc = box_window("svr_contacts", c, cp->lod, cp->use_box, cp->box_off, cp->box_shape, cp->selected, cp->selected_count, lo, n); if (rc) return rc; }
+    const int lod = cp->lod, ignore_zero = cp->ignore_zero;
+    const uint32_t* sel = cp->selected; const uint32_t nsel = cp->selected_count, capacity = cp->capacity;
+    return SVR_DRAW_ORDERED(c, stream, svr_launch_contacts(c, lod, lo, n, sel, nsel, ignore_zero, capacity, *out, s));
 }
 
 int svr_mesh(svr_ctx* c, const svr_mesh_params* mp, const svr_mesh_outputs* out, void* stream) {
