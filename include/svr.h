@@ -1135,6 +1135,86 @@ typedef struct svr_contacts_outputs {   /* DEVICE pointers, both required */
 } svr_contacts_outputs;
 int  svr_contacts(svr_ctx* ctx, const svr_contacts_params* params, const svr_contacts_outputs* out, void* stream);
 
+/* ---- split touching objects: the watershed of a height field, normally the d2 of svr_distance: which of the objects
+ * that touch in one blob of a level set is this voxel part of, how many are there, where is the deepest point of each?
+ * (No counterpart in the reference; the last step of threshold, distance transform, watershed, which a viewer runs today
+ * on the CPU after reading the distance field back.)  An addition within ABI version 9: one new symbol and three new
+ * structs, nothing older changes.  The positive voxels of the field are partitioned in HBM into regions, one per
+ * significant summit; nothing is copied to the host.
+ * Defined HERE (numpy restatement: tests/split_twin.py):
+ *   height      a DEVICE pointer to int32 [n_z][n_y][n_x], dense over a box B of n[0] x n[1] x n[2] = n_x x n_y x n_z
+ *               voxels, at most SVR_SPLIT_MAX_VOXELS; voxel (x, y, z) has the linear index i = (z n_y + y) n_x + x.
+ *               The call reads no ring: B is the caller's, usually header[10..12] of the svr_distance call that wrote
+ *               the field.  Nothing beyond B exists.
+ *   inside(i)   height[i] > 0: the negative half of a signed field is outside.  SVR_DISTANCE_FAR is an ordinary value
+ *               (a plateau).
+ *   neighbours  under `connectivity`, 6 (they differ by one on one axis) or 26 (by at most one on every axis, and are
+ *               not equal); it governs both the ascent and the links.
+ *   order       i BEATS j iff height[i] > height[j], or the two are equal and i < j: a strict total order.
+ *   ascent      up(i) is the voxel that beats all others among i and its neighbours in B (an outside neighbour has a
+ *               height <= 0 and never wins); summit(i) is the fixed point of up from i, which exists because every
+ *               step of the chain beats the one before.  A BASIN is the set of inside voxels that share one summit S;
+ *               peak(S) = height[S].
+ *   links       two neighbouring inside voxels p, q with different summits LINK their basins iff, with
+ *                 s = min(height[p], height[q]),  a = min(peak(summit(p)), peak(summit(q)))  (always a >= s),
+ *                 H = merge_squared,  t = a - s - H:      t <= 0  or  t * t <= 4 * H * s      in 64-bit integers,
+ *               which is exactly sqrt(a) - sqrt(s) <= sqrt(H): the lower of the two peaks stands less than sqrt(H)
+ *               above the pass.  H <= SVR_SPLIT_MAX_MERGE keeps both sides at or below 2^62.  The test reads the field
+ *               and the summits of the ascent alone, never another link, and it is monotone in s, so the highest pass
+ *               between two basins passes it iff any pair of voxels between them does.  With H = 0 basins of equal peak
+ *               that meet at that height still link: a plateau of any shape is one region.
+ *   regions     the classes of the transitive closure of the links.  The SEED of a region is its smallest summit index;
+ *               regions are numbered 1 .. N in ascending order of their seeds.  Its TOP is the summit of it that beats
+ *               its others: the region's deepest point.
+ *   ids         dense uint32 [n_z][n_y][n_x] over B: 0 for a voxel that is outside, else the number of its region.
+ *               Written, whole, only when ids_capacity >= n_x n_y n_z; else not touched.
+ *   records     N records of 80 bytes in id order.  Written, all of them, only when record_capacity >= N; else not
+ *               touched.  Every coordinate is relative to B, in shader order (x, y, z); lo and hi are both inclusive.
+ *   header      16 x uint64_t:
+ *                 [0] N                          [1] inside voxels
+ *                 [2] elements of ids written    [3] records written
+ *                 [4] basins                     [5..9] 0
+ *                 [10..12] n_x, n_y, n_z         [13..15] 0
+ *               The header is overwritten by every call.  Capacities of 0 with NULL arrays are the count-only call.
+ * Everything is an integer and fully specified: the result does not depend on the order in which the device visits the
+ * voxels, and two calls on the same field give identical bytes.  Enqueued on `stream`; asynchronous.  The call reads no
+ * ring, so no ordering against uploads is promised: the caller orders it behind whatever wrote `height`, as usual for a
+ * stream.  It works in scratch memory owned by the context (12 bytes per voxel of B, grown on demand, SVR_ERR_NOMEM when
+ * it cannot be, released by svr_destroy); a call is ordered behind the previous svr_split of the same context, whatever
+ * its stream.  The material, the variant, the interpolation and the cut planes are not read.
+ * Not in this call: heights read from the density ring (an intensity watershed); regions that stop at label borders;
+ * markers given by the caller; the h-maxima hierarchy (the link rule is ONE round on the original basins, and links can
+ * chain); writing the regions back into a label ring.
+ * SVR_ERR_INVALID, with nothing enqueued and the outputs untouched, for: a NULL ctx, params, outputs, header or height;
+ * a connectivity other than 6 or 26; merge_squared above SVR_SPLIT_MAX_MERGE; an extent <= 0 or more than
+ * SVR_SPLIT_MAX_VOXELS voxels; a NULL array with a non-zero capacity. */
+#define SVR_SPLIT_MAX_VOXELS (1u << 30)
+#define SVR_SPLIT_MAX_MERGE  (1u << 29)
+typedef struct svr_split_params {
+    const int32_t* height;              /* DEVICE, n[2] x n[1] x n[0] elements, x fastest */
+    int32_t  n[3];                      /* n_x, n_y, n_z: each > 0, the product at most SVR_SPLIT_MAX_VOXELS */
+    int32_t  connectivity;              /* 6 (faces) or 26 (faces, edges, corners) */
+    uint32_t merge_squared;             /* H, at most SVR_SPLIT_MAX_MERGE */
+    uint32_t reserved;                  /* not read */
+} svr_split_params;
+typedef struct svr_split_record {       /* 80 bytes */
+    uint32_t id;          /* 1 .. N */
+    uint32_t basins;      /* the summits of the region */
+    uint64_t voxels;
+    uint64_t sum[3];      /* sum over them of x, y, z in B */
+    int32_t  top[3];      /* the region's best summit, as (x, y, z) in B */
+    int32_t  lo[3], hi[3];/* smallest and largest coordinate in B, both inclusive */
+    int32_t  peak;        /* height at top */
+} svr_split_record;
+typedef struct svr_split_outputs {      /* DEVICE pointers; header required */
+    uint32_t* ids;                      /* ids_capacity elements */
+    uint64_t  ids_capacity;             /* 0: ids may be NULL */
+    svr_split_record* records;          /* record_capacity records */
+    uint64_t  record_capacity;          /* 0: records may be NULL */
+    uint64_t* header;                   /* 16 */
+} svr_split_outputs;
+int  svr_split(svr_ctx* ctx, const svr_split_params* params, const svr_split_outputs* out, void* stream);
+
 /* ---- sync */
 int  svr_sync(svr_ctx* ctx);                 /* both streams idle */
 int  svr_sync_uploads(svr_ctx* ctx);         /* upload stream idle */

@@ -19,6 +19,7 @@ from .mesh import SurfaceMesh
 from .components import ComponentLabels
 from .distance import DistanceField
 from .contacts import ContactTable
+from .split import SplitLabels
 
 __all__ = [
     "SubVolume",
@@ -41,6 +42,7 @@ __all__ = [
     "ComponentLabels",
     "DistanceField",
     "ContactTable",
+    "SplitLabels",
     "subtract_rois",
     # display-side output of a render (pygfx's job in the reference)
     "compose",

@@ -379,6 +379,44 @@ DISTANCE_FAR = 0x7FFFFFFF                           # SVR_DISTANCE_FAR
 DISTANCE_MAX_EXTENT = 16384                         # SVR_DISTANCE_MAX_EXTENT
 DISTANCE_MAX_VOXELS = 1 << 30                       # SVR_DISTANCE_MAX_VOXELS
 
+
+class SplitParams(C.Structure):
+    _fields_ = [
+        ("height", C.c_void_p),
+        ("n", C.c_int32 * 3),
+        ("connectivity", C.c_int32),
+        ("merge_squared", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class SplitRecord(C.Structure):
+    _fields_ = [
+        ("id", C.c_uint32),
+        ("basins", C.c_uint32),
+        ("voxels", C.c_uint64),
+        ("sum", C.c_uint64 * 3),
+        ("top", C.c_int32 * 3),
+        ("lo", C.c_int32 * 3),
+        ("hi", C.c_int32 * 3),
+        ("peak", C.c_int32),
+    ]
+
+
+class SplitOutputs(C.Structure):
+    _fields_ = [
+        ("ids", C.c_void_p),
+        ("ids_capacity", C.c_uint64),
+        ("records", C.c_void_p),
+        ("record_capacity", C.c_uint64),
+        ("header", C.c_void_p),
+    ]
+
+
+SPLIT_MAX_VOXELS = 1 << 30                          # SVR_SPLIT_MAX_VOXELS
+SPLIT_MAX_MERGE = 1 << 29                           # SVR_SPLIT_MAX_MERGE
+SPLIT_RECORD_BYTES = 80                             # sizeof(svr_split_record)
+
 INTERPOLATIONS = {"nearest": 0, "linear": 1}      # SVR_INTERP_*
 CUT_MODES = {"ANY": 0, "ALL": 1}                  # SVR_CUT_*
 MAX_CUT_PLANES = 8                                # SVR_MAX_CUT_PLANES
@@ -444,6 +482,7 @@ SIGNATURES = {
     "svr_mesh": (C.c_int, [C.c_void_p, C.POINTER(MeshParams), C.POINTER(MeshOutputs), C.c_void_p]),
     "svr_components": (C.c_int, [C.c_void_p, C.POINTER(ComponentsParams), C.POINTER(ComponentsOutputs), C.c_void_p]),
     "svr_distance": (C.c_int, [C.c_void_p, C.POINTER(DistanceParams), C.POINTER(DistanceOutputs), C.c_void_p]),
+    "svr_split": (C.c_int, [C.c_void_p, C.POINTER(SplitParams), C.POINTER(SplitOutputs), C.c_void_p]),
     "svr_sync": (C.c_int, [C.c_void_p]),
     "svr_sync_uploads": (C.c_int, [C.c_void_p]),
     "svr_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),

@@ -234,6 +234,14 @@ def lod_center_to_data(center, scale_factor):
     return (c + 0.5) / np.asarray(scale_factor, np.float64) - 0.5
 
 
+def lod_center_to_world(volume, center, scale_factor):
+    """A point in a LOD's voxel coordinates (numpy order, as :func:`lod_center_to_data` reads it) as a world-space
+    position (x, y, z) under ``volume``'s world transform, for :meth:`SubVolume.center_on_position`."""
+    data = lod_center_to_data(center, scale_factor)[::-1]     # shader order
+    world = np.asarray(volume.world.matrix, np.float64) @ np.array([*data, 1.0])
+    return tuple(float(v) for v in world[:3])
+
+
 @dataclass
 class ObjectTable:
     """The occupied records of one ``svr_objects`` call (include/svr.h), compacted and sorted by id on the device.
@@ -1258,6 +1266,25 @@ class SubVolume(_HasWorld):
 
         return distance(self, level=level, labels=labels, background=background, invert=invert, border=border, signed=signed, lod=lod,
                         box=box, stream=stream)
+
+    # -- which of the objects that touch in one blob is this voxel part of? -----------------
+    def split(self, level=None, labels=None, background: bool = False, merge: float = 1.0, connectivity: int = 26, border: bool = True,
+              lod: int = 0, box=None, distance=None, stream=None):
+        """Touching objects split apart on the device (definition: ``svr_split`` in include/svr.h): the watershed of the
+        squared distances of :meth:`distance` -> :class:`~.split.SplitLabels`, a dense volume of region numbers and one
+        row per region (voxel count, deepest voxel and the distance there, bounding box, centroid).  Every inside voxel
+        climbs, neighbour by neighbour under ``connectivity`` (6 or 26), to the deepest point it can reach; two such
+        basins stay one region where the lower of their two depths is less than ``merge`` voxels above the depth of the
+        pass between them, so ``merge=0`` keeps every summit apart (but for plateaus) and a large ``merge`` gives the
+        connected components back.  ``merge * merge`` is at most 2^29.  ``level``, ``labels``, ``background``,
+        ``border``, ``lod`` and ``box`` go to :meth:`distance`, which makes the field; or pass the
+        :class:`~.distance.DistanceField` you already hold as ``distance=`` (then ``level`` and ``labels`` raise
+        ``ValueError``): a ``signed=True`` field splits its inside, an ``invert=True`` field the space between the
+        objects.  The call SYNCHRONISES twice: it counts first, allocates exactly, then emits."""
+        from .split import split
+
+        return split(self, level=level, labels=labels, background=background, merge=merge, connectivity=connectivity, border=border,
+                     lod=lod, box=box, distance=distance, stream=stream)
 
     def synchronize(self):
         N.check(N.lib().svr_sync(self._rings.handle), "svr_sync")

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _native as N
 from ._box_pass import box_pass, level32
-from ._wobject import finest_box, label_ids, lod_center_to_data
+from ._wobject import finest_box, label_ids, lod_center_to_world
 
 __all__ = ["ComponentLabels", "components", "components_arguments"]
 
@@ -60,9 +60,7 @@ class ComponentLabels:
     def position(self, id):
         """The world-space position (x, y, z) of the component's centroid, for :meth:`SubVolume.center_on_position`:
         what ``ObjectTable.position`` computes for an object."""
-        data = lod_center_to_data(self._rows()["centroid"][self._row(id)], self.scale_factor)[::-1]     # shader order
-        world = np.asarray(self.volume.world.matrix, np.float64) @ np.array([*data, 1.0])
-        return tuple(float(v) for v in world[:3])
+        return lod_center_to_world(self.volume, self._rows()["centroid"][self._row(id)], self.scale_factor)
 
     def largest(self, k: int = 1):
         """The numbers of the ``k`` largest components, by descending voxel count, ties by ascending number."""

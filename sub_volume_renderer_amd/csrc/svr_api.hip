@@ -174,7 +174,7 @@ int svr_destroy(svr_ctx* c) {
     for (float* p : c->colors_retired) (void)hipFree(p);
     if (svr_ext(c)->tf_dev) (void)hipFree(svr_ext(c)->tf_dev);
     for (float* p : svr_ext(c)->tf_retired) (void)hipFree(p);
-    svr_ext(c)->mesh.release(); svr_ext(c)->comp.release(); svr_ext(c)->dist.release();
+    svr_ext(c)->mesh.release(); svr_ext(c)->comp.release(); svr_ext(c)->dist.release(); svr_ext(c)->split.release();
     if (c->dbg_dev) (void)hipFree(c->dbg_dev);
     for (auto& t : c->tile_orders) if (t.dev) (void)hipFree(t.dev);
     for (auto& t : c->cost_orders) {

@@ -1,7 +1,7 @@
 // The render modes and passes of the C ABI (include/svr.h) beside the march: slices, slabs, composite and iso renders,
-// histograms, object and contact tables, surface meshes, connected components and distance transforms, and the three setters of the
+// histograms, object and contact tables, surface meshes, connected components, distance transforms and their watershed, and the three setters of the
 // state they share (svr_ctx_ext, svr_host.h).  Each entry point checks its arguments and hands the launch of its kernel
-// unit to draw_ordered; svr_mesh, svr_components and svr_distance besides keep the scratch memory their kernels work in.
+// unit to draw_ordered; svr_mesh, svr_components, svr_distance and svr_split besides keep the scratch memory their kernels work in.
 #include <math.h>
 
 #include <algorithm>
@@ -11,6 +11,7 @@
 #include "mesh_plan.h"
 #include "components_plan.h"
 #include "distance_plan.h"
+#include "split_plan.h"
 
 // What svr_slice, svr_slab, svr_composite and svr_iso check first, in this order (who: the entry point's name, the
 // prefix of its error texts; args_ok: its own null test), and the frame with band_h defaulted to one band.
@@ -76,7 +77,7 @@ static int box_window(const char* who, const svr_ctx* c, int lod, int use_box, c
     return SVR_OK;
 }
 
-// What svr_mesh, svr_components and svr_distance end with (who: the entry point, the prefix of the error text; what:
+// What svr_mesh, svr_components, svr_distance and svr_split end with (who: the entry point, the prefix of the error text; what:
 // the launch as draw_ordered names it): launch(scratch, s) as draw_ordered runs it, in the pass's scratch (ScratchSlot)
 // grown to `bytes` (0: an empty box needs none), behind the pass's call before it.  Under the slot's lock throughout.
 template <class Launch>
@@ -250,6 +251,22 @@ int svr_distance(svr_ctx* c, const svr_distance_params* dp, const svr_distance_o
     // the count-only call works in the bits alone, but sizes the scratch for the call that follows it
     return scratch_ordered(c, svr_ext(c)->dist, any ? plan.bytes : 0u, stream, "svr_distance", "svr_launch_distance", [&](void* scratch, hipStream_t s) {
         return svr_launch_distance(c, dp->lod, lo, any ? &plan : nullptr, *dp, scratch, *out, s);
+    });
+}
+
+int svr_split(svr_ctx* c, const svr_split_params* sp, const svr_split_outputs* out, void* stream) {
+    SVR_REQUIRE(c && sp && out && out->header && sp->height, "svr_split: null argument");
+    SVR_REQUIRE(sp->connectivity == 6 || sp->connectivity == 26, "svr_split: connectivity must be 6 or 26");
+    SVR_REQUIRE(sp->merge_squared <= SVR_SPLIT_MAX_MERGE, "svr_split: merge_squared above SVR_SPLIT_MAX_MERGE");
+    SVR_REQUIRE(sp->n[0] > 0 && sp->n[1] > 0 && sp->n[2] > 0, "svr_split: every extent must be > 0");
+    SVR_REQUIRE(out->ids || out->ids_capacity == 0, "svr_split: NULL ids with a non-zero ids_capacity");
+    SVR_REQUIRE(out->records || out->record_capacity == 0, "svr_split: NULL records with a non-zero record_capacity");
+    SplitPlan plan;
+    SVR_REQUIRE(split_plan(sp->n, plan), "svr_split: more than SVR_SPLIT_MAX_VOXELS voxels");
+
+    // no ring is read; scratch_ordered orders the call like a draw all the same, which costs a wait that has long passed
+    return scratch_ordered(c, svr_ext(c)->split, plan.bytes, stream, "svr_split", "svr_launch_split", [&](void* scratch, hipStream_t s) {
+        return svr_launch_split(plan, *sp, scratch, *out, s);
     });
 }
 

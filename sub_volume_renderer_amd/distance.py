@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _native as N
 from ._box_pass import box_pass, level32
-from ._wobject import label_ids, lod_center_to_data
+from ._wobject import label_ids, lod_center_to_world
 
 __all__ = ["DistanceField", "distance", "distance_arguments", "signed_squared"]
 
@@ -55,9 +55,7 @@ class DistanceField:
     def deepest_position(self):
         """The world-space position (x, y, z) of ``deepest``, for :meth:`SubVolume.center_on_position`: the arithmetic
         of ``ComponentLabels.position`` on the centre of that voxel."""
-        data = lod_center_to_data(np.asarray(self.deepest, np.float64), self.scale_factor)[::-1]      # shader order
-        world = np.asarray(self.volume.world.matrix, np.float64) @ np.array([*data, 1.0])
-        return tuple(float(v) for v in world[:3])
+        return lod_center_to_world(self.volume, np.asarray(self.deepest, np.float64), self.scale_factor)
 
     def eroded(self, r):
         """The targets that lie more than ``r`` voxels from every source, as a bool tensor of ``squared``'s shape on the
