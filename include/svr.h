@@ -1031,7 +1031,7 @@ int  svr_components(svr_ctx* ctx, const svr_components_params* params, const svr
  *               [2], [3], [14], [15] at 0; so does a call whose capacity is too small.
  * Everything is an integer and fully specified, whatever algorithm computes it: two calls on the same rings give
  * identical bytes.  Distances are in voxels of the chosen LOD (no anisotropic spacing); the nearest source itself is
- * not returned (it is not unique at ties).  Ordered like svr_components: it waits for published uploads, and later
+ * not returned (it is not unique at ties; svr_nearest returns it, under a tie rule).  Ordered like svr_components: it waits for published uploads, and later
  * uploads are ordered behind it.  Enqueued on `stream`; asynchronous.  The call works in scratch memory owned by the
  * context (8 bytes and 1 bit per voxel of B, grown on demand, SVR_ERR_NOMEM when it cannot be, released by svr_destroy);
  * a call is ordered behind the previous svr_distance of the same context, whatever its stream.  The material, the
@@ -1061,6 +1061,54 @@ typedef struct svr_distance_outputs {   /* DEVICE pointers; header required */
     uint64_t* header;                   /* 16 */
 } svr_distance_outputs;
 int  svr_distance(svr_ctx* ctx, const svr_distance_params* params, const svr_distance_outputs* out, void* stream);
+
+/* ---- nearest source of every voxel (the exact feature transform): which object is this background voxel nearest to, what
+ * are the objects grown by r voxels without merging them (skimage.segmentation.expand_labels: the Voronoi partition of
+ * the labels), which surface voxel lies nearest a picked point?  (No counterpart in the reference; what a viewer answers
+ * today by reading the window back and running scipy.ndimage.distance_transform_edt(return_indices=True) on the CPU.)  An
+ * addition within ABI version 9: one new symbol and two new structs, nothing older changes.
+ * Defined HERE (numpy restatement: tests/nearest_twin.py):
+ *   params      the fields of svr_distance_params but for border, with their meanings.  B, inside(), targets and sources
+ *               are svr_distance's with border == 0: nothing beyond B is a source, a lattice point beyond B has no voxel
+ *               to name.
+ *   d2, header  byte for byte what svr_distance gives for the same parameters with border = 0, all 16 words.
+ *   index       dense int32 [n_z][n_y][n_x] over B.  index[i] is, for a voxel that is no target (a source), i itself;
+ *               for a target with at least one source, the dense index (z n_y + y) n_x + x in B of the nearest source;
+ *               for a target whose d2 is SVR_DISTANCE_FAR, -1.
+ *   tie rule    among the sources at the minimum distance, the one with the smallest dense index wins.  This is stated
+ *               without reference to an algorithm and makes the answer unique: two calls give identical bytes.
+ *   label       dense uint32 over B: the label ring's value at voxel index[i]; 0 where index[i] == -1; 0 everywhere in
+ *               a context without label rings.  Defined in both modes.  With SVR_COMPONENTS_LABELS, invert != 0,
+ *               selected_count == 0 and ignore_zero != 0 every label-0 voxel gets the label of the nearest object and
+ *               an object voxel keeps its own.  label may always be NULL and is then not written.
+ *   capacity    in elements, common to the three arrays.  They are written, whole, only when capacity >= n_x n_y n_z;
+ *               otherwise nothing is touched and the call is svr_distance's count-only call, with the same header
+ *               words left at 0.
+ * Ordered like svr_distance, whose scratch memory it shares (14 bytes and 1 bit per voxel of B here): a call is ordered
+ * behind the previous svr_distance or svr_nearest of the same context, whatever its stream.
+ * Not in it: anisotropic spacing; sources beyond the box; writing the grown labels back into a label ring
+ * (svr_upload_region_device with labels alone takes a device array, and the wrap split of a logical box is the caller's).
+ * SVR_ERR_INVALID, with nothing enqueued and the outputs untouched, for what svr_distance refuses, and for a NULL d2 or
+ * index with a non-zero capacity.  The error texts start with "svr_nearest: ". */
+typedef struct svr_nearest_params {
+    int32_t lod;
+    int32_t use_box;                    /* 0: the LOD's whole resident window */
+    int32_t box_off[3], box_shape[3];   /* LOD-l logical voxels, shader order: svr_histogram_params' */
+    int32_t mode;                       /* SVR_COMPONENTS_LABELS or SVR_COMPONENTS_LEVEL */
+    float   level;                      /* SVR_COMPONENTS_LEVEL: inside is v >= level; not NaN */
+    const uint32_t* selected;           /* SVR_COMPONENTS_LABELS: DEVICE, sorted ascending; NULL when the count is 0 */
+    uint32_t selected_count;            /* 0: every label */
+    int32_t  ignore_zero;               /* SVR_COMPONENTS_LABELS: != 0: label-0 voxels are outside; counted in header[13] */
+    int32_t  invert;                    /* != 0: targets and sources are swapped */
+} svr_nearest_params;
+typedef struct svr_nearest_outputs {    /* DEVICE pointers; header required */
+    int32_t*  d2;                       /* capacity elements */
+    int32_t*  index;                    /* capacity elements */
+    uint32_t* label;                    /* capacity elements, or NULL: not written */
+    uint64_t  capacity;                 /* 0: d2 and index may be NULL */
+    uint64_t* header;                   /* 16 */
+} svr_nearest_outputs;
+int  svr_nearest(svr_ctx* ctx, const svr_nearest_params* params, const svr_nearest_outputs* out, void* stream);
 
 /* ---- contacts between resident objects: what does an object touch, over how much surface, where, and what does the
  * data look like along that contact?  (No counterpart in the reference; the region adjacency graph of a segmentation:

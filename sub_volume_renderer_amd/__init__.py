@@ -18,6 +18,7 @@ from ._wrapping_buffer import WrappingBuffer, subtract_rois
 from .mesh import SurfaceMesh
 from .components import ComponentLabels
 from .distance import DistanceField
+from .nearest import NearestField
 from .contacts import ContactTable
 from .split import SplitLabels
 
@@ -41,6 +42,7 @@ __all__ = [
     "SurfaceMesh",
     "ComponentLabels",
     "DistanceField",
+    "NearestField",
     "ContactTable",
     "SplitLabels",
     "subtract_rois",

@@ -380,6 +380,31 @@ DISTANCE_MAX_EXTENT = 16384                         # SVR_DISTANCE_MAX_EXTENT
 DISTANCE_MAX_VOXELS = 1 << 30                       # SVR_DISTANCE_MAX_VOXELS
 
 
+class NearestParams(C.Structure):
+    _fields_ = [
+        ("lod", C.c_int32),
+        ("use_box", C.c_int32),
+        ("box_off", C.c_int32 * 3),
+        ("box_shape", C.c_int32 * 3),
+        ("mode", C.c_int32),
+        ("level", C.c_float),
+        ("selected", C.c_void_p),
+        ("selected_count", C.c_uint32),
+        ("ignore_zero", C.c_int32),
+        ("invert", C.c_int32),
+    ]
+
+
+class NearestOutputs(C.Structure):
+    _fields_ = [
+        ("d2", C.c_void_p),
+        ("index", C.c_void_p),
+        ("label", C.c_void_p),
+        ("capacity", C.c_uint64),
+        ("header", C.c_void_p),
+    ]
+
+
 class SplitParams(C.Structure):
     _fields_ = [
         ("height", C.c_void_p),
@@ -482,6 +507,7 @@ SIGNATURES = {
     "svr_mesh": (C.c_int, [C.c_void_p, C.POINTER(MeshParams), C.POINTER(MeshOutputs), C.c_void_p]),
     "svr_components": (C.c_int, [C.c_void_p, C.POINTER(ComponentsParams), C.POINTER(ComponentsOutputs), C.c_void_p]),
     "svr_distance": (C.c_int, [C.c_void_p, C.POINTER(DistanceParams), C.POINTER(DistanceOutputs), C.c_void_p]),
+    "svr_nearest": (C.c_int, [C.c_void_p, C.POINTER(NearestParams), C.POINTER(NearestOutputs), C.c_void_p]),
     "svr_split": (C.c_int, [C.c_void_p, C.POINTER(SplitParams), C.POINTER(SplitOutputs), C.c_void_p]),
     "svr_sync": (C.c_int, [C.c_void_p]),
     "svr_sync_uploads": (C.c_int, [C.c_void_p]),

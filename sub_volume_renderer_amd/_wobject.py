@@ -1267,6 +1267,31 @@ class SubVolume(_HasWorld):
         return distance(self, level=level, labels=labels, background=background, invert=invert, border=border, signed=signed, lod=lod,
                         box=box, stream=stream)
 
+    # -- which source is nearest, what are the objects grown by r voxels? --------------------
+    def nearest(self, level=None, labels=None, background: bool = False, invert: bool = False, with_labels: bool = True, lod: int = 0,
+                box=None, stream=None):
+        """The nearest source of every voxel of what LOD ``lod`` holds in HBM, computed on the device (definition:
+        ``svr_nearest`` in include/svr.h) -> :class:`~.nearest.NearestField`: what :meth:`distance` gives with
+        ``border=False`` and, for every voxel, which voxel that distance is measured to (``index``) and the label there
+        (``label``; ``with_labels=False`` leaves it out).  ``level``, ``labels``, ``background`` and ``invert`` mean what
+        they mean in :meth:`distance`; nothing beyond box and window is a source.  Among the sources at the smallest
+        distance the first in (z, y, x) order is taken, so two calls agree.  With ``invert=True`` over the segmentation
+        every background voxel gets the label of the nearest object: see :meth:`expand_labels`.  ``box`` means what it
+        means in :meth:`histogram`.  The call SYNCHRONISES twice: it counts first, allocates exactly, then emits."""
+        from .nearest import nearest
+
+        return nearest(self, level=level, labels=labels, background=background, invert=invert, with_labels=with_labels, lod=lod, box=box,
+                       stream=stream)
+
+    def expand_labels(self, r, labels=None, lod: int = 0, box=None):
+        """The objects of the segmentation (``labels``; None: every label but 0) grown by ``r`` voxels without merging
+        them, as a dense u32 volume on the device: every voxel outside them that lies at most ``r`` voxels from one takes
+        the label of the nearest (``skimage.segmentation.expand_labels``), the others are 0.  The same as
+        ``nearest(labels=labels, invert=True).expanded(r)``."""
+        from .nearest import expand_labels
+
+        return expand_labels(self, r, labels=labels, lod=lod, box=box)
+
     # -- which of the objects that touch in one blob is this voxel part of? -----------------
     def split(self, level=None, labels=None, background: bool = False, merge: float = 1.0, connectivity: int = 26, border: bool = True,
               lod: int = 0, box=None, distance=None, stream=None):

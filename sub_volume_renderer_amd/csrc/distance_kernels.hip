@@ -20,6 +20,12 @@
 //            per wave on (d2 << 32) | (0xFFFFFFFF - index), and one add.
 //   finish   one thread: unpacks that maximum into header [3] and [14].
 // Every store is an ordinary vector store; the only atomics are the counters of the header.
+//
+// svr_nearest (the nearest source of every voxel) runs the same chain without a border, with kernels of its own for x, y
+// and z that also store who owns each voxel along the axis (u16 planes in the scratch: distance_plan.h), and ends with
+//   compose  a thread per voxel: z' = own_z[z][y][x], y' = own_y[z'][y][x], x' = own_x[z'][y'][x], the dense index of
+//            (x', y', z') into index, and one gather from the label ring at that voxel's ring slot into label.
+// init, header and finish are svr_distance's kernels, and so are the stack, the ring in LDS and the reduction of the header.
 #include "svr_host.h"
 #include "distance_plan.h"
 #include "distance_scan.h"
@@ -174,13 +180,93 @@ __global__ __launch_bounds__(kDistColumnThreads) void dist_column_kernel(const D
     }
 }
 
-}  // namespace
+// ---- svr_nearest: x, y, z with owners, compose ------------------------------------------------------------------------------
+struct NearOut {
+    uint16_t* own[3];          // the owner planes of the x, y and z pass (distance_plan.h)
+    int32_t* index;
+    uint32_t* label;           // null: not written
+};
 
-// lo: the first voxel of the box (box and window intersected) in logical voxels of the LOD; plan: dist_plan of its
-// extent, or null for an empty box; scratch: plan->bytes of device memory no other call is using.  Everything was
-// validated by svr_distance.
-hipError_t svr_launch_distance(const svr_ctx* c, int lod, const int64_t lo[3], const DistPlan* plan, const svr_distance_params& dp,
-                               void* scratch, const svr_distance_outputs& out, hipStream_t stream) {
+__global__ __launch_bounds__(kDistThreads) void near_x_kernel(const DistArgs a, uint16_t* const own) {
+    const uint32_t i = blockIdx.x * kDistThreads + threadIdx.x;
+    if (i >= a.voxels) return;
+    const uint32_t row = i / a.n[0], rx = i - row * a.n[0];
+    uint32_t at = kDistNoOwner + a.head;
+    a.d2[i] = dist_row_nearest_at(a.bits + (size_t)row * a.wpr, a.wpr, rx + a.head, &at);
+    own[i] = (uint16_t)(at - a.head);                        // an element of the row -> a voxel of it
+}
+
+// dist_column_kernel without a border, and the owner of every position into its plane
+template <bool FINAL>
+__global__ __launch_bounds__(kDistColumnThreads) void near_column_kernel(const DistArgs a, uint16_t* const own, uint32_t columns) {
+    __shared__ DistEntry slots[kDistRingEntries * kDistColumnThreads];
+    const DistRing<kDistRingEntries> ring(slots + threadIdx.x, kDistColumnThreads);
+    const uint32_t c = blockIdx.x * kDistColumnThreads + threadIdx.x;
+    const uint32_t n0 = a.n[0], n1 = a.n[1], n2 = a.n[2];
+    uint32_t far = 0u;
+    unsigned long long key = 0ull;
+    if (c < columns) {
+        const uint32_t x = c % n0, other = c / n0;           // FINAL: other is y; else z
+        const uint32_t base = FINAL ? c : other * n1 * n0 + x;
+        const uint32_t stride = FINAL ? n0 * n1 : n0, length = FINAL ? n2 : n1;
+        int32_t* const col = a.d2 + base;
+        uint16_t* const who = own + base;
+        dist_scan_column_owner(col, stride, length, a.stack + c, columns, ring, [&](uint32_t u, int32_t v, uint32_t s) {
+            col[(size_t)u * stride] = v;
+            who[(size_t)u * stride] = (uint16_t)s;
+            if (FINAL) {
+                if (v == kDistFar) ++far;
+                else if (v != 0) {
+                    const unsigned long long k = ((unsigned long long)(uint32_t)v << 32) | (0xFFFFFFFFu - (base + u * stride));
+                    if (k > key) key = k;
+                }
+            }
+        });
+    }
+    if (FINAL) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            far += (uint32_t)__shfl_xor((int)far, d);
+            const unsigned long long o = __shfl_xor(key, d);
+            if (o > key) key = o;
+        }
+        if (__lane_id() == 0u) {
+            if (key) atomicMax(&a.header[3], key);
+            if (far) atomicAdd(&a.header[15], (unsigned long long)far);
+        }
+    }
+}
+
+// Every owner is compared with its extent before it is used: kDistNoOwner, of a column without a source, fails it, and no
+// gather leaves its plane or the ring.  An owner that the z pass names has a finite value, so the two below it exist.
+__global__ __launch_bounds__(kDistThreads) void near_compose_kernel(const DistArgs a, const NearOut o) {
+    const uint32_t i = blockIdx.x * kDistThreads + threadIdx.x;
+    if (i >= a.voxels) return;
+    const uint32_t n0 = a.n[0], n1 = a.n[1];
+    const uint32_t row = i / n0, x = i - row * n0, y = row % n1;
+    int32_t index = -1;
+    uint32_t label = 0u;
+    const uint32_t oz = o.own[2][i];
+    if (oz < a.n[2]) {
+        const uint32_t oy = o.own[1][(oz * n1 + y) * n0 + x];
+        if (oy < n1) {
+            const uint32_t r = oz * n1 + oy;
+            const uint32_t ox = o.own[0][r * n0 + x];
+            if (ox < n0) {
+                index = (int32_t)(r * n0 + ox);
+                if (a.labels) label = a.labels[box_row_offset(a, oy, oz) + box_slot(a.s0[0], ox, a.ring[0])];
+            }
+        }
+    }
+    o.index[i] = index;
+    if (o.label) o.label[i] = label;
+}
+
+// What both launchers begin with: the header zeroed, then for a box that is not empty (plan) a and h filled, the init pass
+// and the header kernel.  *go: d2 is to be written, the rest of the chain follows.
+hipError_t dist_begin(const svr_ctx* c, int lod, const int64_t lo[3], const DistPlan* plan, const svr_distance_params& dp, void* scratch,
+                      const svr_distance_outputs& out, hipStream_t stream, DistArgs& a, bool* go) {
+    *go = false;
     const LodStorage& L = c->lod[lod];
     const svr_lod_state& st = L.state;
     DistHeader h;
@@ -197,7 +283,6 @@ hipError_t svr_launch_distance(const svr_ctx* c, int lod, const int64_t lo[3], c
     char* const base = static_cast<char*>(scratch);
     const bool is_level = dp.mode == SVR_COMPONENTS_LEVEL;
     const bool fits = out.d2_capacity >= (uint64_t)p.voxels;
-    DistArgs a;
     a.density = L.density; a.labels = L.labels;
     for (int ax = 0; ax < 3; ++ax) {
         a.ring[ax] = (uint32_t)L.ring[ax];
@@ -226,7 +311,23 @@ hipError_t svr_launch_distance(const svr_ctx* c, int lod, const int64_t lo[3], c
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(dist_header_kernel, dim3(1), dim3(1), 0, stream, h);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (!a.d2) return hipSuccess;                           // the count-only call, and a capacity that is too small
+    *go = a.d2 != nullptr;                                  // else the count-only call, and a capacity that is too small
+    return hipSuccess;
+}
+
+}  // namespace
+
+// lo: the first voxel of the box (box and window intersected) in logical voxels of the LOD; plan: dist_plan of its
+// extent, or null for an empty box; scratch: plan->bytes of device memory no other call is using.  Everything was
+// validated by svr_distance.
+hipError_t svr_launch_distance(const svr_ctx* c, int lod, const int64_t lo[3], const DistPlan* plan, const svr_distance_params& dp,
+                               void* scratch, const svr_distance_outputs& out, hipStream_t stream) {
+    DistArgs a;
+    bool go;
+    hipError_t e = dist_begin(c, lod, lo, plan, dp, scratch, out, stream, a, &go);
+    if (e != hipSuccess || !go) return e;
+    const DistPlan& p = *plan;
+    const dim3 block(kDistThreads);
 
     hipLaunchKernelGGL(dist_x_kernel, dim3((p.voxels + kDistThreads - 1u) / kDistThreads), block, 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -237,6 +338,40 @@ hipError_t svr_launch_distance(const svr_ctx* c, int lod, const int64_t lo[3], c
     hipLaunchKernelGGL((dist_column_kernel<true>), dim3((p.columns[1] + kDistColumnThreads - 1u) / kDistColumnThreads), column_block, 0,
                        stream, a, p.columns[1]);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(dist_finish_kernel, dim3(1), dim3(1), 0, stream, h.header);
+    hipLaunchKernelGGL(dist_finish_kernel, dim3(1), dim3(1), 0, stream, a.header);
+    return hipGetLastError();
+}
+
+// As svr_launch_distance with border = 0; plan: near_plan of the box's extent.  Everything was validated by svr_nearest.
+hipError_t svr_launch_nearest(const svr_ctx* c, int lod, const int64_t lo[3], const NearPlan* plan, const svr_nearest_params& np,
+                              void* scratch, const svr_nearest_outputs& out, hipStream_t stream) {
+    svr_distance_params dp;
+    dp.lod = np.lod; dp.use_box = np.use_box;
+    for (int ax = 0; ax < 3; ++ax) { dp.box_off[ax] = np.box_off[ax]; dp.box_shape[ax] = np.box_shape[ax]; }
+    dp.mode = np.mode; dp.level = np.level; dp.selected = np.selected; dp.selected_count = np.selected_count;
+    dp.ignore_zero = np.ignore_zero; dp.invert = np.invert; dp.border = 0;
+    const svr_distance_outputs dout = {out.d2, out.capacity, out.header};
+    DistArgs a;
+    bool go;
+    hipError_t e = dist_begin(c, lod, lo, plan ? &plan->d : nullptr, dp, scratch, dout, stream, a, &go);
+    if (e != hipSuccess || !go) return e;
+    const DistPlan& p = plan->d;
+    char* const base = static_cast<char*>(scratch);
+    NearOut o;
+    for (int ax = 0; ax < 3; ++ax) o.own[ax] = reinterpret_cast<uint16_t*>(base + plan->own_off[ax]);
+    o.index = out.index; o.label = out.label;
+    const dim3 block(kDistThreads), voxel_grid((p.voxels + kDistThreads - 1u) / kDistThreads), column_block(kDistColumnThreads);
+
+    hipLaunchKernelGGL(near_x_kernel, voxel_grid, block, 0, stream, a, o.own[0]);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL((near_column_kernel<false>), dim3((p.columns[0] + kDistColumnThreads - 1u) / kDistColumnThreads), column_block, 0,
+                       stream, a, o.own[1], p.columns[0]);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL((near_column_kernel<true>), dim3((p.columns[1] + kDistColumnThreads - 1u) / kDistColumnThreads), column_block, 0,
+                       stream, a, o.own[2], p.columns[1]);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(dist_finish_kernel, dim3(1), dim3(1), 0, stream, a.header);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(near_compose_kernel, voxel_grid, block, 0, stream, a, o);
     return hipGetLastError();
 }

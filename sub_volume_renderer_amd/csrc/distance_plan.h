@@ -17,6 +17,15 @@
 //           adjacent entries.  The y pass has n_x n_z columns of n_y entries, the z pass n_x n_y columns of n_z.
 // 8 bytes per voxel for the stacks and 1 bit (rounded up to whole words per row) for the sources.  The squared
 // distances themselves are worked on in the caller's array.
+//
+// svr_nearest (NearPlan) works in the same slot and adds, behind the stacks, three planes of owners, one u16 per voxel
+// each at the voxel's dense index: own[0] the row voxel rx' of the nearest source of the voxel's row (the x pass), own[1]
+// the y' that owns the voxel in its y column (the y pass), own[2] the z' that owns it in its z column (the z pass);
+// kDistNoOwner where the row or column has no source.  They are never stored into d2, which the passes rewrite in
+// place.  The compose kernel reads them as z' = own[2][z][y][x], y' = own[1][z'][y][x], x' = own[0][z'][y'][x].  6
+// bytes per voxel more: 14 bytes and 1 bit per voxel in all.  The x owners are stored, not recomputed from the bits at
+// compose time: a plane costs one 2-byte store per voxel in a pass that is bound by its 4-byte store, and the gather
+// from it is one load where the row walk is a loop.
 #pragma once
 
 #include <stdint.h>
@@ -65,6 +74,25 @@ inline bool dist_plan(const int64_t n[3], uint32_t head, DistPlan& p, int* refus
     return true;
 }
 
+// svr_nearest's: the plan of svr_distance and the three owner planes behind its scratch
+struct NearPlan {
+    DistPlan d;
+    uint64_t own_off[3];               // byte offsets of the x, y and z owners: voxels * 2 bytes each
+    uint64_t bytes;                    // of scratch in all: >= d.bytes, the slot is svr_distance's
+};
+
+// as dist_plan, which decides what is empty and what is refused
+inline bool near_plan(const int64_t n[3], uint32_t head, NearPlan& p, int* refused = nullptr) {
+    if (!dist_plan(n, head, p.d, refused)) return false;
+    uint64_t at = (p.d.bytes + 15u) & ~(uint64_t)15u;
+    for (int a = 0; a < 3; ++a) {
+        p.own_off[a] = at;
+        at += ((uint64_t)p.d.voxels * sizeof(uint16_t) + 15u) & ~(uint64_t)15u;
+    }
+    p.bytes = at;
+    return true;
+}
+
 // The squared distance of voxel r (0 <= r < n) of a row to the nearest source of the row, or kDistFar: the x pass.
 // words: the row's wpr words of source bits; e = r + head.  Walks outwards word by word, bounded by the row.
 DIST_FN int32_t dist_row_nearest(const uint32_t* words, uint32_t wpr, uint32_t e) {
@@ -92,4 +120,36 @@ DIST_FN int32_t dist_row_nearest(const uint32_t* words, uint32_t wpr, uint32_t e
         m = words[k];
     }
     return best == 0xFFFFFFFFu ? kDistFar : (int32_t)(best * best);
+}
+
+// The same, and into *at the element of that source: of two at the same distance the left one (the smaller element), e
+// itself where e is a source, untouched with kDistFar.  svr_nearest's x pass.
+DIST_FN int32_t dist_row_nearest_at(const uint32_t* words, uint32_t wpr, uint32_t e, uint32_t* at) {
+    const uint32_t wi = e >> 5, b = e & 31u;
+    const uint32_t w = words[wi];
+    if ((w >> b) & 1u) { *at = e; return 0; }
+    uint32_t best = 0xFFFFFFFFu, where = 0u;
+    uint32_t m = w & ((1u << b) - 1u);                                   // the bits below b
+    for (uint32_t k = wi;;) {
+        if (m) {
+            where = 32u * k + 31u - (uint32_t)__builtin_clz(m);
+            best = e - where;
+            break;
+        }
+        if (k == 0u) break;
+        m = words[--k];
+    }
+    m = b == 31u ? 0u : (w & (0xFFFFFFFFu << (b + 1u)));                 // the bits above b
+    for (uint32_t k = wi;;) {
+        if (m) {
+            const uint32_t right = 32u * k + (uint32_t)__builtin_ctz(m);
+            if (right - e < best) { best = right - e; where = right; }   // strictly nearer: a tie stays left
+            break;
+        }
+        if (++k == wpr) break;
+        m = words[k];
+    }
+    if (best == 0xFFFFFFFFu) return kDistFar;
+    *at = where;
+    return (int32_t)(best * best);
 }

@@ -61,10 +61,15 @@ struct DistRing {
 
 constexpr int kDistAhead = 4;                     // entries the backward scan reads ahead of the pop that needs them
 
+constexpr uint32_t kDistNoOwner = 0xFFFFu;        // the owner of a position of a column that has no parabola: no vertex is that large
+
 // g: the column, element u at g[u * gs]; stack: m entries, entry k at stack[k * ss]; ring: a DistRing of any size;
-// emit(u, value) is called once for every u, from m - 1 down to 0, after the last read of g: it may store into g.
+// emit(u, value, owner) is called once for every u, from m - 1 down to 0, after the last read of g: it may store into g.
+// owner: the vertex i of the parabola that gives the value, the smallest such i where several do (svr_nearest's tie rule,
+// include/svr.h): an older vertex keeps every position at which the newer one is not strictly below it, as the pop test
+// (a strict >) and the start 1 + sep say.  kDistNoOwner with kDistFar.
 template <class Ring, class Emit>
-DIST_FN void dist_scan_column(const int32_t* g, size_t gs, uint32_t m, DistEntry* stack, size_t ss, Ring ring, Emit&& emit) {
+DIST_FN void dist_scan_column_owner(const int32_t* g, size_t gs, uint32_t m, DistEntry* stack, size_t ss, Ring ring, Emit&& emit) {
     int32_t q = -1;                               // the top of the stack, which also lives in (ts, tv, tt)
     int32_t ts = 0, tv = 0, tt = 0;
     int32_t next = g[0];
@@ -95,7 +100,7 @@ DIST_FN void dist_scan_column(const int32_t* g, size_t gs, uint32_t m, DistEntry
         }
     }
     if (q < 0) {
-        for (uint32_t u = m; u-- > 0u;) emit(u, kDistFar);
+        for (uint32_t u = m; u-- > 0u;) emit(u, kDistFar, kDistNoOwner);
         return;
     }
     // the entries below the top, in the order the pops will want them, read kDistAhead pops ahead of their use
@@ -106,7 +111,7 @@ DIST_FN void dist_scan_column(const int32_t* g, size_t gs, uint32_t m, DistEntry
     for (int j = 0; j < kDistAhead; ++j) below[j] = q - 1 - j >= 0 ? stack[(size_t)(q - 1 - j) * ss] : DistEntry{0, 0u};
     for (uint32_t u = m; u-- > 0u;) {
         const int32_t d = (int32_t)u - ts;
-        emit(u, d * d + tv);
+        emit(u, d * d + tv, (uint32_t)ts);
         if ((int32_t)u == tt && q > 0) {
             --q;
             tv = below[0].value; ts = (int32_t)(below[0].st & 0xFFFFu); tt = (int32_t)(below[0].st >> 16);
@@ -117,4 +122,10 @@ DIST_FN void dist_scan_column(const int32_t* g, size_t gs, uint32_t m, DistEntry
             if (q - kDistAhead >= 0) below[kDistAhead - 1] = stack[(size_t)(q - kDistAhead) * ss];
         }
     }
+}
+
+// The same without the owner: emit(u, value).  svr_distance's.
+template <class Ring, class Emit>
+DIST_FN void dist_scan_column(const int32_t* g, size_t gs, uint32_t m, DistEntry* stack, size_t ss, Ring ring, Emit&& emit) {
+    dist_scan_column_owner(g, gs, m, stack, ss, ring, [&](uint32_t u, int32_t v, uint32_t) { emit(u, v); });
 }

@@ -63,6 +63,11 @@ hipError_t svr_launch_components(const svr_ctx* c, int lod, const int64_t lo[3],
 struct DistPlan;
 hipError_t svr_launch_distance(const svr_ctx* c, int lod, const int64_t lo[3], const DistPlan* plan, const svr_distance_params& dp,
                                void* scratch, const svr_distance_outputs& out, hipStream_t stream);
+// The same unit.  plan: near_plan (distance_plan.h), null for an empty box; scratch: plan->bytes of the same scratch;
+// everything checked by svr_nearest.
+struct NearPlan;
+hipError_t svr_launch_nearest(const svr_ctx* c, int lod, const int64_t lo[3], const NearPlan* plan, const svr_nearest_params& np,
+                              void* scratch, const svr_nearest_outputs& out, hipStream_t stream);
 // split_kernels.hip.  plan: split_plan (split_plan.h) of sp.n; scratch: plan.bytes of the context's split scratch;
 // everything checked by svr_split.  No ring is read, so there is no context among the arguments.
 struct SplitPlan;
@@ -96,7 +101,7 @@ struct svr_ctx_ext : svr_ctx {
     std::vector<float*> tf_retired;
     int interp = SVR_INTERP_NEAREST;
     CutState cut = {};
-    ScratchSlot mesh, comp, dist, split;   // of svr_mesh, svr_components, svr_distance and svr_split
+    ScratchSlot mesh, comp, dist, split;   // of svr_mesh, svr_components, svr_distance (and svr_nearest) and svr_split
 };
 // (every svr_ctx* of the ABI comes from svr_create)
 inline svr_ctx_ext* svr_ext(svr_ctx* c) { return static_cast<svr_ctx_ext*>(c); }

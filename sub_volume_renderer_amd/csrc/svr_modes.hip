@@ -1,7 +1,7 @@
 // The render modes and passes of the C ABI (include/svr.h) beside the march: slices, slabs, composite and iso renders,
 // histograms, object and contact tables, surface meshes, connected components, distance transforms and their watershed, and the three setters of the
 // state they share (svr_ctx_ext, svr_host.h).  Each entry point checks its arguments and hands the launch of its kernel
-// unit to draw_ordered; svr_mesh, svr_components, svr_distance and svr_split besides keep the scratch memory their kernels work in.
+// unit to draw_ordered; svr_mesh, svr_components, svr_distance, svr_nearest and svr_split besides keep the scratch memory their kernels work in.
 #include <math.h>
 
 #include <algorithm>
@@ -77,7 +77,7 @@ static int box_window(const char* who, const svr_ctx* c, int lod, int use_box, c
     return SVR_OK;
 }
 
-// What svr_mesh, svr_components, svr_distance and svr_split end with (who: the entry point, the prefix of the error text; what:
+// What svr_mesh, svr_components, svr_distance, svr_nearest and svr_split end with (who: the entry point, the prefix of the error text; what:
 // the launch as draw_ordered names it): launch(scratch, s) as draw_ordered runs it, in the pass's scratch (ScratchSlot)
 // grown to `bytes` (0: an empty box needs none), behind the pass's call before it.  Under the slot's lock throughout.
 template <class Launch>
@@ -251,6 +251,27 @@ int svr_distance(svr_ctx* c, const svr_distance_params* dp, const svr_distance_o
     // the count-only call works in the bits alone, but sizes the scratch for the call that follows it
     return scratch_ordered(c, svr_ext(c)->dist, any ? plan.bytes : 0u, stream, "svr_distance", "svr_launch_distance", [&](void* scratch, hipStream_t s) {
         return svr_launch_distance(c, dp->lod, lo, any ? &plan : nullptr, *dp, scratch, *out, s);
+    });
+}
+
+int svr_nearest(svr_ctx* c, const svr_nearest_params* np, const svr_nearest_outputs* out, void* stream) {
+    SVR_REQUIRE(c && np && out && out->header, "svr_nearest: null argument");
+    { const int rc = box_lod("svr_nearest", c, np->lod); if (rc) return rc; }
+    SVR_REQUIRE(np->mode == SVR_COMPONENTS_LABELS || np->mode == SVR_COMPONENTS_LEVEL, "svr_nearest: unknown mode");
+    if (np->mode == SVR_COMPONENTS_LEVEL) SVR_REQUIRE(np->level == np->level, "svr_nearest: level must not be NaN");
+    SVR_REQUIRE(out->d2 || out->capacity == 0, "svr_nearest: NULL d2 with a non-zero capacity");
+    SVR_REQUIRE(out->index || out->capacity == 0, "svr_nearest: NULL index with a non-zero capacity");
+    int64_t lo[3], n[3];
+    { const int rc = box_window("svr_nearest", c, np->lod, np->use_box, np->box_off, np->box_shape, np->selected, np->selected_count, lo, n); if (rc) return rc; }
+    NearPlan plan;
+    int refused = 0;
+    const bool any = near_plan(n, n[0] > 0 ? box_head(lo[0], (uint32_t)c->lod[np->lod].ring[0]) : 0u, plan, &refused);
+    SVR_REQUIRE(refused != 1, "svr_nearest: an extent of more than SVR_DISTANCE_MAX_EXTENT voxels");
+    SVR_REQUIRE(refused != 2, "svr_nearest: more than SVR_DISTANCE_MAX_VOXELS voxels");
+
+    // svr_distance's slot: the two are ordered behind one another
+    return scratch_ordered(c, svr_ext(c)->dist, any ? plan.bytes : 0u, stream, "svr_nearest", "svr_launch_nearest", [&](void* scratch, hipStream_t s) {
+        return svr_launch_nearest(c, np->lod, lo, any ? &plan : nullptr, *np, scratch, *out, s);
     });
 }
 

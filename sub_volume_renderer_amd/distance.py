@@ -70,13 +70,18 @@ class DistanceField:
     def at(self, position) -> int:
         """The squared distance of the voxel that holds the world-space ``position`` (x, y, z), 0 outside the box: the
         depth under a picked point."""
+        voxel = self._voxel(position)
+        return 0 if voxel is None else int(self.squared[voxel])
+
+    def _voxel(self, position):
+        """The voxel of the box (z, y, x, from ``begin``) that holds the world-space ``position``, None outside the box."""
         world = np.array([float(v) for v in position] + [1.0], np.float64)
         data = (np.linalg.inv(np.asarray(self.volume.world.matrix, np.float64)) @ world)[:3][::-1]          # numpy order
         # the LOD voxel that holds finest data coordinate d: the inverse of lod_center_to_data, rounded to the voxel
         voxel = np.floor((data + 0.5) * np.asarray(self.scale_factor, np.float64)).astype(np.int64) - np.asarray(self.begin, np.int64)
         if np.any(voxel < 0) or np.any(voxel >= np.asarray(tuple(self.squared.shape), np.int64)):
-            return 0
-        return int(self.squared[int(voxel[0]), int(voxel[1]), int(voxel[2])])
+            return None
+        return int(voxel[0]), int(voxel[1]), int(voxel[2])
 
 
 def _square(r) -> int:

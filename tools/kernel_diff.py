@@ -54,7 +54,7 @@ def kernels_of(co):
         if m:
             cur = out.setdefault(m.group(1), [])
             continue
-        if cur is None or not line.strip():
+        if cur is None or not line.strip() or line.strip() == "...":      # "...": zero padding up to the next kernel's alignment
             continue
         cur.append(re.sub(r"\s+", " ", line.split("//")[0]).strip())
     return out
