@@ -12,16 +12,6 @@
 // the ring slot modulo 4 of the box's first voxel (lo_x >= 0: a window offset is never negative)
 inline uint32_t box_head(int64_t lo_x, uint32_t ring_x) { return (uint32_t)(lo_x % (int64_t)ring_x) & 3u; }
 
-// The levels of a prefix scan over count0 entries, `block` of them to a workgroup -> their number: count[0] = count0,
-// count[k + 1] the blocks of level k, until one block holds a level (within max_levels by the caller's limit on count0)
-inline int box_scan_levels(uint32_t count0, uint32_t block, int max_levels, uint32_t count[]) {
-    int levels = 1;
-    count[0] = count0;
-    for (int k = 1; k < max_levels; ++k) count[k] = 0;
-    for (; count[levels - 1] > block; ++levels) count[levels] = (count[levels - 1] + block - 1u) / block;
-    return levels;
-}
-
 #ifdef __HIPCC__
 #include "ring_pieces.h"
 

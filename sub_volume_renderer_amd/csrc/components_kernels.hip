@@ -11,27 +11,29 @@
 //            ring row.  Counts the inside voxels and the dropped zeros, one atomic each per wave.
 //   merge    a thread per voxel joins it with the neighbours before it (components_uf.h: uf_merge_voxel, the rules of
 //            the union-find are stated there); 6- and 26-connectivity, with and without labels, are compile-time variants.
-//   flatten  parent[i] = root(i), and the number of roots among each workgroup's voxels: level 0 of the scan.
-//   scan     an exclusive prefix of those counts in place: per-block sums level by level, one workgroup over the top
-//            level (which also writes the header), then each level adds its block's prefix on the way down.
+//   flatten  parent[i] = root(i), and the number of roots among each workgroup's voxels: level 0 of the scan
+//            (components_uf.h: uf_flatten_kernel).
+//   scan     an exclusive prefix of those counts in place: the scan of box_scan.h on u32, whose top level writes the
+//            header (CompHeader).
 //   rank     a root in (z, y, x) order is the first voxel of its component, so the number of roots before it is its
 //            component's number minus one: into aux[root]; and, when the records fit, the root starts its record (id,
 //            label, first; empty sums and an empty box).
 //   emit     a thread per voxel: ids[i] = aux[parent[i]] + 1, and the voxel's share of its record.  The lanes of a
-//            wave that belong to one component add up and reduce their shares with shuffles first, so a component that
-//            fills the wave costs one set of integer atomics per wave, not 64.  Skipped by the count-only call.
+//            wave that belong to one component add up and reduce their shares with shuffles first (box_scan.h:
+//            box_wave_groups).  Skipped by the count-only call.
 // parent is only ever written by the init pass and by atomic minima; every other store is an ordinary vector store.
 #include <limits.h>
 
 #include "svr_host.h"
 #include "components_plan.h"
 #include "components_uf.h"
+#include "box_scan.h"
 #include "box_units.h"
 
 namespace {
 
 constexpr int kCompThreads = 256;
-static_assert(kCompScanBlock == (uint32_t)kCompThreads, "one entry, and one voxel, per thread");
+static_assert(kBoxScanBlock == (uint32_t)kCompThreads, "one entry, and one voxel, per thread");
 
 struct CompArgs {
     const void* density;
@@ -100,98 +102,35 @@ __global__ __launch_bounds__(kCompThreads) void comp_merge_kernel(const CompArgs
     if (i < a.voxels) uf_merge_voxel<CONN26, KEYED>(a.parent, a.aux, i, a.n, a.head);
 }
 
-// the sum of v over the workgroup, in every thread
-__device__ __forceinline__ uint32_t comp_block_sum(uint32_t v, uint32_t* part) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t s = 0u;
-#pragma unroll
-    for (int k = 0; k < kCompThreads / 64; ++k) s += part[k];
-    return s;
-}
-
-// the sum of v over the threads of the workgroup before this one
-__device__ __forceinline__ uint32_t comp_block_exclusive(uint32_t v, uint32_t* part) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t p = (uint32_t)__shfl_up((int)inc, d);
-        if (lane >= (uint32_t)d) inc += p;
-    }
-    if (lane == 63u) part[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0u;
-    for (uint32_t k = 0; k < wave; ++k) before += part[k];
-    return before + inc - v;
-}
-
-// ---- flatten ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kCompThreads) void comp_flatten_kernel(const CompArgs a) {
-    __shared__ uint32_t part[kCompThreads / 64];
-    const uint32_t i = blockIdx.x * kCompThreads + threadIdx.x;
-    uint32_t is_root = 0u;
-    if (i < a.voxels) {
-        const uint32_t p = uf_load(a.parent + i);
-        if (p != kUfOutside) {
-            const uint32_t r = uf_find(a.parent, p);
-            if (r != p) (void)uf_min(a.parent + i, r);
-            is_root = r == i;
-        }
-    }
-    const uint32_t total = comp_block_sum(is_root, part);
-    if (threadIdx.x == 0u) a.cnt[blockIdx.x] = total;
-}
-
 // ---- scan ---------------------------------------------------------------------------------------------------------------
-// out[b] = the sum of block b's kCompScanBlock entries of in[0 .. n)
-__global__ __launch_bounds__(kCompThreads) void comp_scan_sums_kernel(const uint32_t* in, uint32_t n, uint32_t* out) {
-    __shared__ uint32_t part[kCompThreads / 64];
-    const uint32_t i = blockIdx.x * kCompScanBlock + threadIdx.x;
-    const uint32_t total = comp_block_sum(i < n ? in[i] : 0u, part);
-    if (threadIdx.x == 0u) out[blockIdx.x] = total;
-}
-
-// what the top level writes into the header beside N
+// What the top level of the scan does with N, the number of roots: the header but for [1] and [13], which the init pass
+// counted.
 struct CompHeader {
     unsigned long long* header;
     unsigned long long ids_written, rcap;
     int32_t off[3], lo[3];
     uint32_t n[3];
-};
-
-// data[0 .. n): every block's entries become their exclusive prefix inside the block plus base[block] (null: 0).  The top
-// level (`top`: one block holds it all) writes the header but for [1] and [13], which the init pass counted.
-__global__ __launch_bounds__(kCompThreads) void comp_scan_apply_kernel(uint32_t* data, uint32_t n, const uint32_t* base, int top,
-                                                                       const CompHeader h) {
-    __shared__ uint32_t part[kCompThreads / 64];
-    const uint32_t i = blockIdx.x * kCompScanBlock + threadIdx.x;
-    const uint32_t v = i < n ? data[i] : 0u;
-    const uint32_t before = comp_block_exclusive(v, part) + (base ? base[blockIdx.x] : 0u);
-    if (i < n) data[i] = before;
-    if (top && threadIdx.x == kCompThreads - 1) {
-        const unsigned long long N = (unsigned long long)before + v;
-        h.header[0] = N;
-        h.header[2] = h.ids_written;
-        h.header[3] = N <= h.rcap ? N : 0ull;
+    __device__ void operator()(uint32_t total) const {
+        const unsigned long long N = total;
+        header[0] = N;
+        header[2] = ids_written;
+        header[3] = N <= rcap ? N : 0ull;
 #pragma unroll
         for (int ax = 0; ax < 3; ++ax) {
-            h.header[4 + ax] = (unsigned long long)(long long)h.off[ax];
-            h.header[7 + ax] = (unsigned long long)(long long)h.lo[ax];
-            h.header[10 + ax] = h.n[ax];
+            header[4 + ax] = (unsigned long long)(long long)off[ax];
+            header[7 + ax] = (unsigned long long)(long long)lo[ax];
+            header[10 + ax] = n[ax];
         }
-        h.header[14] = 0ull; h.header[15] = 0ull;
+        header[14] = 0ull; header[15] = 0ull;
     }
-}
+};
 
 // ---- rank ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kCompThreads) void comp_rank_kernel(const CompArgs a) {
-    __shared__ uint32_t part[kCompThreads / 64];
+    __shared__ uint32_t part[kBoxScanWaves];
     const uint32_t i = blockIdx.x * kCompThreads + threadIdx.x;
     const uint32_t is_root = i < a.voxels && a.parent[i] == i;
-    const uint32_t rank = comp_block_exclusive(is_root, part) + a.cnt[blockIdx.x];
+    const uint32_t rank = box_block_exclusive(is_root, part) + a.cnt[blockIdx.x];
     if (!is_root) return;
     a.aux[i] = rank;
     if (!a.records || a.header[0] > a.rcap) return;
@@ -219,42 +158,17 @@ __global__ __launch_bounds__(kCompThreads) void comp_emit_kernel(const CompArgs 
     if (!a.records || a.header[0] > a.rcap) return;         // the same for every thread of the launch
     const uint32_t rx = i % a.n[0], row = i / a.n[0], ry = row % a.n[1], rz = row / a.n[1];
     const uint32_t c[3] = {rx, ry, rz};
-    unsigned long long todo = __ballot(id != 0u);
-    while (todo) {                                          // wave-uniform: a round per component that has lanes left
-        const int leader = __ffsll((long long)todo) - 1;
-        const uint32_t lid = (uint32_t)__shfl((int)id, leader);
-        const bool mine = id == lid;
-        const unsigned long long peers = __ballot(mine);
-        todo &= ~peers;
-        uint32_t cmin[3], cmax[3];
-        unsigned long long sum[3];
+    box_wave_groups<false>(id, c, 0ull, [&](uint32_t lid, const BoxShare& s) {
+        svr_component_record& r = a.records[lid - 1u];
+        atomicAdd(reinterpret_cast<unsigned long long*>(&r.voxels), (unsigned long long)s.count);
 #pragma unroll
         for (int ax = 0; ax < 3; ++ax) {
-            cmin[ax] = mine ? c[ax] : 0xFFFFFFFFu; cmax[ax] = mine ? c[ax] : 0u;
-            sum[ax] = mine ? (unsigned long long)((uint32_t)a.rel[ax] + c[ax]) : 0ull;
+            // every lane's share is its coordinate in the window, rel + c
+            atomicAdd(reinterpret_cast<unsigned long long*>(&r.sum[ax]), s.sum[ax] + (unsigned long long)s.count * (uint32_t)a.rel[ax]);
+            atomicMin(&r.lo[ax], a.lo[ax] + (int32_t)s.cmin[ax]);
+            atomicMax(&r.hi[ax], a.lo[ax] + (int32_t)s.cmax[ax]);
         }
-        if (__popcll(peers) > 1) {
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-#pragma unroll
-                for (int ax = 0; ax < 3; ++ax) {
-                    cmin[ax] = min(cmin[ax], (uint32_t)__shfl_xor((int)cmin[ax], d));
-                    cmax[ax] = max(cmax[ax], (uint32_t)__shfl_xor((int)cmax[ax], d));
-                    sum[ax] += __shfl_xor(sum[ax], d);
-                }
-            }
-        }
-        if ((int)__lane_id() == leader) {
-            svr_component_record& r = a.records[lid - 1u];
-            atomicAdd(reinterpret_cast<unsigned long long*>(&r.voxels), (unsigned long long)__popcll(peers));
-#pragma unroll
-            for (int ax = 0; ax < 3; ++ax) {
-                atomicAdd(reinterpret_cast<unsigned long long*>(&r.sum[ax]), sum[ax]);
-                atomicMin(&r.lo[ax], a.lo[ax] + (int32_t)cmin[ax]);
-                atomicMax(&r.hi[ax], a.lo[ax] + (int32_t)cmax[ax]);
-            }
-        }
-    }
+    });
 }
 
 template <typename T, bool LEVEL>
@@ -280,10 +194,7 @@ hipError_t svr_launch_components(const svr_ctx* c, int lod, const int64_t lo[3],
     for (int ax = 0; ax < 3; ++ax) { h.off[ax] = st.offset[ax]; h.lo[ax] = 0; h.n[ax] = 0u; }
     hipError_t e = hipMemsetAsync(h.header, 0, 16 * sizeof(uint64_t), stream);
     if (e != hipSuccess) return e;
-    if (!plan) {                                            // no voxel: the header alone
-        hipLaunchKernelGGL(comp_scan_apply_kernel, dim3(1), dim3(kCompThreads), 0, stream, nullptr, 0u, nullptr, 1, h);
-        return hipGetLastError();
-    }
+    if (!plan) return box_scan_run<uint32_t>(nullptr, nullptr, h, stream);     // no voxel: the header alone
     const CompPlan& p = *plan;
     char* const base = static_cast<char*>(scratch);
     const bool is_level = cp.mode == SVR_COMPONENTS_LEVEL;
@@ -305,7 +216,7 @@ hipError_t svr_launch_components(const svr_ctx* c, int lod, const int64_t lo[3],
     a.ignore_zero = cp.ignore_zero; a.label_mode = is_level ? 0 : 1;
     a.parent = reinterpret_cast<uint32_t*>(base + p.parent_off);
     a.aux = reinterpret_cast<uint32_t*>(base + p.aux_off);
-    a.cnt = reinterpret_cast<uint32_t*>(base + p.cnt_off[0]);
+    a.cnt = reinterpret_cast<uint32_t*>(base + p.scan.off[0]);
     a.header = h.header;
     a.ids = ids_fit ? out.ids : nullptr;
     a.records = out.record_capacity > 0 ? out.records : nullptr;
@@ -322,29 +233,17 @@ hipError_t svr_launch_components(const svr_ctx* c, int lod, const int64_t lo[3],
     else                                       comp_launch_init<float, true>(a, false, init_blocks, stream);
     if ((e = hipGetLastError()) != hipSuccess) return e;
 
-    const dim3 grid(p.count[0]), block(kCompThreads);
+    const dim3 grid(p.scan.count[0]), block(kCompThreads);
     const bool conn26 = cp.connectivity == 26;
     if (conn26 && keyed)  hipLaunchKernelGGL((comp_merge_kernel<true, true>), grid, block, 0, stream, a);
     else if (conn26)      hipLaunchKernelGGL((comp_merge_kernel<true, false>), grid, block, 0, stream, a);
     else if (keyed)       hipLaunchKernelGGL((comp_merge_kernel<false, true>), grid, block, 0, stream, a);
     else                  hipLaunchKernelGGL((comp_merge_kernel<false, false>), grid, block, 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(comp_flatten_kernel, grid, block, 0, stream, a);
+    hipLaunchKernelGGL(uf_flatten_kernel, grid, block, 0, stream, a.parent, a.voxels, a.cnt);
     if ((e = hipGetLastError()) != hipSuccess) return e;
 
-    uint32_t* lev[kCompMaxLevels];
-    for (int k = 0; k < p.levels; ++k) lev[k] = reinterpret_cast<uint32_t*>(base + p.cnt_off[k]);
-    for (int k = 0; k + 1 < p.levels; ++k) {
-        hipLaunchKernelGGL(comp_scan_sums_kernel, dim3(p.count[k + 1]), block, 0, stream, lev[k], p.count[k], lev[k + 1]);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    const int top = p.levels - 1;
-    hipLaunchKernelGGL(comp_scan_apply_kernel, dim3(1), block, 0, stream, lev[top], p.count[top], nullptr, 1, h);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    for (int k = top - 1; k >= 0; --k) {
-        hipLaunchKernelGGL(comp_scan_apply_kernel, dim3(p.count[k + 1]), block, 0, stream, lev[k], p.count[k], lev[k + 1], 0, h);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+    if ((e = box_scan_run<uint32_t>(&p.scan, scratch, h, stream)) != hipSuccess) return e;
     // the count-only call skips the last two kernels; a call whose records cannot fit finds that out on the device
     if (!a.ids && !a.records) return hipSuccess;
     hipLaunchKernelGGL(comp_rank_kernel, grid, block, 0, stream, a);

@@ -9,8 +9,8 @@
 //   parent  one u32 per voxel: the union-find (components_uf.h); after the flatten pass the root of every inside voxel.
 //   aux     one u32 per voxel.  Until the merge pass has run: the label of an inside voxel (what connect() compares).
 //           From the rank pass on: at a root, the rank of its component (its number minus one).
-//   scan    level 0 holds one u32 per block of kCompScanBlock voxels, the roots among them; level k + 1 holds the sums
-//           of level k's blocks of kCompScanBlock entries, until one block holds a whole level.
+//   scan    level 0 holds one u32 per block of kBoxScanBlock voxels, the roots among them; the levels above it are
+//           those of box_scan.h.
 // The init pass reads a row in the units of box_units.h, 4 ring slots at a multiple of 4: voxel rx of a row is element
 // rx + head of it, head (0 .. 3; box_head) being the ring slot of the box's first voxel modulo 4, and a row has upr
 // units.  The voxels of one unit are linked along x by the init pass itself (comp_x_implied).
@@ -19,6 +19,7 @@
 
 #include <stdint.h>
 
+#include "box_scan.h"
 #include "box_units.h"
 
 #ifdef __HIPCC__
@@ -27,8 +28,8 @@
 #define COMP_FN inline
 #endif
 
-constexpr uint32_t kCompScanBlock = 256;          // entries one workgroup scans, and voxels per workgroup of the voxel passes
-constexpr int      kCompMaxLevels = 3;            // 2^30 voxels -> 2^22 counts -> 2^14 -> 2^6
+constexpr uint32_t kCompScanBlock = 256;          // voxels per workgroup of the voxel passes: the name tests/test_gpu_components.py sizes its boxes by
+static_assert(kCompScanBlock == kBoxScanBlock, "a voxel pass fills one entry of level 0 of the scan per workgroup");
 constexpr uint64_t kCompMaxVoxels = 1ull << 30;   // SVR_COMPONENTS_MAX_VOXELS
 
 struct CompPlan {
@@ -37,10 +38,8 @@ struct CompPlan {
     uint32_t head;                     // elements before a row's first voxel, 0 .. 3
     uint32_t upr;                      // units of 4 ring slots per row
     uint32_t units;                    // upr * n[1] * n[2] <= voxels
-    int32_t  levels;                   // arrays of the scan, 1 .. kCompMaxLevels
-    uint32_t count[kCompMaxLevels];    // entries of level k; count[0] = the workgroups of a voxel pass; count[levels - 1] <= kCompScanBlock
     uint64_t parent_off, aux_off;      // byte offsets into the scratch
-    uint64_t cnt_off[kCompMaxLevels];
+    BoxScanPlan scan;                  // count[0] = the workgroups of a voxel pass, kBoxScanBlock voxels each: <= 2^22, three levels at the most
     uint64_t bytes;                    // of scratch in all
 };
 
@@ -62,14 +61,8 @@ inline bool comp_plan(const int64_t n[3], uint32_t head, CompPlan& p, bool* too_
     p.head = head;
     p.upr = (p.n[0] + head + 3u) / 4u;
     p.units = p.upr * p.n[1] * p.n[2];           // upr <= n[0] but for rows of one voxel, where it is 1 too
-    p.levels = box_scan_levels((p.voxels + kCompScanBlock - 1u) / kCompScanBlock, kCompScanBlock, kCompMaxLevels, p.count);
     p.parent_off = 0;
     p.aux_off = voxels * 4u;
-    uint64_t at = voxels * 8u;
-    for (int k = 0; k < kCompMaxLevels; ++k) {
-        p.cnt_off[k] = at;
-        at += (uint64_t)p.count[k] * 4u;
-    }
-    p.bytes = at;
+    p.bytes = box_scan_plan((p.voxels + kBoxScanBlock - 1u) / kBoxScanBlock, 4u, voxels * 8u, p.scan);
     return true;
 }

@@ -12,6 +12,8 @@
 //   * uf_union retries only when the atomic minimum returned something other than the root it assumed, and goes on from
 //     that returned value: the larger of its two indices shrinks with every retry, so it ends too.
 // No thread ever waits for another one.
+// svr_split keeps its summits in such an array too (split_kernels.hip); the flatten kernel at the end is the pass that
+// follows the unions in both chains.
 #pragma once
 
 #include <stdint.h>
@@ -98,3 +100,23 @@ UF_FN void uf_merge_voxel(uint32_t* parent, const uint32_t* aux, uint32_t i, con
         if (rx + 1u < n[0] && uf_connects<KEYED>(parent, aux, key, j + 1u)) uf_union(parent, i, j + 1u);
     }
 }
+
+#ifdef __HIPCC__
+// The flatten pass, a thread per entry: parent[i] = root(i), and into cnt[workgroup] the number of roots among the
+// workgroup's kBoxScanBlock entries: level 0 of the scan (box_scan.h).  static: no template, and in two units.
+static __global__ __launch_bounds__(kBoxScanBlock) void uf_flatten_kernel(uint32_t* parent, uint32_t voxels, uint32_t* cnt) {
+    __shared__ uint32_t part[kBoxScanWaves];
+    const uint32_t i = blockIdx.x * kBoxScanBlock + threadIdx.x;
+    uint32_t is_root = 0u;
+    if (i < voxels) {
+        const uint32_t p = uf_load(parent + i);
+        if (p != kUfOutside) {
+            const uint32_t r = uf_find(parent, p);
+            if (r != p) (void)uf_min(parent + i, r);
+            is_root = r == i;
+        }
+    }
+    const uint32_t total = box_block_sum(is_root, part);
+    if (threadIdx.x == 0u) cnt[blockIdx.x] = total;
+}
+#endif

@@ -21,11 +21,12 @@
 //   finish   one thread: unpacks that maximum into header [3] and [14].
 // Every store is an ordinary vector store; the only atomics are the counters of the header.
 //
-// svr_nearest (the nearest source of every voxel) runs the same chain without a border, with kernels of its own for x, y
-// and z that also store who owns each voxel along the axis (u16 planes in the scratch: distance_plan.h), and ends with
+// svr_nearest (the nearest source of every voxel) runs the same chain without a border, in the OWN instantiations of the
+// x, y and z kernels, which also store who owns each voxel along the axis (u16 planes in the scratch: distance_plan.h),
+// and ends with
 //   compose  a thread per voxel: z' = own_z[z][y][x], y' = own_y[z'][y][x], x' = own_x[z'][y'][x], the dense index of
 //            (x', y', z') into index, and one gather from the label ring at that voxel's ring slot into label.
-// init, header and finish are svr_distance's kernels, and so are the stack, the ring in LDS and the reduction of the header.
+// Everything else is one text for both calls.
 #include "svr_host.h"
 #include "distance_plan.h"
 #include "distance_scan.h"
@@ -122,17 +123,26 @@ __global__ void dist_finish_kernel(unsigned long long* header) {
 }
 
 // ---- x ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kDistThreads) void dist_x_kernel(const DistArgs a) {
+// OWN (svr_nearest): and the row voxel of that source into own[i]; else own is not used
+template <bool OWN>
+__global__ __launch_bounds__(kDistThreads) void dist_x_kernel(const DistArgs a, uint16_t* const own) {
     const uint32_t i = blockIdx.x * kDistThreads + threadIdx.x;
     if (i >= a.voxels) return;
     const uint32_t row = i / a.n[0], rx = i - row * a.n[0];
-    a.d2[i] = dist_row_nearest(a.bits + (size_t)row * a.wpr, a.wpr, rx + a.head);
+    if constexpr (OWN) {
+        uint32_t at = kDistNoOwner + a.head;
+        a.d2[i] = dist_row_nearest_at(a.bits + (size_t)row * a.wpr, a.wpr, rx + a.head, &at);
+        own[i] = (uint16_t)(at - a.head);                    // an element of the row -> a voxel of it
+    } else {
+        a.d2[i] = dist_row_nearest(a.bits + (size_t)row * a.wpr, a.wpr, rx + a.head);
+    }
 }
 
 // ---- y and z ------------------------------------------------------------------------------------------------------------
-// FINAL: the z pass, else the y pass.  columns = voxels / length.
-template <bool FINAL>
-__global__ __launch_bounds__(kDistColumnThreads) void dist_column_kernel(const DistArgs a, uint32_t columns) {
+// FINAL: the z pass, else the y pass.  columns = voxels / length.  OWN (svr_nearest): the owner of every position into
+// the plane `own`, and no border; else own is not used.
+template <bool FINAL, bool OWN>
+__global__ __launch_bounds__(kDistColumnThreads) void dist_column_kernel(const DistArgs a, uint16_t* const own, uint32_t columns) {
     __shared__ DistEntry slots[kDistRingEntries * kDistColumnThreads];     // slot j of lane l at [j * 64 + l]: no bank conflicts
     const DistRing<kDistRingEntries> ring(slots + threadIdx.x, kDistColumnThreads);
     const uint32_t c = blockIdx.x * kDistColumnThreads + threadIdx.x;
@@ -144,27 +154,28 @@ __global__ __launch_bounds__(kDistColumnThreads) void dist_column_kernel(const D
         const uint32_t base = FINAL ? c : other * n1 * n0 + x;
         const uint32_t stride = FINAL ? n0 * n1 : n0, length = FINAL ? n2 : n1;
         int32_t* const col = a.d2 + base;
-        if (FINAL) {
-            // the squared distance to the nearest lattice point beyond the box is ((face distance) + 1)^2; without a
-            // border nothing lies there
-            const bool border = a.border != 0 && a.invert == 0;
-            const uint32_t fxy = min(min(x + 1u, n0 - x), min(other + 1u, n1 - other));
-            dist_scan_column(col, stride, length, a.stack + c, columns, ring, [&](uint32_t u, int32_t v) {
-                if (border && v != 0) {
-                    const uint32_t f = min(fxy, min(u + 1u, n2 - u));
-                    v = min(v, (int32_t)(f * f));
-                }
-                col[(size_t)u * stride] = v;
+        // the squared distance to the nearest lattice point beyond the box is ((face distance) + 1)^2; without a
+        // border nothing lies there
+        const bool border = FINAL && !OWN && a.border != 0 && a.invert == 0;
+        const uint32_t fxy = min(min(x + 1u, n0 - x), min(other + 1u, n1 - other));
+        const auto sink = [&](uint32_t u, int32_t v, uint32_t s) {
+            if (border && v != 0) {
+                const uint32_t f = min(fxy, min(u + 1u, n2 - u));
+                v = min(v, (int32_t)(f * f));
+            }
+            col[(size_t)u * stride] = v;
+            if (OWN) own[base + (size_t)u * stride] = (uint16_t)s;
+            if (FINAL) {
                 if (v == kDistFar) ++far;
                 else if (v != 0) {
                     // u runs downward: an equal value at a smaller index replaces the key, as its low half is larger
                     const unsigned long long k = ((unsigned long long)(uint32_t)v << 32) | (0xFFFFFFFFu - (base + u * stride));
                     if (k > key) key = k;
                 }
-            });
-        } else {
-            dist_scan_column(col, stride, length, a.stack + c, columns, ring, [&](uint32_t u, int32_t v) { col[(size_t)u * stride] = v; });
-        }
+            }
+        };
+        if constexpr (OWN) dist_scan_column_owner(col, stride, length, a.stack + c, columns, ring, sink);
+        else dist_scan_column(col, stride, length, a.stack + c, columns, ring, [&](uint32_t u, int32_t v) { sink(u, v, 0u); });
     }
     if (FINAL) {
 #pragma unroll
@@ -180,62 +191,12 @@ __global__ __launch_bounds__(kDistColumnThreads) void dist_column_kernel(const D
     }
 }
 
-// ---- svr_nearest: x, y, z with owners, compose ------------------------------------------------------------------------------
+// ---- svr_nearest: compose -----------------------------------------------------------------------------------------------
 struct NearOut {
     uint16_t* own[3];          // the owner planes of the x, y and z pass (distance_plan.h)
     int32_t* index;
     uint32_t* label;           // null: not written
 };
-
-__global__ __launch_bounds__(kDistThreads) void near_x_kernel(const DistArgs a, uint16_t* const own) {
-    const uint32_t i = blockIdx.x * kDistThreads + threadIdx.x;
-    if (i >= a.voxels) return;
-    const uint32_t row = i / a.n[0], rx = i - row * a.n[0];
-    uint32_t at = kDistNoOwner + a.head;
-    a.d2[i] = dist_row_nearest_at(a.bits + (size_t)row * a.wpr, a.wpr, rx + a.head, &at);
-    own[i] = (uint16_t)(at - a.head);                        // an element of the row -> a voxel of it
-}
-
-// dist_column_kernel without a border, and the owner of every position into its plane
-template <bool FINAL>
-__global__ __launch_bounds__(kDistColumnThreads) void near_column_kernel(const DistArgs a, uint16_t* const own, uint32_t columns) {
-    __shared__ DistEntry slots[kDistRingEntries * kDistColumnThreads];
-    const DistRing<kDistRingEntries> ring(slots + threadIdx.x, kDistColumnThreads);
-    const uint32_t c = blockIdx.x * kDistColumnThreads + threadIdx.x;
-    const uint32_t n0 = a.n[0], n1 = a.n[1], n2 = a.n[2];
-    uint32_t far = 0u;
-    unsigned long long key = 0ull;
-    if (c < columns) {
-        const uint32_t x = c % n0, other = c / n0;           // FINAL: other is y; else z
-        const uint32_t base = FINAL ? c : other * n1 * n0 + x;
-        const uint32_t stride = FINAL ? n0 * n1 : n0, length = FINAL ? n2 : n1;
-        int32_t* const col = a.d2 + base;
-        uint16_t* const who = own + base;
-        dist_scan_column_owner(col, stride, length, a.stack + c, columns, ring, [&](uint32_t u, int32_t v, uint32_t s) {
-            col[(size_t)u * stride] = v;
-            who[(size_t)u * stride] = (uint16_t)s;
-            if (FINAL) {
-                if (v == kDistFar) ++far;
-                else if (v != 0) {
-                    const unsigned long long k = ((unsigned long long)(uint32_t)v << 32) | (0xFFFFFFFFu - (base + u * stride));
-                    if (k > key) key = k;
-                }
-            }
-        });
-    }
-    if (FINAL) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            far += (uint32_t)__shfl_xor((int)far, d);
-            const unsigned long long o = __shfl_xor(key, d);
-            if (o > key) key = o;
-        }
-        if (__lane_id() == 0u) {
-            if (key) atomicMax(&a.header[3], key);
-            if (far) atomicAdd(&a.header[15], (unsigned long long)far);
-        }
-    }
-}
 
 // Every owner is compared with its extent before it is used: kDistNoOwner, of a column without a source, fails it, and no
 // gather leaves its plane or the ring.  An owner that the z pass names has a finite value, so the two below it exist.
@@ -262,15 +223,17 @@ __global__ __launch_bounds__(kDistThreads) void near_compose_kernel(const DistAr
     if (o.label) o.label[i] = label;
 }
 
-// What both launchers begin with: the header zeroed, then for a box that is not empty (plan) a and h filled, the init pass
-// and the header kernel.  *go: d2 is to be written, the rest of the chain follows.
-hipError_t dist_begin(const svr_ctx* c, int lod, const int64_t lo[3], const DistPlan* plan, const svr_distance_params& dp, void* scratch,
-                      const svr_distance_outputs& out, hipStream_t stream, DistArgs& a, bool* go) {
+// What both calls want of a box: P is svr_distance_params or svr_nearest_params, whose fields of the same names mean the same.
+// The header zeroed, then for a box that is not empty (plan) a and h filled, the init pass and the header kernel.  *go: d2
+// is to be written, dist_axes follows.
+template <class P>
+hipError_t dist_begin(const svr_ctx* c, int lod, const int64_t lo[3], const DistPlan* plan, const P& dp, int border, void* scratch,
+                      int32_t* d2, uint64_t capacity, uint64_t* header, hipStream_t stream, DistArgs& a, bool* go) {
     *go = false;
     const LodStorage& L = c->lod[lod];
     const svr_lod_state& st = L.state;
     DistHeader h;
-    h.header = reinterpret_cast<unsigned long long*>(out.header);
+    h.header = reinterpret_cast<unsigned long long*>(header);
     h.voxels = 0ull; h.written = 0ull; h.invert = dp.invert != 0;
     for (int ax = 0; ax < 3; ++ax) { h.off[ax] = st.offset[ax]; h.lo[ax] = 0; h.n[ax] = 0u; }
     hipError_t e = hipMemsetAsync(h.header, 0, 16 * sizeof(uint64_t), stream);
@@ -282,7 +245,7 @@ hipError_t dist_begin(const svr_ctx* c, int lod, const int64_t lo[3], const Dist
     const DistPlan& p = *plan;
     char* const base = static_cast<char*>(scratch);
     const bool is_level = dp.mode == SVR_COMPONENTS_LEVEL;
-    const bool fits = out.d2_capacity >= (uint64_t)p.voxels;
+    const bool fits = capacity >= (uint64_t)p.voxels;
     a.density = L.density; a.labels = L.labels;
     for (int ax = 0; ax < 3; ++ax) {
         a.ring[ax] = (uint32_t)L.ring[ax];
@@ -293,10 +256,10 @@ hipError_t dist_begin(const svr_ctx* c, int lod, const int64_t lo[3], const Dist
     a.voxels = p.voxels; a.head = p.head; a.upr = p.upr; a.wpr = p.wpr; a.units = p.units;
     a.level = dp.level;
     a.sel = is_level ? nullptr : dp.selected; a.nsel = is_level ? 0u : dp.selected_count;
-    a.ignore_zero = is_level ? 0 : dp.ignore_zero; a.invert = dp.invert != 0; a.border = dp.border != 0;
+    a.ignore_zero = is_level ? 0 : dp.ignore_zero; a.invert = dp.invert != 0; a.border = border != 0;
     a.bits = reinterpret_cast<uint32_t*>(base + p.bits_off);
     a.stack = reinterpret_cast<DistEntry*>(base + p.stack_off);
-    a.d2 = fits ? out.d2 : nullptr;
+    a.d2 = fits ? d2 : nullptr;
     a.header = h.header;
     h.voxels = p.voxels; h.written = fits ? (unsigned long long)p.voxels : 0ull;
 
@@ -315,6 +278,23 @@ hipError_t dist_begin(const svr_ctx* c, int lod, const int64_t lo[3], const Dist
     return hipSuccess;
 }
 
+// x, y, z and finish.  OWN: own[3], the owner planes of the three passes; else own is null.
+template <bool OWN>
+hipError_t dist_axes(const DistPlan& p, const DistArgs& a, uint16_t* const* own, hipStream_t stream) {
+    const dim3 block(kDistThreads), column_block(kDistColumnThreads);
+    hipError_t e;
+    hipLaunchKernelGGL(dist_x_kernel<OWN>, dim3((p.voxels + kDistThreads - 1u) / kDistThreads), block, 0, stream, a, OWN ? own[0] : nullptr);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL((dist_column_kernel<false, OWN>), dim3((p.columns[0] + kDistColumnThreads - 1u) / kDistColumnThreads), column_block, 0,
+                       stream, a, OWN ? own[1] : nullptr, p.columns[0]);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL((dist_column_kernel<true, OWN>), dim3((p.columns[1] + kDistColumnThreads - 1u) / kDistColumnThreads), column_block, 0,
+                       stream, a, OWN ? own[2] : nullptr, p.columns[1]);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(dist_finish_kernel, dim3(1), dim3(1), 0, stream, a.header);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 // lo: the first voxel of the box (box and window intersected) in logical voxels of the LOD; plan: dist_plan of its
@@ -324,54 +304,23 @@ hipError_t svr_launch_distance(const svr_ctx* c, int lod, const int64_t lo[3], c
                                void* scratch, const svr_distance_outputs& out, hipStream_t stream) {
     DistArgs a;
     bool go;
-    hipError_t e = dist_begin(c, lod, lo, plan, dp, scratch, out, stream, a, &go);
+    const hipError_t e = dist_begin(c, lod, lo, plan, dp, dp.border, scratch, out.d2, out.d2_capacity, out.header, stream, a, &go);
     if (e != hipSuccess || !go) return e;
-    const DistPlan& p = *plan;
-    const dim3 block(kDistThreads);
-
-    hipLaunchKernelGGL(dist_x_kernel, dim3((p.voxels + kDistThreads - 1u) / kDistThreads), block, 0, stream, a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    const dim3 column_block(kDistColumnThreads);
-    hipLaunchKernelGGL((dist_column_kernel<false>), dim3((p.columns[0] + kDistColumnThreads - 1u) / kDistColumnThreads), column_block, 0,
-                       stream, a, p.columns[0]);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL((dist_column_kernel<true>), dim3((p.columns[1] + kDistColumnThreads - 1u) / kDistColumnThreads), column_block, 0,
-                       stream, a, p.columns[1]);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(dist_finish_kernel, dim3(1), dim3(1), 0, stream, a.header);
-    return hipGetLastError();
+    return dist_axes<false>(*plan, a, nullptr, stream);
 }
 
-// As svr_launch_distance with border = 0; plan: near_plan of the box's extent.  Everything was validated by svr_nearest.
+// As svr_launch_distance without a border; plan: near_plan of the box's extent.  Everything was validated by svr_nearest.
 hipError_t svr_launch_nearest(const svr_ctx* c, int lod, const int64_t lo[3], const NearPlan* plan, const svr_nearest_params& np,
                               void* scratch, const svr_nearest_outputs& out, hipStream_t stream) {
-    svr_distance_params dp;
-    dp.lod = np.lod; dp.use_box = np.use_box;
-    for (int ax = 0; ax < 3; ++ax) { dp.box_off[ax] = np.box_off[ax]; dp.box_shape[ax] = np.box_shape[ax]; }
-    dp.mode = np.mode; dp.level = np.level; dp.selected = np.selected; dp.selected_count = np.selected_count;
-    dp.ignore_zero = np.ignore_zero; dp.invert = np.invert; dp.border = 0;
-    const svr_distance_outputs dout = {out.d2, out.capacity, out.header};
     DistArgs a;
     bool go;
-    hipError_t e = dist_begin(c, lod, lo, plan ? &plan->d : nullptr, dp, scratch, dout, stream, a, &go);
+    hipError_t e = dist_begin(c, lod, lo, plan ? &plan->d : nullptr, np, 0, scratch, out.d2, out.capacity, out.header, stream, a, &go);
     if (e != hipSuccess || !go) return e;
     const DistPlan& p = plan->d;
-    char* const base = static_cast<char*>(scratch);
     NearOut o;
-    for (int ax = 0; ax < 3; ++ax) o.own[ax] = reinterpret_cast<uint16_t*>(base + plan->own_off[ax]);
+    for (int ax = 0; ax < 3; ++ax) o.own[ax] = reinterpret_cast<uint16_t*>(static_cast<char*>(scratch) + plan->own_off[ax]);
     o.index = out.index; o.label = out.label;
-    const dim3 block(kDistThreads), voxel_grid((p.voxels + kDistThreads - 1u) / kDistThreads), column_block(kDistColumnThreads);
-
-    hipLaunchKernelGGL(near_x_kernel, voxel_grid, block, 0, stream, a, o.own[0]);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL((near_column_kernel<false>), dim3((p.columns[0] + kDistColumnThreads - 1u) / kDistColumnThreads), column_block, 0,
-                       stream, a, o.own[1], p.columns[0]);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL((near_column_kernel<true>), dim3((p.columns[1] + kDistColumnThreads - 1u) / kDistColumnThreads), column_block, 0,
-                       stream, a, o.own[2], p.columns[1]);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(dist_finish_kernel, dim3(1), dim3(1), 0, stream, a.header);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(near_compose_kernel, voxel_grid, block, 0, stream, a, o);
+    if ((e = dist_axes<true>(p, a, o.own, stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(near_compose_kernel, dim3((p.voxels + kDistThreads - 1u) / kDistThreads), dim3(kDistThreads), 0, stream, a, o);
     return hipGetLastError();
 }

@@ -94,40 +94,14 @@ inline bool near_plan(const int64_t n[3], uint32_t head, NearPlan& p, int* refus
 }
 
 // The squared distance of voxel r (0 <= r < n) of a row to the nearest source of the row, or kDistFar: the x pass.
-// words: the row's wpr words of source bits; e = r + head.  Walks outwards word by word, bounded by the row.
-DIST_FN int32_t dist_row_nearest(const uint32_t* words, uint32_t wpr, uint32_t e) {
+// words: the row's wpr words of source bits; e = r + head.  Walks outwards word by word, bounded by the row.  AT: and
+// into *at the element of that source: of two at the same distance the left one (the smaller element), e itself where e
+// is a source, untouched with kDistFar; else `at` is not used.
+template <bool AT>
+DIST_FN int32_t dist_row_walk(const uint32_t* words, uint32_t wpr, uint32_t e, uint32_t* at) {
     const uint32_t wi = e >> 5, b = e & 31u;
     const uint32_t w = words[wi];
-    if ((w >> b) & 1u) return 0;
-    uint32_t best = 0xFFFFFFFFu;
-    uint32_t m = w & ((1u << b) - 1u);                                   // the bits below b
-    for (uint32_t k = wi;;) {
-        if (m) {
-            best = e - (32u * k + 31u - (uint32_t)__builtin_clz(m));
-            break;
-        }
-        if (k == 0u) break;
-        m = words[--k];
-    }
-    m = b == 31u ? 0u : (w & (0xFFFFFFFFu << (b + 1u)));                 // the bits above b
-    for (uint32_t k = wi;;) {
-        if (m) {
-            const uint32_t d = 32u * k + (uint32_t)__builtin_ctz(m) - e;
-            if (d < best) best = d;
-            break;
-        }
-        if (++k == wpr) break;
-        m = words[k];
-    }
-    return best == 0xFFFFFFFFu ? kDistFar : (int32_t)(best * best);
-}
-
-// The same, and into *at the element of that source: of two at the same distance the left one (the smaller element), e
-// itself where e is a source, untouched with kDistFar.  svr_nearest's x pass.
-DIST_FN int32_t dist_row_nearest_at(const uint32_t* words, uint32_t wpr, uint32_t e, uint32_t* at) {
-    const uint32_t wi = e >> 5, b = e & 31u;
-    const uint32_t w = words[wi];
-    if ((w >> b) & 1u) { *at = e; return 0; }
+    if ((w >> b) & 1u) { if (AT) *at = e; return 0; }
     uint32_t best = 0xFFFFFFFFu, where = 0u;
     uint32_t m = w & ((1u << b) - 1u);                                   // the bits below b
     for (uint32_t k = wi;;) {
@@ -150,6 +124,10 @@ DIST_FN int32_t dist_row_nearest_at(const uint32_t* words, uint32_t wpr, uint32_
         m = words[k];
     }
     if (best == 0xFFFFFFFFu) return kDistFar;
-    *at = where;
+    if (AT) *at = where;
     return (int32_t)(best * best);
 }
+
+// svr_distance's x pass, and svr_nearest's
+DIST_FN int32_t dist_row_nearest(const uint32_t* words, uint32_t wpr, uint32_t e) { return dist_row_walk<false>(words, wpr, e, nullptr); }
+DIST_FN int32_t dist_row_nearest_at(const uint32_t* words, uint32_t wpr, uint32_t e, uint32_t* at) { return dist_row_walk<true>(words, wpr, e, at); }

@@ -9,15 +9,15 @@
 //   classify   bit operations only: a thread makes one word of 16 cells from 17 bits of each of the 4 voxel rows
 //              (y, y + 1) x (z, z + 1); the x neighbour is the same bits shifted by one.  Rows outside the box read as
 //              zero without touching memory.  Writes the word and its two counts (active cells, crossing edges).
-//   scan       an exclusive prefix of the two counts in place: per-block sums level by level, one workgroup over the
-//              top level (which also writes header[0 .. 6]), then each level adds its block's prefix on the way down.
-//              Workgroups never wait for one another inside a launch.
+//   scan       an exclusive prefix of the two counts in place: the scan of box_scan.h on uint2, whose top level writes
+//              header[0 .. 6] (MeshTop).
 //   emit       a thread per cell.  The index of a cell's vertex is prefix[word] + popcount(active bits below it), that
 //              of its quads likewise; the corners' inside bits come from the bit map, and only SVR_MESH_LEVEL reads
 //              the rings again, for the values at an active cell's corners.  Does nothing when a capacity is too small.
 // All stores are ordinary vector stores; the one atomic is the u64 add of the inside-voxel count, once per wave.
 #include "svr_host.h"
 #include "mesh_plan.h"
+#include "box_scan.h"
 #include "box_units.h"
 
 namespace {
@@ -133,56 +133,21 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_classify_kernel(const MeshA
 }
 
 // ---- scan ---------------------------------------------------------------------------------------------------------------
-// out[b] = the sum of block b's kMeshScanBlock entries of in[0 .. n)
-__global__ __launch_bounds__(kMeshThreads) void mesh_scan_sums_kernel(const uint2* in, uint32_t n, uint2* out) {
-    static_assert(kMeshScanBlock == kMeshThreads, "one entry per thread");
-    __shared__ uint2 part[kMeshThreads / 64];
-    const uint32_t i = blockIdx.x * kMeshScanBlock + threadIdx.x;
-    uint2 v = i < n ? in[i] : make_uint2(0u, 0u);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        v.x += (uint32_t)__shfl_xor((int)v.x, d);
-        v.y += (uint32_t)__shfl_xor((int)v.y, d);
-    }
-    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        uint2 s = part[0];
-        for (int k = 1; k < kMeshThreads / 64; ++k) { s.x += part[k].x; s.y += part[k].y; }
-        out[blockIdx.x] = s;
-    }
-}
-
-// data[0 .. n): every block's entries become their exclusive prefix inside the block plus base[block] (null: 0).  With a
-// header (the top level: one block holds it all) the totals go there: V, T = 2 x quads, what a call with these capacities
-// writes, and the window offset.
-__global__ __launch_bounds__(kMeshThreads) void mesh_scan_apply_kernel(uint2* data, uint32_t n, const uint2* base, unsigned long long* header,
-                                                                       unsigned long long vcap, unsigned long long tcap,
-                                                                       int32_t ox, int32_t oy, int32_t oz) {
-    __shared__ uint2 part[kMeshThreads / 64];
-    const uint32_t i = blockIdx.x * kMeshScanBlock + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint2 v = i < n ? data[i] : make_uint2(0u, 0u);
-    uint2 inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t px = (uint32_t)__shfl_up((int)inc.x, d), py = (uint32_t)__shfl_up((int)inc.y, d);
-        if (lane >= (uint32_t)d) { inc.x += px; inc.y += py; }
-    }
-    if (lane == 63u) part[wave] = inc;
-    __syncthreads();
-    uint2 before = base ? base[blockIdx.x] : make_uint2(0u, 0u);
-    for (uint32_t k = 0; k < wave; ++k) { before.x += part[k].x; before.y += part[k].y; }
-    if (i < n) data[i] = make_uint2(before.x + inc.x - v.x, before.y + inc.y - v.y);
-    if (header && threadIdx.x == kMeshThreads - 1) {
-        const unsigned long long V = (unsigned long long)before.x + inc.x, T = 2ull * ((unsigned long long)before.y + inc.y);
+// What the top level of the scan (box_scan.h) does with the totals: V, T = 2 x quads, what a call with these capacities
+// writes, and the window offset, into header[0 .. 6].
+struct MeshTop {
+    unsigned long long* header;
+    unsigned long long vcap, tcap;
+    int32_t off[3];
+    __device__ void operator()(uint2 total) const {
+        const unsigned long long V = total.x, T = 2ull * total.y;
         const bool fits = V <= vcap && T <= tcap;
         header[0] = V; header[1] = T;
         header[2] = fits ? V : 0ull; header[3] = fits ? T : 0ull;
-        header[4] = (unsigned long long)(long long)ox;
-        header[5] = (unsigned long long)(long long)oy;
-        header[6] = (unsigned long long)(long long)oz;
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) header[4 + ax] = (unsigned long long)(long long)off[ax];
     }
-}
+};
 
 // ---- emit ---------------------------------------------------------------------------------------------------------------
 // inside(voxel (rx, ry, rz) of the box), from the bit map; coordinates outside the box (negative ones wrapped) are outside
@@ -318,14 +283,10 @@ hipError_t svr_launch_mesh(const svr_ctx* c, int lod, const int64_t lo[3], const
     const LodStorage& L = c->lod[lod];
     const svr_lod_state& st = L.state;
     unsigned long long* const header = reinterpret_cast<unsigned long long*>(out.header);
+    const MeshTop top = {header, out.vertex_capacity, out.triangle_capacity, {st.offset[0], st.offset[1], st.offset[2]}};
     hipError_t e = hipMemsetAsync(header, 0, 8 * sizeof(uint64_t), stream);
     if (e != hipSuccess) return e;
-    if (!plan) {                                            // the empty mesh: the header alone
-        hipLaunchKernelGGL(mesh_scan_apply_kernel, dim3(1), dim3(kMeshThreads), 0, stream, nullptr, 0u, nullptr, header,
-                           (unsigned long long)out.vertex_capacity, (unsigned long long)out.triangle_capacity, st.offset[0], st.offset[1],
-                           st.offset[2]);
-        return hipGetLastError();
-    }
+    if (!plan) return box_scan_run<uint2>(nullptr, nullptr, top, stream);      // the empty mesh: the header alone
     const MeshPlan& p = *plan;
     char* const base = static_cast<char*>(scratch);
     MeshArgs a;
@@ -340,7 +301,7 @@ hipError_t svr_launch_mesh(const svr_ctx* c, int lod, const int64_t lo[3], const
     a.level = level; a.sel = sel; a.nsel = nsel;
     a.bits = reinterpret_cast<uint32_t*>(base + p.bit_off);
     a.nib = reinterpret_cast<unsigned long long*>(base + p.nib_off);
-    a.cnt = reinterpret_cast<uint2*>(base + p.cnt_off[0]);
+    a.cnt = reinterpret_cast<uint2*>(base + p.scan.off[0]);
     a.header = header;
     a.vertices = out.vertices; a.triangles = out.triangles;
     a.vcap = out.vertex_capacity; a.tcap = out.triangle_capacity;
@@ -354,22 +315,7 @@ hipError_t svr_launch_mesh(const svr_ctx* c, int lod, const int64_t lo[3], const
     hipLaunchKernelGGL(mesh_classify_kernel, dim3((p.words + kMeshThreads - 1) / kMeshThreads), dim3(kMeshThreads), 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
 
-    uint2* lev[kMeshMaxLevels];
-    for (int k = 0; k < p.levels; ++k) lev[k] = reinterpret_cast<uint2*>(base + p.cnt_off[k]);
-    for (int k = 0; k + 1 < p.levels; ++k) {
-        hipLaunchKernelGGL(mesh_scan_sums_kernel, dim3(p.count[k + 1]), dim3(kMeshThreads), 0, stream, lev[k], p.count[k], lev[k + 1]);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    const int top = p.levels - 1;
-    hipLaunchKernelGGL(mesh_scan_apply_kernel, dim3(1), dim3(kMeshThreads), 0, stream, lev[top], p.count[top], nullptr, header,
-                       (unsigned long long)out.vertex_capacity, (unsigned long long)out.triangle_capacity, st.offset[0], st.offset[1],
-                       st.offset[2]);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    for (int k = top - 1; k >= 0; --k) {
-        hipLaunchKernelGGL(mesh_scan_apply_kernel, dim3(p.count[k + 1]), dim3(kMeshThreads), 0, stream, lev[k], p.count[k], lev[k + 1], nullptr,
-                           0ull, 0ull, 0, 0, 0);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+    if ((e = box_scan_run<uint2>(&p.scan, scratch, top, stream)) != hipSuccess) return e;
     // the count-only call, and one that cannot fit, skip the last kernel
     const bool emit = out.vertex_capacity > 0 && out.triangle_capacity > 0;
     mesh_launch_step(a, c->density_storage, is_level, 0u, emit, stream, 1);

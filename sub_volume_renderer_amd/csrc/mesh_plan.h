@@ -13,18 +13,19 @@
 //          the surface; bit 3: the cell is active); 16 cells are one 64-bit word, and a row of cells is a whole number
 //          of words, so that a word never spans two rows; the cells a row's last word has too many are zero.  Words are
 //          in row order (z, then y), which is the order of vertices and quads.
-//   scan   level 0 holds two u32 counts per word of cells (active cells, crossing edges); level k + 1 holds the sums of
-//          level k's blocks of kMeshScanBlock entries, until one block holds a whole level.
+//   scan   level 0 holds two u32 counts per word of cells (active cells, crossing edges); the levels above it are those
+//          of box_scan.h.
 // About 1 byte per cell for cells and scan, and an eighth of a byte per voxel for the bits.
 #pragma once
 
 #include <stdint.h>
 
+#include "box_scan.h"
 #include "box_units.h"
 
 constexpr uint32_t kMeshCellsPerWord = 16;
-constexpr uint32_t kMeshScanBlock = 256;          // entries one workgroup scans: one per thread
-constexpr int      kMeshMaxLevels = 4;            // 2^28 words -> 2^20 -> 2^12 -> 2^4
+constexpr uint32_t kMeshScanBlock = 256;          // words of cells per scan block: the name tests/test_gpu_mesh.py sizes its windows by
+static_assert(kMeshScanBlock == kBoxScanBlock, "the scan of box_scan.h is the one that runs");
 constexpr uint64_t kMeshMaxCells = 1ull << 28;    // SVR_MESH_MAX_CELLS
 
 struct MeshPlan {
@@ -36,10 +37,8 @@ struct MeshPlan {
     uint32_t wpr;                      // words per row of cells
     uint32_t rows;                     // cells[1] * cells[2]
     uint32_t words;                    // wpr * rows  (<= the number of cells)
-    int32_t  levels;                   // arrays of the scan, 1 .. kMeshMaxLevels
-    uint32_t count[kMeshMaxLevels];    // entries of level k; count[0] = words, count[levels - 1] <= kMeshScanBlock
     uint64_t nib_off;                  // byte offsets into the scratch: the words of cells,
-    uint64_t cnt_off[kMeshMaxLevels];  // the levels of the scan (8 bytes per entry),
+    BoxScanPlan scan;                  // the scan (8 bytes per entry; count[0] = words <= 2^28: four levels at the most),
     uint64_t bit_off;                  // the bits
     uint64_t bytes;                    // of scratch in all
 };
@@ -63,13 +62,8 @@ inline bool mesh_plan(const int64_t n[3], uint32_t head, MeshPlan& p, bool* too_
     p.wpr = (p.cells[0] + kMeshCellsPerWord - 1u) / kMeshCellsPerWord;
     p.rows = p.cells[1] * p.cells[2];
     p.words = p.wpr * p.rows;                    // wpr <= cells[0]: no more words than cells
-    p.levels = box_scan_levels(p.words, kMeshScanBlock, kMeshMaxLevels, p.count);
     p.nib_off = 0;
-    uint64_t at = (uint64_t)p.words * 8u;
-    for (int k = 0; k < kMeshMaxLevels; ++k) {
-        p.cnt_off[k] = at;
-        at += (uint64_t)p.count[k] * 8u;
-    }
+    uint64_t at = box_scan_plan(p.words, 8u, (uint64_t)p.words * 8u, p.scan);
     p.bit_off = at;
     at += (uint64_t)p.bit_words * 4u;
     p.bytes = at;

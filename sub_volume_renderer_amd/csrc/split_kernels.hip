@@ -22,13 +22,13 @@
 //            agent-scope atomic loads holds because this kernel reads uf through uf_union alone.  The test reads
 //            height and up only, which no thread writes here: which pair of two basins comes first does not matter.
 //   flatten  uf[S] = root(S), the smallest summit of S's region: its seed; and the number of seeds among each
-//            workgroup's voxels: level 0 of the scan.
-//   scan     an exclusive prefix of those counts in place (this unit's copy of the scan of components_kernels.hip);
-//            the one workgroup over the top level also writes the header.
+//            workgroup's voxels: level 0 of the scan (components_uf.h: uf_flatten_kernel, on uf).
+//   scan     an exclusive prefix of those counts in place: the scan of box_scan.h on u32, whose top level writes the
+//            header (SplitHeader).
 //   rank     the number of seeds before a seed is its region's number minus one: into aux[seed]; and, when the records
 //            fit, the seed starts its record.
 //   emit     ids[i] = aux[uf[up[i]]] + 1, and the voxel's share of its record.  The lanes of a wave that belong to one
-//            region reduce their shares with shuffles first, as comp_emit_kernel does.  A summit adds 1 to basins and
+//            region reduce their shares with shuffles first (box_scan.h: box_wave_groups).  A summit adds 1 to basins and
 //            offers split_key(height, index) to a 64-bit atomic maximum kept in the record's top[0..1].
 //   finish   a thread per record unpacks that maximum into top[3] and peak.
 // The count-only call ends behind the scan.  uf is written by the up pass and by atomic minima alone; every other store
@@ -40,11 +40,12 @@
 #include "split_plan.h"
 #include "split_link.h"
 #include "components_uf.h"
+#include "box_scan.h"
 
 namespace {
 
 constexpr int kSplitThreads = 256;
-static_assert(kSplitScanBlock == (uint32_t)kSplitThreads, "one entry, and one voxel, per thread");
+static_assert(kBoxScanBlock == (uint32_t)kSplitThreads, "one entry, and one voxel, per thread");
 static_assert(kSplitOutside == kUfOutside, "uf is an array of components_uf.h");
 static_assert(sizeof(svr_split_record) == 80 && offsetof(svr_split_record, top) % 8 == 0, "top[0..1] holds a 64-bit maximum");
 
@@ -145,93 +146,29 @@ __global__ __launch_bounds__(kSplitThreads) void split_link_kernel(const SplitAr
     }
 }
 
-// the sum of v over the workgroup, in every thread
-__device__ __forceinline__ uint32_t split_block_sum(uint32_t v, uint32_t* part) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t s = 0u;
-#pragma unroll
-    for (int k = 0; k < kSplitThreads / 64; ++k) s += part[k];
-    return s;
-}
-
-// the sum of v over the threads of the workgroup before this one
-__device__ __forceinline__ uint32_t split_block_exclusive(uint32_t v, uint32_t* part) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t p = (uint32_t)__shfl_up((int)inc, d);
-        if (lane >= (uint32_t)d) inc += p;
-    }
-    if (lane == 63u) part[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0u;
-    for (uint32_t k = 0; k < wave; ++k) before += part[k];
-    return before + inc - v;
-}
-
-// ---- flatten ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kSplitThreads) void split_flatten_kernel(const SplitArgs a) {
-    __shared__ uint32_t part[kSplitThreads / 64];
-    const uint32_t i = blockIdx.x * kSplitThreads + threadIdx.x;
-    uint32_t is_seed = 0u;
-    if (i < a.voxels) {
-        const uint32_t p = uf_load(a.uf + i);
-        if (p != kSplitOutside) {                           // a summit
-            const uint32_t r = uf_find(a.uf, p);
-            if (r != p) (void)uf_min(a.uf + i, r);
-            is_seed = r == i;
-        }
-    }
-    const uint32_t total = split_block_sum(is_seed, part);
-    if (threadIdx.x == 0u) a.cnt[blockIdx.x] = total;
-}
-
 // ---- scan ---------------------------------------------------------------------------------------------------------------
-// out[b] = the sum of block b's kSplitScanBlock entries of in[0 .. n)
-__global__ __launch_bounds__(kSplitThreads) void split_scan_sums_kernel(const uint32_t* in, uint32_t n, uint32_t* out) {
-    __shared__ uint32_t part[kSplitThreads / 64];
-    const uint32_t i = blockIdx.x * kSplitScanBlock + threadIdx.x;
-    const uint32_t total = split_block_sum(i < n ? in[i] : 0u, part);
-    if (threadIdx.x == 0u) out[blockIdx.x] = total;
-}
-
-// what the top level writes into the header beside N
+// What the top level of the scan does with N, the number of seeds: the header's words [0], [2], [3] and [10..12]; the up
+// pass counted [1] and [4], and the launcher zeroed the rest.
 struct SplitHeader {
     unsigned long long* header;
     unsigned long long ids_written, rcap;
     uint32_t n[3];
-};
-
-// data[0 .. n): every block's entries become their exclusive prefix inside the block plus base[block] (null: 0).  The top
-// level (`top`: one block holds it all) writes the header's words [0], [2], [3] and [10..12]; the up pass counted [1] and
-// [4], and the launcher zeroed the rest.
-__global__ __launch_bounds__(kSplitThreads) void split_scan_apply_kernel(uint32_t* data, uint32_t n, const uint32_t* base, int top,
-                                                                         const SplitHeader h) {
-    __shared__ uint32_t part[kSplitThreads / 64];
-    const uint32_t i = blockIdx.x * kSplitScanBlock + threadIdx.x;
-    const uint32_t v = i < n ? data[i] : 0u;
-    const uint32_t before = split_block_exclusive(v, part) + (base ? base[blockIdx.x] : 0u);
-    if (i < n) data[i] = before;
-    if (top && threadIdx.x == kSplitThreads - 1) {
-        const unsigned long long N = (unsigned long long)before + v;
-        h.header[0] = N;
-        h.header[2] = h.ids_written;
-        h.header[3] = N <= h.rcap ? N : 0ull;
+    __device__ void operator()(uint32_t total) const {
+        const unsigned long long N = total;
+        header[0] = N;
+        header[2] = ids_written;
+        header[3] = N <= rcap ? N : 0ull;
 #pragma unroll
-        for (int ax = 0; ax < 3; ++ax) h.header[10 + ax] = h.n[ax];
+        for (int ax = 0; ax < 3; ++ax) header[10 + ax] = n[ax];
     }
-}
+};
 
 // ---- rank ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kSplitThreads) void split_rank_kernel(const SplitArgs a) {
-    __shared__ uint32_t part[kSplitThreads / 64];
+    __shared__ uint32_t part[kBoxScanWaves];
     const uint32_t i = blockIdx.x * kSplitThreads + threadIdx.x;
     const uint32_t is_seed = i < a.voxels && a.uf[i] == i;
-    const uint32_t rank = split_block_exclusive(is_seed, part) + a.cnt[blockIdx.x];
+    const uint32_t rank = box_block_exclusive(is_seed, part) + a.cnt[blockIdx.x];
     if (!is_seed) return;
     a.aux[i] = rank;
     if (!a.records || a.header[0] > a.rcap) return;
@@ -259,50 +196,20 @@ __global__ __launch_bounds__(kSplitThreads) void split_emit_kernel(const SplitAr
     if (!a.records || a.header[0] > a.rcap) return;         // the same for every thread of the launch
     const uint32_t rx = i % a.n[0], row = i / a.n[0], ry = row % a.n[1], rz = row / a.n[1];
     const uint32_t c[3] = {rx, ry, rz};
-    unsigned long long todo = __ballot(id != 0u);
-    while (todo) {                                          // wave-uniform: a round per region that has lanes left
-        const int leader = __ffsll((long long)todo) - 1;
-        const uint32_t lid = (uint32_t)__shfl((int)id, leader);
-        const bool mine = id == lid;
-        const unsigned long long peers = __ballot(mine);
-        const unsigned long long tops = __ballot(mine && key != 0ull);
-        todo &= ~peers;
-        uint32_t cmin[3], cmax[3];
-        unsigned long long sum[3];
-        unsigned long long best = mine ? key : 0ull;
+    box_wave_groups<true>(id, c, key, [&](uint32_t lid, const BoxShare& s) {
+        svr_split_record& r = a.records[lid - 1u];
+        atomicAdd(reinterpret_cast<unsigned long long*>(&r.voxels), (unsigned long long)s.count);
 #pragma unroll
         for (int ax = 0; ax < 3; ++ax) {
-            cmin[ax] = mine ? c[ax] : 0xFFFFFFFFu; cmax[ax] = mine ? c[ax] : 0u;
-            sum[ax] = mine ? (unsigned long long)c[ax] : 0ull;
+            atomicAdd(reinterpret_cast<unsigned long long*>(&r.sum[ax]), s.sum[ax]);
+            atomicMin(&r.lo[ax], (int32_t)s.cmin[ax]);
+            atomicMax(&r.hi[ax], (int32_t)s.cmax[ax]);
         }
-        if (__popcll(peers) > 1) {
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-#pragma unroll
-                for (int ax = 0; ax < 3; ++ax) {
-                    cmin[ax] = min(cmin[ax], (uint32_t)__shfl_xor((int)cmin[ax], d));
-                    cmax[ax] = max(cmax[ax], (uint32_t)__shfl_xor((int)cmax[ax], d));
-                    sum[ax] += __shfl_xor(sum[ax], d);
-                }
-                const unsigned long long other = __shfl_xor(best, d);
-                best = other > best ? other : best;
-            }
+        if (s.tops) {
+            atomicAdd(&r.basins, (uint32_t)__popcll(s.tops));
+            atomicMax(reinterpret_cast<unsigned long long*>(&r.top[0]), s.best);
         }
-        if ((int)__lane_id() == leader) {
-            svr_split_record& r = a.records[lid - 1u];
-            atomicAdd(reinterpret_cast<unsigned long long*>(&r.voxels), (unsigned long long)__popcll(peers));
-#pragma unroll
-            for (int ax = 0; ax < 3; ++ax) {
-                atomicAdd(reinterpret_cast<unsigned long long*>(&r.sum[ax]), sum[ax]);
-                atomicMin(&r.lo[ax], (int32_t)cmin[ax]);
-                atomicMax(&r.hi[ax], (int32_t)cmax[ax]);
-            }
-            if (tops) {
-                atomicAdd(&r.basins, (uint32_t)__popcll(tops));
-                atomicMax(reinterpret_cast<unsigned long long*>(&r.top[0]), best);
-            }
-        }
-    }
+    });
 }
 
 // ---- finish -------------------------------------------------------------------------------------------------------------
@@ -337,7 +244,7 @@ hipError_t svr_launch_split(const SplitPlan& p, const svr_split_params& sp, void
     a.up = reinterpret_cast<uint32_t*>(base + p.up_off);
     a.uf = reinterpret_cast<uint32_t*>(base + p.uf_off);
     a.aux = reinterpret_cast<uint32_t*>(base + p.aux_off);
-    a.cnt = reinterpret_cast<uint32_t*>(base + p.cnt_off[0]);
+    a.cnt = reinterpret_cast<uint32_t*>(base + p.scan.off[0]);
     a.header = h.header;
     a.ids = ids_fit ? out.ids : nullptr;
     a.records = out.record_capacity > 0 ? out.records : nullptr;
@@ -345,7 +252,7 @@ hipError_t svr_launch_split(const SplitPlan& p, const svr_split_params& sp, void
 
     hipError_t e = hipMemsetAsync(h.header, 0, 16 * sizeof(uint64_t), stream);
     if (e != hipSuccess) return e;
-    const dim3 grid(p.count[0]), block(kSplitThreads);
+    const dim3 grid(p.scan.count[0]), block(kSplitThreads);
     const bool conn26 = sp.connectivity == 26;
     if (conn26) hipLaunchKernelGGL(split_up_kernel<true>, grid, block, 0, stream, a);
     else        hipLaunchKernelGGL(split_up_kernel<false>, grid, block, 0, stream, a);
@@ -355,22 +262,10 @@ hipError_t svr_launch_split(const SplitPlan& p, const svr_split_params& sp, void
     if (conn26) hipLaunchKernelGGL(split_link_kernel<true>, grid, block, 0, stream, a);
     else        hipLaunchKernelGGL(split_link_kernel<false>, grid, block, 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(split_flatten_kernel, grid, block, 0, stream, a);
+    hipLaunchKernelGGL(uf_flatten_kernel, grid, block, 0, stream, a.uf, a.voxels, a.cnt);
     if ((e = hipGetLastError()) != hipSuccess) return e;
 
-    uint32_t* lev[kSplitMaxLevels];
-    for (int k = 0; k < p.levels; ++k) lev[k] = reinterpret_cast<uint32_t*>(base + p.cnt_off[k]);
-    for (int k = 0; k + 1 < p.levels; ++k) {
-        hipLaunchKernelGGL(split_scan_sums_kernel, dim3(p.count[k + 1]), block, 0, stream, lev[k], p.count[k], lev[k + 1]);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    const int top = p.levels - 1;
-    hipLaunchKernelGGL(split_scan_apply_kernel, dim3(1), block, 0, stream, lev[top], p.count[top], nullptr, 1, h);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    for (int k = top - 1; k >= 0; --k) {
-        hipLaunchKernelGGL(split_scan_apply_kernel, dim3(p.count[k + 1]), block, 0, stream, lev[k], p.count[k], lev[k + 1], 0, h);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+    if ((e = box_scan_run<uint32_t>(&p.scan, scratch, h, stream)) != hipSuccess) return e;
     // the count-only call ends here; a call whose records cannot fit finds that out on the device
     if (!a.ids && !a.records) return hipSuccess;
     hipLaunchKernelGGL(split_rank_kernel, grid, block, 0, stream, a);

@@ -9,28 +9,25 @@
 //           its own root, every other voxel holds kSplitOutside for good.  After the flatten pass a summit holds the
 //           seed of its region.
 //   aux     one u32 per voxel, written at seeds only: the rank of the region (its number minus one).
-//   scan    level 0 holds one u32 per block of kSplitScanBlock voxels, the seeds among them; level k + 1 holds the sums
-//           of level k's blocks of kSplitScanBlock entries, until one block holds a whole level.
+//   scan    level 0 holds one u32 per block of kBoxScanBlock voxels, the seeds among them; the levels above it are
+//           those of box_scan.h.
 // 12 bytes per voxel, and 4 bytes per 256 voxels for the scan.
 #pragma once
 
 #include <stdint.h>
 
+#include "box_scan.h"
 #include "box_units.h"
 
 constexpr uint32_t kSplitOutside = 0xFFFFFFFFu;    // == kUfOutside (components_uf.h)
-constexpr uint32_t kSplitScanBlock = 256;          // entries one workgroup scans, and voxels per workgroup of the voxel passes
-constexpr int      kSplitMaxLevels = 3;            // 2^30 voxels -> 2^22 counts -> 2^14 -> 2^6
 constexpr uint64_t kSplitMaxVoxels = 1ull << 30;   // SVR_SPLIT_MAX_VOXELS
 constexpr uint32_t kSplitMaxMerge = 1u << 29;      // SVR_SPLIT_MAX_MERGE
 
 struct SplitPlan {
     uint32_t n[3];                     // voxels per axis (x, y, z)
     uint32_t voxels;                   // n[0] * n[1] * n[2] <= 2^30: every index, and kSplitOutside beside them, fits u32
-    int32_t  levels;                   // arrays of the scan, 1 .. kSplitMaxLevels
-    uint32_t count[kSplitMaxLevels];   // entries of level k; count[0] = the workgroups of a voxel pass; count[levels - 1] <= kSplitScanBlock
     uint64_t up_off, uf_off, aux_off;  // byte offsets into the scratch
-    uint64_t cnt_off[kSplitMaxLevels];
+    BoxScanPlan scan;                  // count[0] = the workgroups of a voxel pass, kBoxScanBlock voxels each: <= 2^22, three levels at the most
     uint64_t bytes;                    // of scratch in all
 };
 
@@ -44,15 +41,9 @@ inline bool split_plan(const int32_t n[3], SplitPlan& p) {
         p.n[a] = (uint32_t)n[a];
     }
     p.voxels = (uint32_t)voxels;
-    p.levels = box_scan_levels((p.voxels + kSplitScanBlock - 1u) / kSplitScanBlock, kSplitScanBlock, kSplitMaxLevels, p.count);
     p.up_off = 0;
     p.uf_off = voxels * 4u;
     p.aux_off = voxels * 8u;
-    uint64_t at = voxels * 12u;
-    for (int k = 0; k < kSplitMaxLevels; ++k) {
-        p.cnt_off[k] = at;
-        at += (uint64_t)p.count[k] * 4u;
-    }
-    p.bytes = at;
+    p.bytes = box_scan_plan((p.voxels + kBoxScanBlock - 1u) / kBoxScanBlock, 4u, voxels * 12u, p.scan);
     return true;
 }

@@ -15,6 +15,7 @@ from scipy import ndimage
 
 from components_twin import RECORD, components_twin, label_components, neighbour_offsets
 from odd_ring_scenes import plan_cases
+from parent_plans import held_to_parent
 from sub_volume_renderer_amd import ComponentLabels, SubVolume, SubVolumeMaterial, _native as N
 from sub_volume_renderer_amd.components import components_arguments
 
@@ -140,7 +141,7 @@ def test_components_twin_header_records_and_boxes():
 # ---- the union-find and the plan on the host -----------------------------------------------------------------------------
 # "label FILE nx ny nz head connectivity keyed threads OUT": FILE holds nx ny nz bytes of inside(), then as many u32 keys;
 # OUT receives parent[] after the flatten pass, then the numbers (0 outside), u32 each.
-# "plan" reads "nx ny nz head" lines -> "voxels head upr units levels count[3] parent_off aux_off cnt_off[3] bytes", "empty" or "too_many".
+# "plan" reads "nx ny nz head" lines -> "voxels head upr units levels count[4] parent_off aux_off off[4] bytes", "empty" or "too_many".
 DRIVER = r"""
 #include <inttypes.h>
 #include <stdio.h>
@@ -156,9 +157,9 @@ static void merge(uint32_t* parent, const uint32_t* aux, const CompPlan& p, int 
     std::vector<std::thread> pool;
     for (int t = 0; t < threads; ++t)
         pool.emplace_back([=, &p]() {
-            // a "workgroup" of kCompScanBlock voxels at a time, dealt round robin, so that neighbours are joined by different threads
-            for (uint32_t b = (uint32_t)t; b < p.count[0]; b += (uint32_t)threads)
-                for (uint32_t i = b * kCompScanBlock; i < p.voxels && i < (b + 1) * kCompScanBlock; ++i)
+            // a "workgroup" of kBoxScanBlock voxels at a time, dealt round robin, so that neighbours are joined by different threads
+            for (uint32_t b = (uint32_t)t; b < p.scan.count[0]; b += (uint32_t)threads)
+                for (uint32_t i = b * kBoxScanBlock; i < p.voxels && i < (b + 1) * kBoxScanBlock; ++i)
                     uf_merge_voxel<C26, KEYED>(parent, aux, i, p.n, p.head);
         });
     for (auto& th : pool) th.join();
@@ -195,28 +196,29 @@ static int label(int argc, char** argv) {
     if (conn == 26) { if (keyed) merge<true, true>(parent.data(), aux.data(), p, threads); else merge<true, false>(parent.data(), aux.data(), p, threads); }
     else            { if (keyed) merge<false, true>(parent.data(), aux.data(), p, threads); else merge<false, false>(parent.data(), aux.data(), p, threads); }
     // flatten, and the roots of every block of voxels: level 0 of the scan
-    std::vector<std::vector<uint32_t>> lev(p.levels);
-    for (int k = 0; k < p.levels; ++k) lev[k].assign(p.count[k], 0u);
+    const BoxScanPlan& s = p.scan;
+    std::vector<std::vector<uint32_t>> lev(s.levels);
+    for (int k = 0; k < s.levels; ++k) lev[k].assign(s.count[k], 0u);
     for (uint32_t i = 0; i < p.voxels; ++i) {
         if (parent[i] == kUfOutside) continue;
         const uint32_t r = uf_find(parent.data(), i);
         (void)uf_min(parent.data() + i, r);
-        if (r == i) ++lev[0][i / kCompScanBlock];
+        if (r == i) ++lev[0][i / kBoxScanBlock];
     }
-    for (int k = 0; k + 1 < p.levels; ++k)
-        for (uint32_t i = 0; i < p.count[k]; ++i) lev[k + 1][i / kCompScanBlock] += lev[k][i];
-    for (int k = p.levels - 1; k >= 0; --k) {                // exclusive prefixes inside a block, plus the block's from above
+    for (int k = 0; k + 1 < s.levels; ++k)
+        for (uint32_t i = 0; i < s.count[k]; ++i) lev[k + 1][i / kBoxScanBlock] += lev[k][i];
+    for (int k = s.levels - 1; k >= 0; --k) {                // exclusive prefixes inside a block, plus the block's from above
         uint32_t run = 0;
-        for (uint32_t i = 0; i < p.count[k]; ++i) {
-            if (i % kCompScanBlock == 0) run = k + 1 < p.levels ? lev[k + 1][i / kCompScanBlock] : 0u;
+        for (uint32_t i = 0; i < s.count[k]; ++i) {
+            if (i % kBoxScanBlock == 0) run = k + 1 < s.levels ? lev[k + 1][i / kBoxScanBlock] : 0u;
             const uint32_t v = lev[k][i];
             lev[k][i] = run; run += v;
         }
     }
     std::vector<uint32_t> ids(p.voxels, 0u);
-    for (uint32_t b = 0; b < p.count[0]; ++b) {
+    for (uint32_t b = 0; b < s.count[0]; ++b) {
         uint32_t rank = lev[0][b];
-        for (uint32_t i = b * kCompScanBlock; i < p.voxels && i < (b + 1) * kCompScanBlock; ++i)
+        for (uint32_t i = b * kBoxScanBlock; i < p.voxels && i < (b + 1) * kBoxScanBlock; ++i)
             if (parent[i] == i) aux[i] = rank++;
     }
     for (uint32_t i = 0; i < p.voxels; ++i) if (parent[i] != kUfOutside) ids[i] = aux[parent[i]] + 1u;
@@ -228,15 +230,15 @@ static int label(int argc, char** argv) {
 
 int main(int argc, char** argv) {
     if (argc > 1 && !strcmp(argv[1], "label")) return label(argc, argv);
-    printf("%u %d %" PRIu64 " %u\n", kCompScanBlock, kCompMaxLevels, kCompMaxVoxels, kUfOutside);
+    printf("%u %d %" PRIu64 " %u\n", kBoxScanBlock, kBoxScanMaxLevels, kCompMaxVoxels, kUfOutside);
     for (;;) {
         int64_t n[3]; uint32_t head;
         if (scanf("%" SCNd64 "%" SCNd64 "%" SCNd64 "%" SCNu32, &n[0], &n[1], &n[2], &head) != 4) return 0;
         CompPlan p; bool too_many = false;
         if (!comp_plan(n, head, p, &too_many)) { printf(too_many ? "too_many\n" : "empty\n"); continue; }
-        printf("%u %u %u %u %d %u %u %u %" PRIu64 " %" PRIu64, p.voxels, p.head, p.upr, p.units, (int)p.levels, p.count[0], p.count[1], p.count[2],
-               p.parent_off, p.aux_off);
-        for (int k = 0; k < kCompMaxLevels; ++k) printf(" %" PRIu64, p.cnt_off[k]);
+        printf("%u %u %u %u %d %u %u %u %u %" PRIu64 " %" PRIu64, p.voxels, p.head, p.upr, p.units, (int)p.scan.levels, p.scan.count[0],
+               p.scan.count[1], p.scan.count[2], p.scan.count[3], p.parent_off, p.aux_off);
+        for (int k = 0; k < kBoxScanMaxLevels; ++k) printf(" %" PRIu64, p.scan.off[k]);
         printf(" %" PRIu64 "\n", p.bytes);
     }
 }
@@ -296,15 +298,15 @@ def plans(exe, cases):
             res.append(line)
             continue
         w = [int(v) for v in line.split()]
-        res.append(dict(voxels=w[0], head=w[1], upr=w[2], units=w[3], levels=w[4], count=w[5:8], parent_off=w[8], aux_off=w[9], cnt_off=w[10:13],
-                        bytes=w[13]))
+        res.append(dict(voxels=w[0], head=w[1], upr=w[2], units=w[3], levels=w[4], count=w[5:9], parent_off=w[9], aux_off=w[10], cnt_off=w[11:15],
+                        bytes=w[15]))
     assert len(res) == len(cases)
     return [int(v) for v in lines[0].split()], res
 
 
 def test_components_plan(driver):
     (block, max_levels, max_voxels, outside), _ = plans(driver, [])
-    assert (block, max_levels, max_voxels, outside) == (256, 3, 1 << 30, 0xFFFFFFFF) and max_voxels == N.COMPONENTS_MAX_VOXELS
+    assert (block, max_levels, max_voxels, outside) == (256, 4, 1 << 30, 0xFFFFFFFF) and max_voxels == N.COMPONENTS_MAX_VOXELS
     assert outside >= max_voxels                            # the marker is no voxel's index, and every index fits u32
     cases = [(nx, 3, 2, h) for nx in (1, 3, 4, 5, 65) for h in (0, 1, 3)]
     cases += [(block, 1, 1, 0), (block + 1, 1, 1, 0), (block, block, 1, 2), (block, block, 1 + 1, 0), (16, block * block // 16, 1, 0),
@@ -322,7 +324,7 @@ def test_components_plan(driver):
             count.append(-(-count[-1] // block))
         assert p["voxels"] == voxels and p["head"] == head and p["upr"] == -(-(nx + head) // 4) and p["units"] == p["upr"] * ny * nz, (c, p)
         assert p["units"] <= voxels and 4 * p["upr"] >= nx + head > 4 * (p["upr"] - 1)
-        assert p["levels"] == len(count) <= max_levels and p["count"][:len(count)] == count and not any(p["count"][len(count):]), (c, p)
+        assert p["levels"] == len(count) <= 3 and p["count"][:len(count)] == count and not any(p["count"][len(count):]), (c, p)
         assert p["count"][p["levels"] - 1] <= block
         # the scratch: parent, aux, then the levels, back to back, 4-byte entries
         assert p["parent_off"] == 0 and p["aux_off"] == 4 * voxels
@@ -331,11 +333,14 @@ def test_components_plan(driver):
             assert p["cnt_off"][k] == at
             at += 4 * p["count"][k]
         assert p["bytes"] == at
+        # the fourth level, which 2^30 voxels never need, takes no bytes; and nothing moved
+        assert p["count"][3] == 0 and p["cnt_off"][3] == p["bytes"]
+        held_to_parent("components", c, [p["parent_off"], p["aux_off"], *p["cnt_off"][:3], p["bytes"]])
     by = {tuple(c): p for c, p in zip(cases, res)}
-    assert by[(block, 1, 1, 0)]["levels"] == 1 and by[(block + 1, 1, 1, 0)]["count"] == [2, 0, 0]
-    assert by[(block, block, 1, 2)]["levels"] == 1 and by[(block, block, 2, 0)]["count"] == [2 * block, 2, 0]
+    assert by[(block, 1, 1, 0)]["levels"] == 1 and by[(block + 1, 1, 1, 0)]["count"] == [2, 0, 0, 0]
+    assert by[(block, block, 1, 2)]["levels"] == 1 and by[(block, block, 2, 0)]["count"] == [2 * block, 2, 0, 0]
     assert by[(16, block * block // 16, 1, 0)]["levels"] == 1 and by[(16, block * block // 16 + 1, 1, 0)]["levels"] == 2
-    assert by[(1 << 10, 1 << 10, 1 << 10, 0)]["count"] == [1 << 22, 1 << 14, 1 << 6]       # the most voxels, and the most levels
+    assert by[(1 << 10, 1 << 10, 1 << 10, 0)]["count"] == [1 << 22, 1 << 14, 1 << 6, 0]    # the most voxels, and the most levels
 
 
 def test_components_plan_refusals(driver):
@@ -343,6 +348,7 @@ def test_components_plan_refusals(driver):
                             (1 << 30, 1, 1, 3)])
     assert res[0] == "empty" and res[1] == "empty" and res[2] == "too_many" and res[3] == "too_many" and res[4] == "too_many"
     assert res[5]["voxels"] == 1 << 30 and res[5]["upr"] == (1 << 28) + 1 and res[5]["bytes"] < 1 << 34
+    held_to_parent("components", (1 << 30, 1, 1, 3), [res[5]["parent_off"], res[5]["aux_off"], *res[5]["cnt_off"][:3], res[5]["bytes"]])
 
 
 # ---- the surface ---------------------------------------------------------------------------------------------------------

@@ -1,9 +1,11 @@
 """GPU: svr_split (include/svr.h) == the numpy restatement tests/split_twin.py: the header, the dense numbers and every
 field of every record are equal exactly, in every case.  Through the C ABI on height fields made here (random heights
 with many ties, the squared distances of two overlapping balls, an all-FAR plateau) in boxes from one voxel to one whose
-scan has a second level; capacities; reproducibility; two streams; every refusal.  Through SubVolume.split on a two-LOD
-scene whose rings are 21 voxels wide along x and whose windows wrap them."""
+scan has a second level, and one of isolated voxels whose scan has a third; capacities; reproducibility; two streams;
+every refusal.  Through SubVolume.split on a two-LOD scene whose rings are 21 voxels wide along x and whose windows wrap them."""
 import ctypes as C
+import os
+import re
 
 import numpy as np
 import pytest
@@ -18,6 +20,8 @@ FILL = 0x5A5A5A5A
 MERGES = (0, 1, 9, 1 << 29)
 BOXES = [(1, 1, 1), (5, 1, 1), (1, 1, 7), (63, 5, 3), (65, 9, 4), (67, 33, 31)]        # (n_x, n_y, n_z)
 LEVEL = 128.0
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SCAN_BLOCK = int(re.search(r"kBoxScanBlock = (\d+);", open(os.path.join(ROOT, "sub_volume_renderer_amd", "csrc", "box_scan.h")).read()).group(1))
 
 _SCENE = {}
 
@@ -154,6 +158,38 @@ def test_through_the_c_abi(box):
                     assert twin["header"][1] > 0 and twin["header"][0] >= 1
     if box == (67, 33, 31):
         assert -(-67 * 33 * 31 // 256) > 256 and max(seen) > 256         # a scan of two levels, and regions beyond its first block
+
+
+def test_three_levels_of_the_scan():
+    """More than SCAN_BLOCK^2 blocks of voxels: the block sums of the u32 scan (csrc/box_scan.h), which svr_components runs
+    in the same instantiation, have block sums of their own, level 1 fills more than one block and the top holds two
+    entries.  Positive heights on a thinned checkerboard: no two positive voxels are 6-neighbours, so every one is its own
+    summit and its own region, and its number is the count of positive voxels up to and including it.  The thinning makes
+    the counts per block differ, so that a wrong prefix at any level shows."""
+    nx, ny, nz = 260, 256, 256
+    voxels = nx * ny * nz
+    count = [-(-voxels // SCAN_BLOCK)]
+    while count[-1] > SCAN_BLOCK:
+        count.append(-(-count[-1] // SCAN_BLOCK))
+    assert voxels == 17039360 and count == [66560, 260, 2]
+    rng = np.random.default_rng(29)
+    z, y, x = np.ogrid[:nz, :ny, :nx]
+    keep = ((x + y + z) % 2 == 0) & (rng.random((nz, ny, nx)) < 2.0 / 3.0)
+    height = np.where(keep, rng.integers(1, 1000, (nz, ny, nx)), 0).astype(np.int32)
+    header, ids, _, h = c_split(height, 6, 0, ids_cap=voxels, sync=False)
+    torch.cuda.synchronize()
+    positive = (h.reshape(-1) > 0).to(torch.int32)
+    want = torch.cumsum(positive, 0, dtype=torch.int32) * positive
+    n = int(positive.sum())
+    assert n == int(keep.sum()) and voxels // 4 < n < voxels // 2
+    head = [int(v) for v in header.cpu().numpy().view(np.uint64)]
+    assert head[0] == n and head[1] == n and head[2] == voxels, head
+    assert torch.equal(ids, want)
+    del header, ids, h, want, positive
+    torch.cuda.empty_cache()
+    head, _, _ = c_split(height, 6, 0)
+    assert head[0] == n, head
+    torch.cuda.empty_cache()
 
 
 def test_capacities():

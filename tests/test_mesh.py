@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from mesh_twin import EDGES, area_volume, mesh_twin, surface_nets
+from parent_plans import held_to_parent
 from sub_volume_renderer_amd import SubVolume, SubVolumeMaterial, SurfaceMesh, _native as N
 from sub_volume_renderer_amd.mesh import mesh_arguments
 
@@ -245,16 +246,16 @@ DRIVER = r"""
 #include <stdio.h>
 #include "mesh_plan.h"
 int main() {
-    printf("%u %u %d %" PRIu64 "\n", kMeshCellsPerWord, kMeshScanBlock, kMeshMaxLevels, kMeshMaxCells);
+    printf("%u %u %d %" PRIu64 "\n", kMeshCellsPerWord, kBoxScanBlock, kBoxScanMaxLevels, kMeshMaxCells);
     for (;;) {
         int64_t n[3]; uint32_t head;
         if (scanf("%" SCNd64 "%" SCNd64 "%" SCNd64 "%" SCNu32, &n[0], &n[1], &n[2], &head) != 4) return 0;
         MeshPlan p; bool too_many = false;
         if (!mesh_plan(n, head, p, &too_many)) { printf(too_many ? "too_many\n" : "empty\n"); continue; }
-        printf("%u %u %u %u %u %u %u %u %u %d", p.cells[0], p.cells[1], p.cells[2], p.head, p.bpr, p.bit_words, p.wpr, p.rows, p.words, (int)p.levels);
-        for (int k = 0; k < kMeshMaxLevels; ++k) printf(" %u", p.count[k]);
+        printf("%u %u %u %u %u %u %u %u %u %d", p.cells[0], p.cells[1], p.cells[2], p.head, p.bpr, p.bit_words, p.wpr, p.rows, p.words, (int)p.scan.levels);
+        for (int k = 0; k < kBoxScanMaxLevels; ++k) printf(" %u", p.scan.count[k]);
         printf(" %" PRIu64, p.nib_off);
-        for (int k = 0; k < kMeshMaxLevels; ++k) printf(" %" PRIu64, p.cnt_off[k]);
+        for (int k = 0; k < kBoxScanMaxLevels; ++k) printf(" %" PRIu64, p.scan.off[k]);
         printf(" %" PRIu64 " %" PRIu64 "\n", p.bit_off, p.bytes);
     }
 }
@@ -322,6 +323,7 @@ def test_mesh_plan(plan_driver):
             assert p["cnt_off"][k] == at
             at += 8 * p["count"][k]
         assert p["bit_off"] == at and p["bytes"] == at + 4 * p["bit_words"]
+        held_to_parent("mesh", c, [p["nib_off"], *p["cnt_off"], p["bit_off"], p["bytes"]])
         cells_n = cells[0] * cells[1] * cells[2]
         assert p["bytes"] <= 16 * words + 8 * sum(p["count"][1:]) + 4 * p["bit_words"]
         assert wpr * per_word >= cells[0] > (wpr - 1) * per_word and words <= cells_n
@@ -343,6 +345,7 @@ def test_mesh_plan_refusals(plan_driver):
     assert res[4] == "too_many" and res[6] == "too_many"
     # exactly 2^28 cells in rows of one word: the most words there can be, and the most levels
     assert res[5]["cells"] == [2, 1 << 13, 1 << 14] and res[5]["levels"] == 4 and res[5]["count"] == [1 << 27, 1 << 19, 1 << 11, 1 << 3]
+    held_to_parent("mesh", (1, (1 << 13) - 1, (1 << 14) - 1, 0), [res[5]["nib_off"], *res[5]["cnt_off"], res[5]["bit_off"], res[5]["bytes"]])
 
 
 # ---- the surface ---------------------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ from scipy import ndimage
 
 from distance_twin import FAR, squared_edt
 from split_twin import MAX_MERGE, RECORD, count_only, links, split_brute, split_twin, summits_of
+from parent_plans import held_to_parent
 from sub_volume_renderer_amd import SubVolume, SubVolumeMaterial, _native as N
 from sub_volume_renderer_amd.split import SplitLabels, split_arguments
 
@@ -152,15 +153,16 @@ static int do_links() {
 
 // plans: lines of "nx ny nz" -> the plan, or "refused"
 static int do_plans() {
-    printf("%u %u %d %" PRIu64 " %u\n", kSplitOutside, kSplitScanBlock, kSplitMaxLevels, kSplitMaxVoxels, kSplitMaxMerge);
+    printf("%u %u %d %" PRIu64 " %u\n", kSplitOutside, kBoxScanBlock, kBoxScanMaxLevels, kSplitMaxVoxels, kSplitMaxMerge);
     long long n[3];
     while (scanf("%lld %lld %lld", &n[0], &n[1], &n[2]) == 3) {
         const int32_t m[3] = {(int32_t)n[0], (int32_t)n[1], (int32_t)n[2]};
         SplitPlan p;
         if (!split_plan(m, p)) { printf("refused\n"); continue; }
-        printf("%u %d %u %u %u %" PRIu64 " %" PRIu64 " %" PRIu64, p.voxels, (int)p.levels, p.count[0], p.count[1], p.count[2], p.up_off, p.uf_off, p.aux_off);
-        for (int k = 0; k < kSplitMaxLevels; ++k) printf(" %" PRIu64, p.cnt_off[k]);
-        printf(" %" PRIu64 "\n", p.bytes);
+        printf("%u %d %u %u %u %" PRIu64 " %" PRIu64 " %" PRIu64, p.voxels, (int)p.scan.levels, p.scan.count[0], p.scan.count[1], p.scan.count[2],
+               p.up_off, p.uf_off, p.aux_off);
+        for (int k = 0; k < 3; ++k) printf(" %" PRIu64, p.scan.off[k]);
+        printf(" %" PRIu64 " %u %" PRIu64 "\n", p.bytes, p.scan.count[3], p.scan.off[3]);
     }
     return 0;
 }
@@ -282,7 +284,7 @@ def test_split_plan(driver):
              (0, 4, 4), (4, -1, 4), (1024, 1024, 1025), (2147483647, 2147483647, 2147483647), (1 << 30, 1, 1), ((1 << 30) + 1, 1, 1)]
     out = subprocess.run([driver, "plans"], input="".join(f"{a} {b} {c}\n" for a, b, c in cases), capture_output=True, text=True, check=True)
     lines = out.stdout.strip().split("\n")
-    assert lines[0].split() == [str(0xFFFFFFFF), "256", "3", str(1 << 30), str(1 << 29)]
+    assert lines[0].split() == [str(0xFFFFFFFF), "256", "4", str(1 << 30), str(1 << 29)]
     for n, line in zip(cases, lines[1:]):
         voxels = n[0] * n[1] * n[2]
         if min(n) <= 0 or voxels > 1 << 30:
@@ -298,7 +300,9 @@ def test_split_plan(driver):
         for k in range(3):
             offs.append(at)
             at += 4 * count[k]
-        assert v == [voxels, levels, *count, 0, 4 * voxels, 8 * voxels, *offs, at], n
+        # the fourth level, which 2^30 voxels never need, takes no bytes; and nothing moved
+        assert v == [voxels, levels, *count, 0, 4 * voxels, 8 * voxels, *offs, at, 0, at], n
+        held_to_parent("split", n, v[5:12])
         # 12 bytes per voxel plus the scan levels, each a 256th of the one below, rounded up
         assert at <= 12 * voxels + 4 * (voxels // 256 + voxels // 65536 + voxels // (1 << 24) + 3)
     assert len(lines) == 1 + len(cases)

@@ -2,18 +2,20 @@
 """Compare the gfx950 kernels of two builds of the same translation unit, kernel by kernel: the code-object metadata
 (registers, spills, scratch, LDS, kernel-argument size) and the disassembly.  Only reads object files.
 
-usage: kernel_diff.py [-v] [--rename REGEX REPL] BEFORE.o AFTER.o [more pairs ...]
+usage: kernel_diff.py [-v] [--rename REGEX REPL]... BEFORE.o AFTER.o [more pairs ...]
 
 --rename REGEX REPL: re.sub applied to the mangled kernel names of AFTER before pairing, for kernels that gained a
-template parameter (e.g. a trailing `false`: --rename 'Lb0E(EEvNS_\d+\w+ParamsE)$' '\1'); kernels of AFTER that then have
-no partner in BEFORE are counted as new, not as a difference.
+template parameter (e.g. a trailing `false`: --rename 'Lb0E(EEvNS_\d+\w+ParamsE)$' '\1') or moved to a shared name; may be
+given several times, each applied in turn; kernels of AFTER that then have no partner in BEFORE are counted as new, not as
+a difference.
 
 Per kernel, one of
   identical   the instruction text is the same (addresses and encodings stripped)
   renamed     the same mnemonics in the same order with operands of the same kinds; what differs is register numbers
               and / or the literal offsets of scalar loads (s_load_*: kernel arguments that moved inside their struct).
               Renaming is not checked for consistency: read the printed diff of a kernel you care about.
-  changed     anything else; with -v its unified diff is printed
+  changed     anything else: its registers, LDS and instruction count in both builds are printed, with -v its unified
+              diff too
 and a line for every metadata note that differs."""
 import difflib
 import os
@@ -83,10 +85,10 @@ def demangle(names):
 def main():
     args = [a for a in sys.argv[1:] if a != "-v"]
     verbose = "-v" in sys.argv[1:]
-    rename = None
-    if "--rename" in args:
+    rename = []
+    while "--rename" in args:
         k = args.index("--rename")
-        rename = (re.compile(args[k + 1]), args[k + 2])
+        rename.append((re.compile(args[k + 1]), args[k + 2]))
         del args[k:k + 3]
     if not args or len(args) % 2:
         sys.exit(__doc__)
@@ -97,7 +99,12 @@ def main():
             na, nb = notes_of(ca), notes_of(cb)
             ka, kb = kernels_of(ca), kernels_of(cb)
             if rename:
-                paired = {rename[0].sub(rename[1], n): n for n in nb}
+                paired = {}
+                for n in nb:
+                    r = n
+                    for rx, repl in rename:
+                        r = rx.sub(repl, r)
+                    paired[r] = n
                 new = sorted(n for r, n in paired.items() if r not in na)
                 nb = {r: nb[n] for r, n in paired.items() if r in na}
                 kb = {r: kb[n] for r, n in paired.items() if r in na}
@@ -120,6 +127,11 @@ def main():
                 a, b = ka[n], kb[n]
                 kind = "identical" if a == b else "renamed" if [shape(i) for i in a] == [shape(i) for i in b] else "changed"
                 tally[kind].append(dem[n])
+                if kind == "changed":
+                    print(f"   {dem[n]}: vgpr {na[n]['vgpr_count']} -> {nb[n]['vgpr_count']}, sgpr {na[n]['sgpr_count']} -> "
+                          f"{nb[n]['sgpr_count']}, LDS {na[n]['group_segment_fixed_size']} -> {nb[n]['group_segment_fixed_size']}, "
+                          f"scratch {na[n]['private_segment_fixed_size']} -> {nb[n]['private_segment_fixed_size']}, "
+                          f"instructions {len(a)} -> {len(b)}")
                 if kind == "changed" and verbose:
                     print("\n".join(difflib.unified_diff(a, b, "before", "after", lineterm="", n=2)))
             print("   " + ", ".join(f"{k} {len(v)}" for k, v in tally.items()))
